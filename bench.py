@@ -13,16 +13,21 @@ dgl.batch + CSR + node-group plan, mvml_build_csr) -> GNNModule forward -> MVFus
 attention, Conv2d, MLP) -> BCEWithLogits (main.py:91) -> backward -> one flat RCCL all-reduce of
 the gradients (N > 1) -> Adam (main.py:88).  The SMILES and fingerprint view embeddings that
 the fusion also consumes are fixed synthetic tensors (their views are not this workload).
-After the timed steps: a view-only figure (fixed upstream gradient, the round-1 headline) and
-one inference pass over the rank's whole shard whose (B_shard, 384) embeddings are all-gathered
-into the full 1M x 384 matrix (north_star's final embedding gather).
+A plain run sets up, warms up, times the --steps steps and prints the result line; that is all.
+--full adds what else the benchmark measures: the per-kernel breakdown and rooflines (HIP events
+around every entry point of the timed steps), after the timed steps a view-only figure (fixed
+upstream gradient, the round-1 headline) and one inference pass over the rank's whole shard whose
+(B_shard, 384) embeddings are all-gathered into the full 1M x 384 matrix (north_star's final
+embedding gather), and the CPU baseline.  --dump-outputs DIR writes what the last timed step
+computed (dump_outputs below) as DIR/<name>.npy, so two builds can be compared output for output:
+the inputs, the initial weights and the dropout masks depend only on the arguments.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
 
 --gpus N without WORLD_SIZE in the environment starts N ranks itself (torch.distributed.run as
 a child process, before any GPU call); rank 0 prints the ONE JSON line (the driver's contract),
-a per-kernel breakdown goes to stderr.  --workload config5 = the skewed-size stress (per-rank
-sets, weak scaling).  --dry-run = CPU/gloo rehearsal of the launcher, sharding, all-reduce and
+with --full a per-kernel breakdown goes to stderr.  --workload config5 = the skewed-size stress
+(per-rank sets, weak scaling).  --dry-run = CPU/gloo rehearsal of the launcher, sharding, all-reduce and
 gather plumbing with a trivial stand-in model (never a measurement: no HIP code runs).
 """
 import argparse
@@ -77,13 +82,22 @@ def parse(argv=None):
                          "config3, 8192 for config5 / mvp")
     ap.add_argument("--group-size", type=int, default=64)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: per-kernel times and "
+                         "rooflines, the view-only steps, the inference pass + embedding all-gather "
+                         "and the CPU baseline (each can be switched off by its own option below)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (rank 0: logits, "
+                         "loss, the view's embeddings, every gradient and updated parameter) as "
+                         "DIR/<name>.npy in float32; large arrays as a fixed seeded sample")
     ap.add_argument("--view-only-steps", type=int, default=3,
-                    help="extra steps timed without the fusion head (fixed upstream gradient)")
+                    help="--full: extra steps timed without the fusion head (fixed upstream gradient)")
     ap.add_argument("--no-inference", action="store_true",
-                    help="skip the inference pass + embedding all-gather over the whole shard")
+                    help="--full: skip the inference pass + embedding all-gather over the whole shard")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timer", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-kernel-timer", action="store_true",
+                    help="--full: no HIP events around the entry points (no breakdown, no rooflines)")
     ap.add_argument("--proj-bf16", action="store_true",
                     help="BASELINE config 4: the GAT projection GEMMs (fc / res_fc, forward and "
                          "backward) on bf16 operands with fp32 accumulation (mvml_gemm_bf16)")
@@ -92,7 +106,10 @@ def parse(argv=None):
                          "(default: on a side stream beside it, mvml_gat.mvp.OVERLAP_VIEWS)")
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU/gloo plumbing rehearsal with a stand-in model (no measurement)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.dump_outputs is not None and args.steps < 1:
+        ap.error("--dump-outputs writes the last timed step's outputs: needs --steps >= 1")
+    return args
 
 
 def mols_per_step(args):
@@ -197,6 +214,49 @@ def alloc_stats(args):
     out["reserved_bytes"] = int(s.get("reserved_bytes.all.current", 0))
     out["peak_allocated_bytes"] = int(s.get("allocated_bytes.all.peak", 0))
     return out
+
+
+# ----------------------------------------------------------------------------- --dump-outputs
+DUMP_MAX_ELEMS = 65536       # per gradient / parameter tensor (config 3: Set2Set's LSTM alone has 66 M)
+DUMP_MAX_OUT_ELEMS = 4 << 20  # per (molecules, features) output, in whole rows (16 MiB)
+DUMP_MAX_BYTES = 64 * 2 ** 20
+
+
+def _dump_sample(t, rows):
+    """float32 numpy copy of tensor t, whole if it is small enough: else a sorted sample without
+    replacement of its rows (rows=True: a per-molecule output, DUMP_MAX_OUT_ELEMS in all) or of
+    its flattened elements (DUMP_MAX_ELEMS), drawn from a generator seeded by the tensor's shape
+    alone, so the same positions are kept in every run and every build."""
+    t = t.detach()
+    if rows:
+        n, cap = t.shape[0], max(1, DUMP_MAX_OUT_ELEMS // max(1, t.shape[1]))
+    else:
+        t = t.reshape(-1)
+        n, cap = t.numel(), DUMP_MAX_ELEMS
+    if n > cap:
+        idx = np.sort(np.random.default_rng([20240607, *t.shape]).choice(n, size=cap, replace=False))
+        t = t[torch.as_tensor(idx, device=t.device)]
+    return t.float().cpu().numpy()
+
+
+def dump_outputs(path, last, named_params):
+    """What a caller of the timed step receives from its last call, as path/<name>.npy (float32):
+    logits, loss, graph_embedding (config 3 / 5: the view's output the fusion head consumed),
+    and per parameter grad.<name> (this rank's gradient as backward left it, before the
+    all-reduce) and param.<name> (after the step's Adam update).  A parameter that got no
+    gradient (the reference's never-used LayerNorms) has no grad file."""
+    arrays = {k: _dump_sample(v, rows=v.dim() == 2) for k, v in last.items()}
+    for name, p in named_params:
+        arrays["param." + name] = _dump_sample(p, rows=False)
+        if p.grad is not None:
+            arrays["grad." + name] = _dump_sample(p.grad, rows=False)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes in {len(arrays)} arrays, over {DUMP_MAX_BYTES}")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.atleast_1d(a))
+    log(f"--dump-outputs: {len(arrays)} arrays, {total} bytes -> {path}")
 
 
 # ----------------------------------------------------------------------------- CPU baseline
@@ -445,6 +505,7 @@ def run(args):
         model = _PlumbingStandIn()
         fusion = None
         params = list(model.parameters())
+        named = list(model.named_parameters())
     elif mvp:
         import mvml_gat.mvp as mvp_mod
         from mvml_gat.mvp import MVP
@@ -457,11 +518,14 @@ def run(args):
         # every parameter, as main.py:88 passes model.parameters(): the never-used LayerNorms
         # (model.py:42, 120) keep grad None through the reducer, so Adam skips them
         params = list(full.parameters())
+        named = list(full.named_parameters())
     else:
         model = mvml_gat.GNNModule(74, [192, 384], 0.5, 6, 3,
                                    proj_dtype=torch.bfloat16 if args.proj_bf16 else None).to(dev).train()
         fusion = mvml_gat.MVFusion(384, 12, 11, 0.5).to(dev).train()
         params = list(model.parameters()) + list(fusion.parameters())
+        named = ([("gnn." + n, p) for n, p in model.named_parameters()]
+                 + [("fusion." + n, p) for n, p in fusion.named_parameters()])
     # main.py:88's Adam (lr 1e-3, weight decay 1e-4): by default mvml_gat.FlatAdam — the gradient
     # gather, the ONE all-reduce of [gradients | presence flags] and the update as HIP kernels
     # over flat buffers, no host synchronisation (MVML_BENCH_ADAM=fused / foreach: torch's Adam
@@ -478,26 +542,40 @@ def run(args):
 
     one = torch.ones((), device=dev)  # dL/dL, made once (backward() would fill one every step)
 
-    def step(b, fused=True):
+    last = {}  # --dump-outputs: what the last timed step handed back (step(keep=True))
+
+    def step(b, fused=True, keep=False):
         opt.zero_grad(set_to_none=False)
         if not args.dry_run:
             # the collation (dgl.batch + CSR + node-group plan) on the device, every step, as the
             # reference's DataLoader collates every batch (dataset.py:52-54)
             b.g.recollate()
         if mvp and fused:
-            mvml_gat.bce_with_logits(full(b.smiles, b.g, b.feats, b.fp), b.labels).backward(one)
+            logits = full(b.smiles, b.g, b.feats, b.fp)
+            loss = mvml_gat.bce_with_logits(logits, b.labels)
+            loss.backward(one)
+            if keep:
+                last.update(logits=logits.detach(), loss=loss.detach())
+            del logits, loss
             mvp_mod.join_side_stream(dev)
             reducer()
             opt.step()
             return
         out = model(b.g, b.feats)
-        if args.dry_run:
-            torch.nn.functional.binary_cross_entropy_with_logits(
-                model.fuse(b.smiles_x, out, b.fp_x), b.labels).backward()
-        elif fused:
-            mvml_gat.bce_with_logits(fusion(b.smiles_x, out, b.fp_x), b.labels).backward(one)
-        else:
+        if not fused:
             out.backward(b.upstream)
+        else:
+            if args.dry_run:
+                logits = model.fuse(b.smiles_x, out, b.fp_x)
+                loss = torch.nn.functional.binary_cross_entropy_with_logits(logits, b.labels)
+                loss.backward()
+            else:
+                logits = fusion(b.smiles_x, out, b.fp_x)
+                loss = mvml_gat.bce_with_logits(logits, b.labels)
+                loss.backward(one)
+            if keep:
+                last.update(logits=logits.detach(), loss=loss.detach(), graph_embedding=out.detach())
+            del logits, loss
         reducer()
         opt.step()
 
@@ -507,7 +585,7 @@ def run(args):
     big = max(range(nb), key=lambda j: (batches[j].E, batches[j].N))
     for i in range(args.warmup):
         step(batches[big] if i == 0 else batches[i % nb])
-    timer_on = not args.no_kernel_timer and not args.dry_run
+    timer_on = args.full and not args.no_kernel_timer and not args.dry_run
     if timer_on:
         _lib.timer.enable(TIMED)
     if adam_kind == "flat":
@@ -523,7 +601,7 @@ def run(args):
         if not args.dry_run:
             step_ev.append(torch.cuda.Event(enable_timing=True))
             step_ev[-1].record()
-        step(b)
+        step(b, keep=args.dump_outputs is not None and i == args.steps - 1)
         mols += b.B
     if not args.dry_run:
         step_ev.append(torch.cuda.Event(enable_timing=True))
@@ -535,6 +613,9 @@ def run(args):
     if timer_on:
         _lib.timer.disable()
     step_ms = [round(a.elapsed_time(b), 3) for a, b in zip(step_ev[:-1], step_ev[1:])]
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, last, named)
+    last.clear()
 
     def reduce_max(x):
         if world == 1:
@@ -666,7 +747,7 @@ def run(args):
                                   peak_allocated_gb=round(mem1["peak_allocated_bytes"] / 2 ** 30, 2))
 
     # ---- view-only figure (the graph view alone, fixed upstream gradient at its output)
-    if args.view_only_steps > 0 and not args.dry_run:
+    if args.full and args.view_only_steps > 0 and not args.dry_run:
         for b in batches:
             gen = torch.Generator(device=dev).manual_seed(99 + b.B)
             b.upstream = torch.randn((b.B, 384), device=dev, generator=gen) * 1e-3
@@ -690,7 +771,7 @@ def run(args):
             b.upstream = None
 
     # ---- inference over the whole shard + the final embedding all-gather
-    if not args.no_inference:
+    if args.full and not args.no_inference:
         model.eval()
         gather = EmbeddingAllGather()
         with torch.no_grad():
@@ -716,7 +797,7 @@ def run(args):
         model.train()
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.dry_run and not mvp:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.dry_run and not mvp:
         cpu = cpu_baseline(args.cpu_seconds, args.group_size, with_fusion=True)
 
     if rank == 0:
@@ -741,6 +822,7 @@ def run(args):
             "metric": METRIC if not args.dry_run else "DRY RUN (plumbing rehearsal, not a measurement)",
             "value": round(value, 2), "unit": "molecules/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
+            "full": args.full,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "bf16 projection, f32 elsewhere" if args.proj_bf16 else "f32",
             "data": "synthetic (seeded KEGG-like drug-like molecules, random-init weights; the "

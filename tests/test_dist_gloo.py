@@ -162,13 +162,47 @@ def test_bench_launcher_two_ranks_dry_run():
     with n_gpus 2; sharding + all-gather reproduce the single-rank embeddings exactly, and the
     DP training steps (flat all-reduce) run."""
     common = ["--total-mols", "1024", "--mols-per-step", "256"]
-    one = _run_bench("--gpus", "1", "--steps", "0", "--warmup", "0", *common)
-    two = _run_bench("--gpus", "2", "--steps", "0", "--warmup", "0", *common)
+    # (the inference pass + embedding all-gather are part of --full)
+    one = _run_bench("--gpus", "1", "--steps", "0", "--warmup", "0", "--full", *common)
+    two = _run_bench("--gpus", "2", "--steps", "0", "--warmup", "0", "--full", *common)
     assert one["n_gpus"] == 1 and two["n_gpus"] == 2
     assert two["inference"]["molecules"] == one["inference"]["molecules"] == 1024
     assert two["inference"]["checksum"] == one["inference"]["checksum"]
     trained = _run_bench("--gpus", "2", "--steps", "2", "--warmup", "1", *common)
     assert trained["n_gpus"] == 2 and trained["value"] > 0 and trained["config"]["parallelism"] == "dp2"
+
+
+def test_bench_plain_run_is_lean_and_dumps_repeatable_outputs(tmp_path):
+    """A plain run reports only the timed steps (no inference pass, view-only figure, CPU
+    baseline or rooflines: those are --full's) and still carries the headline keys;
+    --dump-outputs writes the last timed step's logits, loss, embeddings, gradients and updated
+    parameters as float32 .npy files, identical from run to run with the same arguments, and
+    changes with the number of timed steps (--steps really sets it)."""
+    common = ["--gpus", "1", "--warmup", "1", "--total-mols", "512", "--mols-per-step", "256"]
+    lines, dumps = [], []
+    for tag, steps in (("a", "2"), ("b", "2"), ("c", "3")):
+        d = tmp_path / tag
+        lines.append(_run_bench(*common, "--steps", steps, "--dump-outputs", str(d)))
+        dumps.append({f.name: np.load(f) for f in sorted(d.iterdir())})
+    line = lines[0]
+    assert line["steps"] == 2 and lines[2]["steps"] == 3 and line["full"] is False
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["roofline"] is None and line["cpu_baseline"] is None
+    assert "inference" not in line and "view_only" not in line and "kernel_ms_per_step" not in line
+    a, b, c = dumps
+    assert {"logits.npy", "loss.npy", "graph_embedding.npy", "param.lin.weight.npy",
+            "grad.lin.weight.npy", "param.head.bias.npy", "grad.head.bias.npy"} <= set(a)
+    assert all(n.endswith(".npy") for n in a) and set(a) == set(b) == set(c)
+    assert a["logits.npy"].shape == (256, 11) and a["graph_embedding.npy"].shape == (256, 384)
+    assert a["loss.npy"].shape == (1,) and np.isfinite(a["loss.npy"]).all()
+    assert a["param.lin.weight.npy"].shape == (74 * 384,)
+    for n in a:
+        assert a[n].dtype == np.float32, n
+        np.testing.assert_array_equal(a[n], b[n], err_msg=n)
+    assert sum(v.nbytes for v in a.values()) <= 64 * 2 ** 20
+    assert not np.array_equal(a["param.lin.weight.npy"], c["param.lin.weight.npy"])
 
 
 def _mvp_setup():

@@ -35,17 +35,17 @@ for P in "$@"; do
       timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > ${O}_smoke.log 2>&1
       rc=$?; tail -3 ${O}_smoke.log; [ $rc = 0 ] || exit $rc ;;
     bench)
-      timeout -k 10 600 python -u bench.py > ${O}_bench.json 2> ${O}_bench.err; rc=$?
+      timeout -k 10 600 python -u bench.py --full > ${O}_bench.json 2> ${O}_bench.err; rc=$?
       cat ${O}_bench.json; [ $rc = 0 ] || exit $rc ;;
     config5|mvp|mvpbf16)
       EXTRA=(--workload $NAME)
       [ $NAME = mvpbf16 ] && EXTRA=(--workload mvp --proj-bf16)
-      timeout -k 10 500 python -u bench.py "${EXTRA[@]}" --steps 10 --warmup 3 --no-cpu-baseline --no-inference \
+      timeout -k 10 500 python -u bench.py "${EXTRA[@]}" --steps 10 --warmup 3 --full --no-cpu-baseline --no-inference \
         > ${O}_$NAME.json 2> ${O}_$NAME.err; rc=$?; cat ${O}_$NAME.json; [ $rc = 0 ] || exit $rc ;;
     prof)
       export TMPDIR=/tmp
       timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d ${O}_prof -o run -- \
-        python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-inference > ${O}_prof.log 2>&1; rc=$?
+        python3 bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-inference > ${O}_prof.log 2>&1; rc=$?
       tail -2 ${O}_prof.log; [ $rc = 0 ] || exit $rc ;;
     ab)
       VL=${ARG:-r04,r05,.}
@@ -58,7 +58,7 @@ for P in "$@"; do
       done ;;
     dp2)  # the 2-rank DP path rehearsed on the one GPU (gloo; RCCL refuses two ranks per device)
       MVML_BENCH_ONE_DEVICE=1 MVML_BENCH_BACKEND=gloo timeout -k 10 600 python -u bench.py --gpus 2 --steps 6 \
-        --warmup 2 --no-cpu-baseline --no-inference > ${O}_dp2.json 2> ${O}_dp2.err; rc=$?
+        --warmup 2 --full --no-cpu-baseline --no-inference > ${O}_dp2.json 2> ${O}_dp2.err; rc=$?
       cat ${O}_dp2.json; [ $rc = 0 ] || exit $rc ;;
     planes)
       timeout -k 10 600 python -u tools/planes_bench.py $ARG > ${O}_planes.txt 2>&1; rc=$?
