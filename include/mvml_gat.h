@@ -753,6 +753,31 @@ int mvml_adam_flat(int64_t nchunks, const int32_t* chunk_param, const int64_t* c
                    const float* grad, float* exp_avg, float* exp_avg_sq, double lr, double beta1,
                    double beta2, double eps, double weight_decay, float grad_scale, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Multi-label metrics of one batch: main.py:32's evaluate(labels, pred) (utils.py:109-135:
+ * accuracy()'s per-row Jaccard and class mismatch counts, sklearn's average="samples"
+ * precision / recall / F1) computed on the device, with no device->host copy.
+ *   z [B][ldz] logits, y [B][ldy] labels, C classes (any C >= 1, any B >= 0; ldz, ldy >= C).
+ *   Prediction rule: p = (z >= 0); NaN gives 0 and -0.0 gives 1.  This is the reference's fp32
+ *   sigmoid(z) >= 0.5 everywhere outside a band just below zero, where the reference's own
+ *   answer depends on how its exp rounds (torch on a CPU: 1 at z = -1.2e-7, 0 at -1e-6).
+ *   A label is positive iff y >= 0.5 (the reference's labels are exact 0 / 1).
+ *   Per row, with t = |y and p|, a = |y|, b = |p|: Jaccard = t / |y or p|; precision = t / b
+ *   (0 if b = 0); recall = t / a (0 if a = 0); F1 = 2t / (a + b) (0 if a + b = 0) — sklearn's
+ *   zero-division default.  A row with an empty union (a = b = 0, where the reference divides
+ *   0 / 0) adds 0 to the Jaccard sum and is counted in sums[5].
+ *   sums[8] (fp64, OVERWRITTEN): [0..3] = sum over the rows of Jaccard, precision, recall, F1;
+ *   [4] = B; [5] = rows with an empty union; [6..7] = 0 (reserved).  B = 0 writes zeros.
+ *   class_counts [4][C] (int64, ADDED TO; the caller zeroes it): tp, fp, fn, tn per class;
+ *   fp + fn is accuracy()'s `counts` (acc_weight).  Integer atomics.
+ * The fp64 sums are added in a fixed order (per-workgroup partials in the workspace, then one
+ * workgroup over them in index order: two launches), so they are bitwise reproducible.
+ * ------------------------------------------------------------------------------------- */
+size_t mvml_multilabel_metrics_workspace_size(int64_t B, int C);
+int mvml_multilabel_metrics(int64_t B, int C, const float* z, int64_t ldz, const float* y,
+                            int64_t ldy, double* sums, int64_t* class_counts, void* workspace,
+                            size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,9 @@ Drop-in for the reference's graph view (model.py:77-95) on the HIP path:
 
 All arithmetic of the training step runs in hand-written HIP kernels (libmvml_gat.so, C ABI in
 include/mvml_gat.h); main.py:88's optimizer is ``FlatAdam(model.parameters(), lr=...,
-weight_decay=...)`` (Adam on the device, one gradient all-reduce).  There is no CPU fallback: ops raise if the library is missing or the
+weight_decay=...)`` (Adam on the device, one gradient all-reduce), main.py:32's per-batch
+``evaluate`` is ``MultiLabelMeter.update`` (one kernel, no host read-back) and main.py's loop is
+``mvml_gat.train``.  There is no CPU fallback: ops raise if the library is missing or the
 tensors are not on the GPU.
 """
 from ._lib import MvmlError, lib
@@ -17,7 +19,8 @@ from .fusion import FPNModule, MVFusion, bce_with_logits
 from .smiles import RNNModule, collate_smiles, tokens_struct
 from .nn import GAT, GATConv, GATLayer, GNNModule, GraphNorm, Set2Set
 from .optim import FlatAdam
+from .metrics import MultiLabelMeter, evaluate, evaluate_class_wise
 
-__all__ = ["GNNModule", "MVFusion", "FPNModule", "RNNModule", "tokens_struct", "collate_smiles", "bce_with_logits", "GAT", "GATLayer", "GATConv", "Set2Set", "GraphNorm", "BatchedMolGraph",
+__all__ = ["MultiLabelMeter", "evaluate", "evaluate_class_wise","GNNModule", "MVFusion", "FPNModule", "RNNModule", "tokens_struct", "collate_smiles", "bce_with_logits", "GAT", "GATLayer", "GATConv", "Set2Set", "GraphNorm", "BatchedMolGraph",
            "MolGraph", "batch", "graph", "bigraph_from_bonds", "from_arrays", "lib", "MvmlError", "FlatAdam"]
 __version__ = "0.1.0"

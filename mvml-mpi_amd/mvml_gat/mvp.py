@@ -93,7 +93,7 @@ def join_side_stream(dev):
         torch.cuda.current_stream(dev).wait_stream(_SIDE[key])
 
 
-def train_step(model, optimizer, batch, reducer=None, loss_fn=bce_with_logits):
+def train_step(model, optimizer, batch, reducer=None, loss_fn=bce_with_logits, meter=None):
     """main.py:24-36 for one batch: forward, BCEWithLogitsLoss (main.py:91), backward, the
     data-parallel flat gradient all-reduce (reducer, BASELINE config 4), optimizer step.
     batch = (smiles, graphs, atom_feats, fp_t, labels); returns the loss tensor.  Gradients are
@@ -101,10 +101,17 @@ def train_step(model, optimizer, batch, reducer=None, loss_fn=bce_with_logits):
     (set_to_none=False, main.py:34); parameters that never receive a gradient (the unused
     LayerNorms, model.py:42, 120) keep grad None — the reducer preserves that — so Adam's
     weight decay leaves them alone.  loss_fn: the HIP BCEWithLogits by default (the CPU tests
-    pass the oracle's)."""
+    pass the oracle's).  meter: a metrics.MultiLabelMeter that scores the batch where main.py:32
+    calls evaluate(labels, pred), between the forward and the loss (one more kernel on the
+    stream, no host read-back); None: nothing is scored."""
     smiles, graphs, atom_feats, fp_t, labels = batch
     optimizer.zero_grad(set_to_none=False)
-    loss = loss_fn(model(smiles, graphs, atom_feats, fp_t), labels)
+    if meter is None:
+        loss = loss_fn(model(smiles, graphs, atom_feats, fp_t), labels)
+    else:
+        logits = model(smiles, graphs, atom_feats, fp_t)
+        meter.update(labels, logits.detach())
+        loss = loss_fn(logits, labels)
     loss.backward()
     join_side_stream(atom_feats.device)
     if reducer is not None:
