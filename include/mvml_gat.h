@@ -550,8 +550,12 @@ int mvml_scale_by(int64_t n, const float* x, const float* s, float* y, void* str
  *     fwd saves per-row mean / rstd; bwd writes g_x and g_y_xhat[rows, D] = g_y * xhat, whose
  *     column sums (mvml_colsum_f32) are dL/dgamma (dL/dbeta = column sums of g_y).
  *   mvml_token_attn_fwd/_bwd: the 3-token attention of model.py:62-68 per (molecule, head);
- *     qkv rows 3b+t = [q (H*dk) | k (H*dk) | v (H*dk)] (ld >= 3 H dk), dk = 384; att [B, H, 3,
- *     dk] (the Conv2d input layout), P [B, H, 3, 3] saved softmax; scale = 1/sqrt(dk).
+ *     qkv rows 3b+t = [q (H*dk) | k (H*dk) | v (H*dk)] (ld >= 3 H dk); att [B, H, 3, dk] (the
+ *     Conv2d input layout), P [B, H, 3, 3] saved softmax; scale = 1/sqrt(dk).
+ *     Accepted dk, here and in every entry of this block that takes one: a multiple of 4 with
+ *     16 <= dk <= 384 (anything else: MVML_ERR_ARG).  dk = 384 runs the unmasked kernels; any
+ *     other width their masked instances (columns >= dk read as exact zeros, never stored), so
+ *     outputs with a leading dimension larger than their row are written inside the rows only.
  *   mvml_token_attn_fold_fwd/_bwd: the same attention with Q.K re-associated: s_ij =
  *     <p_i, x_j> scale, p = x M_h (M_h = W_q,h^T W_k,h), pv rows 3b+t = [p (H*dk) | v (H*dk)]
  *     (ld >= 2 H dk), x = the LayerNorm rows (keys of every head, ldx >= dk); the backward
@@ -588,7 +592,9 @@ int mvml_conv3_bwd(int64_t B, int C, int O, int W, const float* in, const float*
                    const float* out, const float* g_out, float* g_in, float* g_weight,
                    float* g_bias, void* workspace, size_t workspace_bytes, void* stream);
 /* mvml_attn_conv_fwd / _bwd: mvml_token_attn_fold_fwd + mvml_conv3_fwd (and the backward pair)
- * fused, H = 12, dk = 384: the (B, 12, 3, 384) attention cube lives only in LDS.  Forward
+ * fused, H = 12, dk a multiple of 4 in [16, 384]: the (B, 12, 3, dk) attention cube lives only
+ * in LDS.  The backward stages pv's v columns, P, out and g_out in 16-byte pieces: those four
+ * pointers must be 16-byte aligned and ld a multiple of 4 (else MVML_ERR_ARG).  Forward
  * writes P [B, H, 3, 3] (saved softmax) and out [B, 12, dk - 2] (post-ReLU); the backward
  * recomputes the cube from P and pv's v columns and writes g_pv, g_k (as
  * mvml_token_attn_fold_bwd), g_weight, g_bias (as mvml_conv3_bwd; workspace

@@ -11,6 +11,9 @@
 //     per output column computes all 12 output channels (weights as uniform LDS broadcasts).
 //     Weight gradients: per-workgroup partials over a run of molecules, summed in fixed order
 //     by a second kernel (deterministic, no atomics).
+// 384 above is the default head width D = hidden_feats[-1]; the token-attention and fused kernels
+// take any multiple of 4 in [16, 384] (templates over <kMask, kV>, see col_ld below), the
+// LayerNorm rows up to 512 and the convolution any 3 <= W <= 384.
 #include "common.h"
 #include "dropout.h"
 
@@ -98,8 +101,39 @@ layernorm_bwd_kernel(int64_t rows, int D, const float* __restrict__ x, int64_t l
 //   q/k/v of token t = QKV row 3b+t, columns [h*dk | HD + h*dk | 2HD + h*dk] (dk wide)
 //   s_ij = <q_i, k_j> * scale;  p = softmax_j(s);  att[b][h][i] = sum_j p_ij v_j
 constexpr int NT = 3;
-constexpr int kDkVpl = 6;  // dk = 384 = 6 x 64
+constexpr int kDkVpl = 6;  // dk <= 384 = 6 x 64: lane l covers the columns l + 64 i, i < 6
 
+// Every kernel below is a template over <kMask, kV>, kV = ceil(dk / 64) the 64-column groups a
+// lane holds.  <false, 6> is the dk = 384 instance: six full groups, no column test anywhere
+// (the helpers fold away).  <true, kV> takes any dk in (64 (kV - 1), 64 kV]: the groups
+// i < kV - 1 are full, and only the last one is masked.  A column c >= dk of that group is read
+// from the always-in-range address of column dk - 1 and replaced by an exact 0 by a select (so
+// it adds nothing to a dot product or a maximum, and no load is branched around), and is never
+// stored.
+template <bool kMask, int kV>
+__device__ __forceinline__ bool col_ok(int lane, int i, int dk) {
+  return (kMask && i == kV - 1) ? lane + 64 * i < dk : true;
+}
+// column lane + 64 i of the dk-wide row that starts at base[off]
+template <bool kMask, int kV, typename Off>
+__device__ __forceinline__ float col_ld(const float* base, Off off, int lane, int i, int dk) {
+  if (kMask && i == kV - 1) {
+    const float v = base[off + min(lane + 64 * i, dk - 1)];
+    return lane + 64 * i < dk ? v : 0.f;
+  }
+  return base[off + lane + 64 * i];
+}
+// the same with the column c = lane + 64 i formed by the caller (base[off + c])
+template <bool kMask, int kV, typename Off>
+__device__ __forceinline__ float col_ldc(const float* base, Off off, int c, int i, int dk) {
+  if (kMask && i == kV - 1) {
+    const float v = base[off + min(c, dk - 1)];
+    return c < dk ? v : 0.f;
+  }
+  return base[off + c];
+}
+
+template <bool kMask, int kV>
 __global__ void __launch_bounds__(256)
 token_attn_fwd_kernel(int64_t B, int H, int dk, const float* __restrict__ qkv, int64_t ld,
                       float scale, float* __restrict__ att, float* __restrict__ P) {
@@ -109,16 +143,16 @@ token_attn_fwd_kernel(int64_t B, int H, int dk, const float* __restrict__ qkv, i
   const int64_t b = w / H;
   const int h = (int)(w % H);
   const int64_t HD = (int64_t)H * dk;
-  float q[NT][kDkVpl], k[NT][kDkVpl], v[NT][kDkVpl];
+  float q[NT][kV], k[NT][kV], v[NT][kV];
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
     const float* row = qkv + (b * NT + t) * ld + (int64_t)h * dk;
 #pragma unroll
-    for (int i = 0; i < kDkVpl; ++i) {
+    for (int i = 0; i < kV; ++i) {
       const int c = lane + 64 * i;
-      q[t][i] = row[c];
-      k[t][i] = row[HD + c];
-      v[t][i] = row[2 * HD + c];
+      q[t][i] = col_ldc<kMask, kV>(row, 0, c, i, dk);
+      k[t][i] = col_ldc<kMask, kV>(row, HD, c, i, dk);
+      v[t][i] = col_ldc<kMask, kV>(row, 2 * HD, c, i, dk);
     }
   }
   float p[NT][NT];
@@ -128,7 +162,7 @@ token_attn_fwd_kernel(int64_t B, int H, int dk, const float* __restrict__ qkv, i
     for (int c = 0; c < NT; ++c) {
       float s = 0.f;
 #pragma unroll
-      for (int i = 0; i < kDkVpl; ++i) s = fmaf(q[a][i], k[c][i], s);
+      for (int i = 0; i < kV; ++i) s = fmaf(q[a][i], k[c][i], s);
       p[a][c] = wsum(s) * scale;
     }
 #pragma unroll
@@ -147,11 +181,11 @@ token_attn_fwd_kernel(int64_t B, int H, int dk, const float* __restrict__ qkv, i
 #pragma unroll
   for (int a = 0; a < NT; ++a)
 #pragma unroll
-    for (int i = 0; i < kDkVpl; ++i) {
+    for (int i = 0; i < kV; ++i) {
       float o = 0.f;
 #pragma unroll
       for (int c = 0; c < NT; ++c) o = fmaf(p[a][c], v[c][i], o);
-      out[a * dk + lane + 64 * i] = o;
+      if (col_ok<kMask, kV>(lane, i, dk)) out[a * dk + lane + 64 * i] = o;
     }
   if (lane < NT * NT) {
     float pv = p[0][0];
@@ -164,6 +198,7 @@ token_attn_fwd_kernel(int64_t B, int H, int dk, const float* __restrict__ qkv, i
 // Backward of token_attn_fwd: g_v_j = sum_i p_ij g_i;  g_p_ij = <g_i, v_j>;
 // g_s_ij = p_ij (g_p_ij - sum_j' p_ij' g_p_ij');  g_q_i = scale sum_j g_s_ij k_j;
 // g_k_j = scale sum_i g_s_ij q_i.  gqkv has the layout of qkv.
+template <bool kMask, int kV>
 __global__ void __launch_bounds__(256)
 token_attn_bwd_kernel(int64_t B, int H, int dk, const float* __restrict__ qkv, int64_t ld,
                       float scale, const float* __restrict__ P, const float* __restrict__ g_att,
@@ -177,16 +212,16 @@ token_attn_bwd_kernel(int64_t B, int H, int dk, const float* __restrict__ qkv, i
   float p[NT][NT];
 #pragma unroll
   for (int e = 0; e < NT * NT; ++e) p[e / NT][e % NT] = P[w * NT * NT + e];
-  float g[NT][kDkVpl], v[NT][kDkVpl];
+  float g[NT][kV], v[NT][kV];
   const float* ga = g_att + w * NT * dk;
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
     const float* row = qkv + (b * NT + t) * ld + (int64_t)h * dk;
 #pragma unroll
-    for (int i = 0; i < kDkVpl; ++i) {
+    for (int i = 0; i < kV; ++i) {
       const int c = lane + 64 * i;
-      g[t][i] = ga[t * dk + c];
-      v[t][i] = row[2 * HD + c];
+      g[t][i] = col_ldc<kMask, kV>(ga, t * dk, c, i, dk);
+      v[t][i] = col_ldc<kMask, kV>(row, 2 * HD, c, i, dk);
     }
   }
   float gs[NT][NT];
@@ -197,7 +232,7 @@ token_attn_bwd_kernel(int64_t B, int H, int dk, const float* __restrict__ qkv, i
     for (int c = 0; c < NT; ++c) {
       float s = 0.f;
 #pragma unroll
-      for (int i = 0; i < kDkVpl; ++i) s = fmaf(g[a][i], v[c][i], s);
+      for (int i = 0; i < kV; ++i) s = fmaf(g[a][i], v[c][i], s);
       gp[c] = wsum(s);
     }
     const float dot = p[a][0] * gp[0] + p[a][1] * gp[1] + p[a][2] * gp[2];
@@ -209,36 +244,38 @@ token_attn_bwd_kernel(int64_t B, int H, int dk, const float* __restrict__ qkv, i
   for (int c = 0; c < NT; ++c) {
     float* grow = gqkv + (b * NT + c) * ldg + (int64_t)h * dk;
 #pragma unroll
-    for (int i = 0; i < kDkVpl; ++i) {
+    for (int i = 0; i < kV; ++i) {
       float o = 0.f;
 #pragma unroll
       for (int a = 0; a < NT; ++a) o = fmaf(p[a][c], g[a][i], o);
-      grow[2 * HD + lane + 64 * i] = o;
+      if (col_ok<kMask, kV>(lane, i, dk)) grow[2 * HD + lane + 64 * i] = o;
     }
   }
-  float q[NT][kDkVpl], k[NT][kDkVpl];
+  float q[NT][kV], k[NT][kV];
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
     const float* row = qkv + (b * NT + t) * ld + (int64_t)h * dk;
 #pragma unroll
-    for (int i = 0; i < kDkVpl; ++i) {
-      q[t][i] = row[lane + 64 * i];
-      k[t][i] = row[HD + lane + 64 * i];
+    for (int i = 0; i < kV; ++i) {
+      q[t][i] = col_ld<kMask, kV>(row, 0, lane, i, dk);
+      k[t][i] = col_ld<kMask, kV>(row, HD, lane, i, dk);
     }
   }
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
     float* grow = gqkv + (b * NT + t) * ldg + (int64_t)h * dk;
 #pragma unroll
-    for (int i = 0; i < kDkVpl; ++i) {
+    for (int i = 0; i < kV; ++i) {
       float oq = 0.f, ok = 0.f;
 #pragma unroll
       for (int c = 0; c < NT; ++c) {
         oq = fmaf(gs[t][c], k[c][i], oq);
         ok = fmaf(gs[c][t], q[c][i], ok);
       }
-      grow[lane + 64 * i] = oq;
-      grow[HD + lane + 64 * i] = ok;
+      if (col_ok<kMask, kV>(lane, i, dk)) {
+        grow[lane + 64 * i] = oq;
+        grow[HD + lane + 64 * i] = ok;
+      }
     }
   }
 }
@@ -246,8 +283,9 @@ token_attn_bwd_kernel(int64_t B, int H, int dk, const float* __restrict__ qkv, i
 // Softmax backward of one head's 3 x 3 scores: g_p_ac = <g_a, v_c> (wave sums), then
 // g_s_ac = p_ac (g_p_ac - sum_c' p_ac' g_p_ac') scale, with every product and sum explicit (no
 // contraction left to the compiler), so the fused and unfused kernels agree bit for bit.
-__device__ __forceinline__ void fold_grad_scores(const float (&g)[NT][kDkVpl],
-                                                 const float (&v)[NT][kDkVpl],
+template <int kV>
+__device__ __forceinline__ void fold_grad_scores(const float (&g)[NT][kV],
+                                                 const float (&v)[NT][kV],
                                                  const float (&p)[NT][NT], float scale,
                                                  float (&gs)[NT][NT]) {
 #pragma unroll
@@ -257,7 +295,7 @@ __device__ __forceinline__ void fold_grad_scores(const float (&g)[NT][kDkVpl],
     for (int c = 0; c < NT; ++c) {
       float sc = 0.f;
 #pragma unroll
-      for (int i = 0; i < kDkVpl; ++i) sc = fmaf(g[a][i], v[c][i], sc);
+      for (int i = 0; i < kV; ++i) sc = fmaf(g[a][i], v[c][i], sc);
       gp[c] = wsum(sc);
     }
     const float dot = fmaf(p[a][2], gp[2], fmaf(p[a][1], gp[1], __fmul_rn(p[a][0], gp[0])));
@@ -274,6 +312,7 @@ __device__ __forceinline__ void fold_grad_scores(const float (&g)[NT][kDkVpl],
 // over the heads in registers (fixed order) into g_k = sum_h g_k,h, so the data-gradient GEMM
 // also runs over 2 H D columns.
 //   pv rows 3b+t = [p (H dk) | v (H dk)] (ld >= 2 H dk); x rows 3b+t (dk); att, P as above.
+template <bool kMask, int kV>
 __global__ void __launch_bounds__(256)
 token_attn_fold_fwd_kernel(int64_t B, int H, int dk, const float* __restrict__ pv, int64_t ld,
                            const float* __restrict__ x, int64_t ldx, float scale,
@@ -282,20 +321,20 @@ token_attn_fold_fwd_kernel(int64_t B, int H, int dk, const float* __restrict__ p
   const int lane = threadIdx.x & 63;
   if (b >= B) return;
   const int64_t HD = (int64_t)H * dk;
-  float k[NT][kDkVpl];
+  float k[NT][kV];
 #pragma unroll
   for (int t = 0; t < NT; ++t)
 #pragma unroll
-    for (int i = 0; i < kDkVpl; ++i) k[t][i] = x[(b * NT + t) * ldx + lane + 64 * i];
+    for (int i = 0; i < kV; ++i) k[t][i] = col_ld<kMask, kV>(x, (b * NT + t) * ldx, lane, i, dk);
   for (int h = 0; h < H; ++h) {
-    float q[NT][kDkVpl], v[NT][kDkVpl];
+    float q[NT][kV], v[NT][kV];
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
       const float* row = pv + (b * NT + t) * ld + (int64_t)h * dk;
 #pragma unroll
-      for (int i = 0; i < kDkVpl; ++i) {
-        q[t][i] = row[lane + 64 * i];
-        v[t][i] = row[HD + lane + 64 * i];
+      for (int i = 0; i < kV; ++i) {
+        q[t][i] = col_ld<kMask, kV>(row, 0, lane, i, dk);
+        v[t][i] = col_ld<kMask, kV>(row, HD, lane, i, dk);
       }
     }
     float p[NT][NT];
@@ -305,7 +344,7 @@ token_attn_fold_fwd_kernel(int64_t B, int H, int dk, const float* __restrict__ p
       for (int c = 0; c < NT; ++c) {
         float sc = 0.f;
 #pragma unroll
-        for (int i = 0; i < kDkVpl; ++i) sc = fmaf(q[a][i], k[c][i], sc);
+        for (int i = 0; i < kV; ++i) sc = fmaf(q[a][i], k[c][i], sc);
         p[a][c] = wsum(sc) * scale;
       }
 #pragma unroll
@@ -325,11 +364,11 @@ token_attn_fold_fwd_kernel(int64_t B, int H, int dk, const float* __restrict__ p
 #pragma unroll
     for (int a = 0; a < NT; ++a)
 #pragma unroll
-      for (int i = 0; i < kDkVpl; ++i) {
+      for (int i = 0; i < kV; ++i) {
         float o = 0.f;
 #pragma unroll
         for (int c = 0; c < NT; ++c) o = fmaf(p[a][c], v[c][i], o);
-        out[a * dk + lane + 64 * i] = o;
+        if (col_ok<kMask, kV>(lane, i, dk)) out[a * dk + lane + 64 * i] = o;
       }
     if (lane < NT * NT) {
       float pvv = p[0][0];
@@ -342,6 +381,7 @@ token_attn_fold_fwd_kernel(int64_t B, int H, int dk, const float* __restrict__ p
 
 // Backward of token_attn_fold_fwd: g_v_j = sum_i p_ij g_i; g_s = p (g_p - <p, g_p>) scale;
 // g_p_i = sum_j g_s_ij x_j; g_k_j = sum_h sum_i g_s_ij p_i (heads in order).
+template <bool kMask, int kV>
 __global__ void __launch_bounds__(256)
 token_attn_fold_bwd_kernel(int64_t B, int H, int dk, const float* __restrict__ pv, int64_t ld,
                            const float* __restrict__ x, int64_t ldx, float scale,
@@ -353,12 +393,12 @@ token_attn_fold_bwd_kernel(int64_t B, int H, int dk, const float* __restrict__ p
   if (b >= B) return;
   float gmx = 0.f;  // |max| of this lane's gpv stores (split-fp16 scale of the two GEMMs)
   const int64_t HD = (int64_t)H * dk;
-  float k[NT][kDkVpl], gks[NT][kDkVpl];
+  float k[NT][kV], gks[NT][kV];
 #pragma unroll
   for (int t = 0; t < NT; ++t)
 #pragma unroll
-    for (int i = 0; i < kDkVpl; ++i) {
-      k[t][i] = x[(b * NT + t) * ldx + lane + 64 * i];
+    for (int i = 0; i < kV; ++i) {
+      k[t][i] = col_ld<kMask, kV>(x, (b * NT + t) * ldx, lane, i, dk);
       gks[t][i] = 0.f;
     }
   for (int h = 0; h < H; ++h) {
@@ -366,15 +406,15 @@ token_attn_fold_bwd_kernel(int64_t B, int H, int dk, const float* __restrict__ p
     float p[NT][NT];
 #pragma unroll
     for (int e = 0; e < NT * NT; ++e) p[e / NT][e % NT] = P[w * NT * NT + e];
-    float g[NT][kDkVpl], v[NT][kDkVpl];
+    float g[NT][kV], v[NT][kV];
     const float* ga = g_att + w * NT * dk;
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
       const float* row = pv + (b * NT + t) * ld + (int64_t)h * dk;
 #pragma unroll
-      for (int i = 0; i < kDkVpl; ++i) {
-        g[t][i] = ga[t * dk + lane + 64 * i];
-        v[t][i] = row[HD + lane + 64 * i];
+      for (int i = 0; i < kV; ++i) {
+        g[t][i] = col_ld<kMask, kV>(ga, t * dk, lane, i, dk);
+        v[t][i] = col_ld<kMask, kV>(row, HD, lane, i, dk);
       }
     }
     float gs[NT][NT];
@@ -383,33 +423,33 @@ token_attn_fold_bwd_kernel(int64_t B, int H, int dk, const float* __restrict__ p
     for (int c = 0; c < NT; ++c) {
       float* grow = gpv + (b * NT + c) * ldg + (int64_t)h * dk;
 #pragma unroll
-      for (int i = 0; i < kDkVpl; ++i) {
+      for (int i = 0; i < kV; ++i) {
         float o = 0.f;
 #pragma unroll
         for (int a = 0; a < NT; ++a) o = fmaf(p[a][c], g[a][i], o);
-        grow[HD + lane + 64 * i] = o;
+        if (col_ok<kMask, kV>(lane, i, dk)) grow[HD + lane + 64 * i] = o;
         gmx = fmaxf(gmx, fabsf(o));
       }
     }
-    float q[NT][kDkVpl];
+    float q[NT][kV];
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
       const float* row = pv + (b * NT + t) * ld + (int64_t)h * dk;
 #pragma unroll
-      for (int i = 0; i < kDkVpl; ++i) q[t][i] = row[lane + 64 * i];
+      for (int i = 0; i < kV; ++i) q[t][i] = col_ld<kMask, kV>(row, 0, lane, i, dk);
     }
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
       float* grow = gpv + (b * NT + t) * ldg + (int64_t)h * dk;
 #pragma unroll
-      for (int i = 0; i < kDkVpl; ++i) {
+      for (int i = 0; i < kV; ++i) {
         float oq = 0.f, ok = 0.f;
 #pragma unroll
         for (int c = 0; c < NT; ++c) {
           oq = fmaf(gs[t][c], k[c][i], oq);
           ok = fmaf(gs[c][t], q[c][i], ok);
         }
-        grow[lane + 64 * i] = oq;
+        if (col_ok<kMask, kV>(lane, i, dk)) grow[lane + 64 * i] = oq;
         gmx = fmaxf(gmx, fabsf(oq));
         gks[t][i] += ok;
       }
@@ -418,7 +458,8 @@ token_attn_fold_bwd_kernel(int64_t B, int H, int dk, const float* __restrict__ p
 #pragma unroll
   for (int t = 0; t < NT; ++t)
 #pragma unroll
-    for (int i = 0; i < kDkVpl; ++i) gk[(b * NT + t) * ldgk + lane + 64 * i] = gks[t][i];
+    for (int i = 0; i < kV; ++i)
+      if (col_ok<kMask, kV>(lane, i, dk)) gk[(b * NT + t) * ldgk + lane + 64 * i] = gks[t][i];
   if (gpv_amax) {  // one unsigned atomicMax of the float bits per wave (waves may exit early)
     gmx = wave_max(gmx);
     if (lane == 0) atomicMax(gpv_amax, __float_as_uint(gmx));
@@ -888,7 +929,8 @@ constexpr int kFuseG = kConvO * kConvLd;          // g_pre rows o
 static_assert(kFuseW <= kConvLd - 1, "one pad column per cube row");
 
 // softmax(scale * <q_a, k_c>) over c for the 3 x 3 scores of one head (token_attn_fold_fwd's order)
-__device__ __forceinline__ void fold_scores(const float (&q)[NT][kDkVpl], const float (&k)[NT][kDkVpl],
+template <int kV>
+__device__ __forceinline__ void fold_scores(const float (&q)[NT][kV], const float (&k)[NT][kV],
                                             float scale, float (&p)[NT][NT]) {
 #pragma unroll
   for (int a = 0; a < NT; ++a)
@@ -896,7 +938,7 @@ __device__ __forceinline__ void fold_scores(const float (&q)[NT][kDkVpl], const 
     for (int c = 0; c < NT; ++c) {
       float sc = 0.f;
 #pragma unroll
-      for (int i = 0; i < kDkVpl; ++i) sc = fmaf(q[a][i], k[c][i], sc);
+      for (int i = 0; i < kV; ++i) sc = fmaf(q[a][i], k[c][i], sc);
       p[a][c] = wsum(sc) * scale;
     }
 #pragma unroll
@@ -913,36 +955,44 @@ __device__ __forceinline__ void fold_scores(const float (&q)[NT][kDkVpl], const 
   }
 }
 
-// att rows (h, a) = sum_c p_ac v_c into the LDS cube (row stride kConvLd)
-__device__ __forceinline__ void fold_att_lds(const float (&p)[NT][NT], const float (&v)[NT][kDkVpl],
-                                             float* s_rows, int lane) {
+// att rows (h, a) = sum_c p_ac v_c into the LDS cube (row stride kConvLd at every width; the
+// columns >= W of a row are not written)
+template <bool kMask, int kV>
+__device__ __forceinline__ void fold_att_lds(const float (&p)[NT][NT], const float (&v)[NT][kV],
+                                             float* s_rows, int lane, int W) {
 #pragma unroll
   for (int a = 0; a < NT; ++a)
 #pragma unroll
-    for (int i = 0; i < kDkVpl; ++i) {
+    for (int i = 0; i < kV; ++i) {
       float o = 0.f;
 #pragma unroll
       for (int c = 0; c < NT; ++c) o = fmaf(p[a][c], v[c][i], o);
-      s_rows[a * kConvLd + lane + 64 * i] = o;
+      if (col_ok<kMask, kV>(lane, i, W)) s_rows[a * kConvLd + lane + 64 * i] = o;
     }
 }
 
+template <bool kMask, int kV>
 __device__ __forceinline__ void load_rows3(const float* __restrict__ base, int64_t ld, int lane,
-                                           float (&r)[NT][kDkVpl]) {
+                                           float (&r)[NT][kV], int W) {
 #pragma unroll
   for (int t = 0; t < NT; ++t)
 #pragma unroll
-    for (int i = 0; i < kDkVpl; ++i) r[t][i] = base[t * ld + lane + 64 * i];
+    for (int i = 0; i < kV; ++i) r[t][i] = col_ld<kMask, kV>(base, t * ld, lane, i, W);
 }
 
+// kMask = false: W = 384 at compile time (dk is not read); kMask = true: W = dk, a multiple of 4
+// in [16, 384].  The cube keeps its 385-float row stride, so a wave's column tiles and every
+// LDS offset are the 384 instance's; waves whose tile starts at or past W - 2 skip the MFMA steps.
+template <bool kMask, int kV>
 __global__ void __launch_bounds__(kFuseThreads, 3)  // one workgroup per CU
 attn_conv_fwd_kernel(int64_t B, int64_t per_block, const float* __restrict__ pv, int64_t ld,
                      const float* __restrict__ x, int64_t ldx, float scale,
                      const float* __restrict__ wgt, const float* __restrict__ bias,
                      float* __restrict__ P, float* __restrict__ out, uint32_t drop_thr,
-                     float drop_scale, uint64_t drop_seed) {
-  constexpr int W = kFuseW, Wo = W - 2, H = kConvC;
-  constexpr int64_t HD = (int64_t)H * W;
+                     float drop_scale, uint64_t drop_seed, int dk) {
+  constexpr int H = kConvC;
+  const int W = kMask ? dk : kFuseW, Wo = W - 2;
+  const int64_t HD = (int64_t)H * W;
   __shared__ float s_in[kFuseCube];
   const int tid = threadIdx.x, lane = tid & 63, h = tid >> 6;
   const int lo = lane & 15, lk = lane >> 4;
@@ -956,11 +1006,11 @@ attn_conv_fwd_kernel(int64_t B, int64_t per_block, const float* __restrict__ pv,
   const int64_t b0 = (int64_t)blockIdx.x * per_block, b1 = min(B, b0 + per_block);
   // head h's rows of molecule b: keys (the LayerNorm rows), p and v; the next molecule's are
   // loaded while this one's convolution runs
-  float k[NT][kDkVpl], q[NT][kDkVpl], v[NT][kDkVpl];
+  float k[NT][kV], q[NT][kV], v[NT][kV];
   auto load = [&](int64_t b) {
-    load_rows3(x + b * NT * ldx, ldx, lane, k);
-    load_rows3(pv + b * NT * ld + (int64_t)h * W, ld, lane, q);
-    load_rows3(pv + b * NT * ld + HD + (int64_t)h * W, ld, lane, v);
+    load_rows3<kMask>(x + b * NT * ldx, ldx, lane, k, W);
+    load_rows3<kMask>(pv + b * NT * ld + (int64_t)h * W, ld, lane, q, W);
+    load_rows3<kMask>(pv + b * NT * ld + HD + (int64_t)h * W, ld, lane, v, W);
   };
   if (b0 < b1) load(b0);
   for (int64_t b = b0; b < b1; ++b) {
@@ -968,7 +1018,7 @@ attn_conv_fwd_kernel(int64_t B, int64_t per_block, const float* __restrict__ pv,
     {
       float p[NT][NT];
       fold_scores(q, k, scale, p);
-      fold_att_lds(p, v, s_in + h * NT * kConvLd, lane);
+      fold_att_lds<kMask>(p, v, s_in + h * NT * kConvLd, lane, W);
       if (lane < NT * NT) {
         float pvv = p[0][0];
 #pragma unroll
@@ -980,6 +1030,7 @@ attn_conv_fwd_kernel(int64_t B, int64_t per_block, const float* __restrict__ pv,
     __syncthreads();
     // Conv2d + bias + ReLU on the matrix cores (conv3_fwd3_kernel): wave h the column tiles
     // [32 h, 32 h + 32)
+    if (kMask && 32 * h >= Wo) continue;  // no output column in this wave's tiles (wave-uniform)
     f32x4_t acc[2];
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct) acc[ct] = f32x4_t{0.f, 0.f, 0.f, 0.f};
@@ -1028,6 +1079,11 @@ attn_conv_fwd_kernel(int64_t B, int64_t per_block, const float* __restrict__ pv,
 //       gradient partial over head h's own cube rows, then the twelve partials in head order.
 // Staging (one __shared__ array): cube [36 x 385 + 8] | g_out [18 KB] | out [18 KB] | v [3 x
 // 4608] | P [108 + pad], each region a whole number of 1-KB DMA pieces.
+// At a width W < 384 (kMask) the layout, the piece counts and every wave's share of the pieces
+// stay the 384 ones: a molecule's g_out / out block (12 (W - 2) floats) and each v row (12 W
+// floats) fill the front of their regions, and a lane whose float4 would start past the end of
+// its source re-reads the source's last float4 (an aligned, in-range address: 48 (W - 2) and
+// 48 W bytes are multiples of 16) into LDS words nothing reads.
 constexpr int kStG = 18;                       // 1-KB pieces of a molecule's g_out (4584 floats)
 constexpr int kStV = 54;                       // v: 3 rows x 4608 floats
 constexpr int kStVP = kStV + 1;                // + P (108 floats)
@@ -1036,6 +1092,7 @@ constexpr int kOffO = kOffG + kStG * 256;
 constexpr int kOffV = kOffO + kStG * 256;
 constexpr int kOffP = kOffV + kStV * 256;
 constexpr int kBwdLds = kOffP + 256;
+constexpr int kStVRow = (kStV / NT) * 256;    // LDS stride of the staged v rows (= 12 x 384)
 static_assert(kBwdLds * 4 <= 160 * 1024, "backward staging fits the CU's LDS");
 static_assert(kConvO * (kFuseW - 2) <= kStG * 256, "g_out rows fit their staging");
 
@@ -1055,9 +1112,10 @@ __device__ __forceinline__ void glds16(const float* src, float* dst) {
 
 // molecule b's g_out and out rows (contiguous 4584-float blocks) into their staging rows:
 // pieces h and h + 12 of each (18 pieces), lanes past the block re-read its last float4
+template <bool kMask>
 __device__ __forceinline__ void stage_go(const float* __restrict__ g_out, const float* __restrict__ out,
-                                         int64_t b, float* lds, int h, int lane) {
-  constexpr int n = kConvO * (kFuseW - 2);
+                                         int64_t b, float* lds, int h, int lane, int W) {
+  const int n = kConvO * ((kMask ? W : kFuseW) - 2);
   const int64_t base = b * (int64_t)n;
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
@@ -1074,21 +1132,28 @@ __device__ __forceinline__ void stage_go(const float* __restrict__ g_out, const 
 // pieces 5 h .. 5 h + 4 of the 55; wave 11's five (and nothing else) repeat the P piece — every
 // wave issues exactly five, so the compiler's wait for the query / key loads issued before them
 // is vmcnt(5), not a drain of the next molecule's staging
+template <bool kMask>
 __device__ __forceinline__ void stage_vp(const float* __restrict__ pv, int64_t ld,
                                          const float* __restrict__ P, int64_t b, float* lds, int h,
-                                         int lane) {
-  constexpr int64_t HD = (int64_t)kConvC * kFuseW;
+                                         int lane, int W) {
+  const int64_t HD = (int64_t)kConvC * (kMask ? W : kFuseW);
   const float* pb = uniform_ptr(P + b * (kConvC * NT * NT)) + min(4 * lane, kConvC * NT * NT - 4);
 #pragma unroll
   for (int k = 0; k < 5; ++k) {  // branch-free (selects): the wait counts stay exact
     const int piece = 5 * h + k;
     const int t = min(piece, kStV - 1) / 18;
-    const float* vb = uniform_ptr(pv + (b * NT + t) * ld + HD + (min(piece, kStV - 1) % 18) * 256) + 4 * lane;
+    const float* vb;
+    if (kMask)  // a lane past the end of the 12 W-float row re-reads the row's last float4
+      vb = uniform_ptr(pv + (b * NT + t) * ld + HD) +
+           min((min(piece, kStV - 1) % 18) * 256 + 4 * lane, (int)HD - 4);
+    else
+      vb = uniform_ptr(pv + (b * NT + t) * ld + HD + (min(piece, kStV - 1) % 18) * 256) + 4 * lane;
     const bool isv = piece < kStV;  // else the P piece (repeats write the same bytes)
     glds16(isv ? vb : pb, lds + (isv ? kOffV + piece * 256 : kOffP));
   }
 }
 
+template <bool kMask, int kV>
 __global__ void __launch_bounds__(kFuseThreads, 3)  // one workgroup per CU
 attn_conv_bwd_kernel(int64_t B, int64_t per_block, const float* __restrict__ pv, int64_t ld,
                      const float* __restrict__ x, int64_t ldx, float scale,
@@ -1096,14 +1161,15 @@ attn_conv_bwd_kernel(int64_t B, int64_t per_block, const float* __restrict__ pv,
                      const float* __restrict__ out, const float* __restrict__ g_out, float g_scale,
                      float* __restrict__ gpv, int64_t ldg, float* __restrict__ gk, int64_t ldgk,
                      uint32_t* __restrict__ gpv_amax, float* __restrict__ part,
-                     uint32_t* __restrict__ gpv_rows) {
-  constexpr int W = kFuseW, Wo = W - 2, H = kConvC;
-  constexpr int64_t HD = (int64_t)H * W;
+                     uint32_t* __restrict__ gpv_rows, int dk) {
+  constexpr int H = kConvC;
+  const int W = kMask ? dk : kFuseW, Wo = W - 2;
+  const int64_t HD = (int64_t)H * W;
   constexpr int kCD = kConvC * kConvH / 2;  // cube-gradient rows per thread
   __shared__ __attribute__((aligned(16))) float lds[kBwdLds];
   float* s_in = lds;
   const float* s_o = lds + kOffO;
-  const float* s_v = lds + kOffV;   // [3][12 x 384]
+  const float* s_v = lds + kOffV;   // [3][12 x W], row stride kStVRow
   const float* s_p = lds + kOffP;   // [12][9]
   const int tid = threadIdx.x, lane = tid & 63;
   const int h = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform: scalar branches
@@ -1128,12 +1194,16 @@ attn_conv_bwd_kernel(int64_t B, int64_t per_block, const float* __restrict__ pv,
     return (xx >= 0 && xx < Wo) ? v : 0.f;
   };
   float gmx = 0.f, pb = 0.f;
-  // cube-gradient role; half is wave-uniform (W = 6 waves), so its weights are scalar loads
-  const int xp = tid % W, half = __builtin_amdgcn_readfirstlane(tid / W);
+  // cube-gradient role; half is wave-uniform (W = 6 waves), so its weights are scalar loads.
+  // kMask: the split is by W rounded up to whole waves (Wr <= 384), so half stays wave-uniform;
+  // the lanes xp >= W of a wave compute on clamped addresses and store nothing, the waves past
+  // 2 Wr threads (half >= 2) skip the role
+  const int Wr = kMask ? (W + 63) & ~63 : W;
+  const int xp = tid % Wr, half = __builtin_amdgcn_readfirstlane(tid / Wr);
   const int64_t b0 = (int64_t)blockIdx.x * per_block, b1 = min(B, b0 + per_block);
   if (b0 < b1) {
-    stage_go(g_out, out, b0, lds, h, lane);
-    stage_vp(pv, ld, P, b0, lds, h, lane);
+    stage_go<kMask>(g_out, out, b0, lds, h, lane, W);
+    stage_vp<kMask>(pv, ld, P, b0, lds, h, lane, W);
   }
   for (int64_t b = b0; b < b1; ++b) {
     const bool next = b + 1 < b1;
@@ -1144,35 +1214,48 @@ attn_conv_bwd_kernel(int64_t B, int64_t per_block, const float* __restrict__ pv,
       s_gp[e] = s_o[e] > 0.f ? (g_scale == 1.f ? s_gp[e] : s_gp[e] * g_scale) : 0.f;
     // (B) the cube rows of head h
     {
-      float p[NT][NT], v[NT][kDkVpl];
+      float p[NT][NT], v[NT][kV];
 #pragma unroll
       for (int e = 0; e < NT * NT; ++e) p[e / NT][e % NT] = s_p[h * NT * NT + e];
-      load_rows3(s_v + (int64_t)h * W, HD, lane, v);
-      fold_att_lds(p, v, s_in + h * NT * kConvLd, lane);
+      load_rows3<kMask>(s_v + (int64_t)h * W, (int64_t)kStVRow, lane, v, W);
+      fold_att_lds<kMask>(p, v, s_in + h * NT * kConvLd, lane, W);
     }
     __syncthreads();
     __builtin_amdgcn_sched_barrier(0);
     // (C) weight / bias gradient
-#pragma unroll 2
-    for (int ks = 8 * h; ks < 8 * h + 8; ++ks) {
-      const int xx = 4 * ks + lk;
-      const float av = lo < kConvO ? gpre(lo, xx) : 0.f;
+    if (kMask) {  // the steps at or past Wo (g_pre = 0 there: they add nothing) are not run
+      const int ks1 = min(8 * h + 8, (Wo + 3) >> 2);
+      for (int ks = 8 * h; ks < ks1; ++ks) {
+        const int xx = 4 * ks + lk;
+        const float av = lo < kConvO ? gpre(lo, xx) : 0.f;
 #pragma unroll
-      for (int j = 0; j < kConvNT; ++j) {
-        const float bv = boff[j] >= 0 ? s_in[boff[j] + xx] : (boff[j] == -1 ? 1.f : 0.f);
-        acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc[j], 0, 0, 0);
+        for (int j = 0; j < kConvNT; ++j) {
+          const float bv = boff[j] >= 0 ? s_in[boff[j] + xx] : (boff[j] == -1 ? 1.f : 0.f);
+          acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc[j], 0, 0, 0);
+        }
+      }
+    } else {
+#pragma unroll 2
+      for (int ks = 8 * h; ks < 8 * h + 8; ++ks) {
+        const int xx = 4 * ks + lk;
+        const float av = lo < kConvO ? gpre(lo, xx) : 0.f;
+#pragma unroll
+        for (int j = 0; j < kConvNT; ++j) {
+          const float bv = boff[j] >= 0 ? s_in[boff[j] + xx] : (boff[j] == -1 ? 1.f : 0.f);
+          acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc[j], 0, 0, 0);
+        }
       }
     }
     {  // bias of channel h: this molecule's row sum, then the running sum (short chains)
       float sb = 0.f;
 #pragma unroll
-      for (int i = 0; i < kDkVpl; ++i) sb += gpre(h, lane + 64 * i);
+      for (int i = 0; i < kV; ++i) sb += gpre(h, lane + 64 * i);
       pb += wsum(sb);
     }
     __builtin_amdgcn_sched_barrier(0);  // phases stay apart (registers)
     // (D) the cube's gradient in registers
     float acc_in[kCD];
-    {
+    if (!kMask || half < 2) {
       int xpl = xp;  // laundered per molecule: the 36 row addresses are not hoisted out of the loop
       asm volatile("" : "+v"(xpl));
 #pragma unroll
@@ -1201,27 +1284,28 @@ attn_conv_bwd_kernel(int64_t B, int64_t per_block, const float* __restrict__ pv,
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // every staged-row / cube read done
 #pragma unroll
-    for (int cd = 0; cd < kCD; ++cd) s_in[(half * kCD + cd) * kConvLd + xp] = acc_in[cd];
-    float v[NT][kDkVpl], p[NT][NT];
+    for (int cd = 0; cd < kCD; ++cd)
+      if (!kMask || (half < 2 && xp < W)) s_in[(half * kCD + cd) * kConvLd + xp] = acc_in[cd];
+    float v[NT][kV], p[NT][NT];
 #pragma unroll
     for (int e = 0; e < NT * NT; ++e) p[e / NT][e % NT] = s_p[h * NT * NT + e];
-    load_rows3(s_v + (int64_t)h * W, HD, lane, v);
-    if (next) stage_go(g_out, out, b + 1, lds, h, lane);  // after the stores: registers
+    load_rows3<kMask>(s_v + (int64_t)h * W, (int64_t)kStVRow, lane, v, W);
+    if (next) stage_go<kMask>(g_out, out, b + 1, lds, h, lane, W);  // after the stores: registers
     // head h's query rows and the keys (plain loads: the compiler's wait at their first use
     // also covers the LDS-DMA pieces issued before it, so the next molecule's staging and these
     // loads share one memory latency)
-    float q[NT][kDkVpl], k[NT][kDkVpl];
-    load_rows3(pv + b * NT * ld + (int64_t)h * W, ld, lane, q);
-    load_rows3(x + b * NT * ldx, ldx, lane, k);
+    float q[NT][kV], k[NT][kV];
+    load_rows3<kMask>(pv + b * NT * ld + (int64_t)h * W, ld, lane, q, W);
+    load_rows3<kMask>(x + b * NT * ldx, ldx, lane, k, W);
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // cube gradient stored; v / P read
     // unconditional (the last molecule re-stages its own v / P, already in registers): a fixed
     // count of DMA pieces per wave keeps the compiler's wait below at vmcnt(5)
-    stage_vp(pv, ld, P, next ? b + 1 : b, lds, h, lane);
+    stage_vp<kMask>(pv, ld, P, next ? b + 1 : b, lds, h, lane, W);
     __builtin_amdgcn_sched_barrier(0);
     // (E) attention backward of head h (token_attn_fold_bwd_kernel's order)
     {
-      float g[NT][kDkVpl];
-      load_rows3(s_in + h * NT * kConvLd, kConvLd, lane, g);
+      float g[NT][kV];
+      load_rows3<kMask>(s_in + h * NT * kConvLd, kConvLd, lane, g, W);
       float gs[NT][NT];
       fold_grad_scores(g, v, p, scale, gs);
       float rmx[NT];  // this wave's part of each token row's |max| (gpv_rows)
@@ -1230,11 +1314,11 @@ attn_conv_bwd_kernel(int64_t B, int64_t per_block, const float* __restrict__ pv,
         float* grow = gpv + (b * NT + c) * ldg + HD + (int64_t)h * W;
         rmx[c] = 0.f;
 #pragma unroll
-        for (int i = 0; i < kDkVpl; ++i) {
+        for (int i = 0; i < kV; ++i) {
           float o = 0.f;
 #pragma unroll
           for (int a = 0; a < NT; ++a) o = fmaf(p[a][c], g[a][i], o);
-          grow[lane + 64 * i] = o;
+          if (col_ok<kMask, kV>(lane, i, W)) grow[lane + 64 * i] = o;
           rmx[c] = fmaxf(rmx[c], fabsf(o));
         }
       }
@@ -1244,16 +1328,16 @@ attn_conv_bwd_kernel(int64_t B, int64_t per_block, const float* __restrict__ pv,
       for (int t = 0; t < NT; ++t) {
         float* grow = gpv + (b * NT + t) * ldg + (int64_t)h * W;
 #pragma unroll
-        for (int i = 0; i < kDkVpl; ++i) {
+        for (int i = 0; i < kV; ++i) {
           float oq = 0.f, ok = 0.f;
 #pragma unroll
           for (int c = 0; c < NT; ++c) {
             oq = fmaf(gs[t][c], k[c][i], oq);
             ok = fmaf(gs[c][t], q[c][i], ok);
           }
-          grow[lane + 64 * i] = oq;
+          if (col_ok<kMask, kV>(lane, i, W)) grow[lane + 64 * i] = oq;
           rmx[t] = fmaxf(rmx[t], fabsf(oq));
-          s_in[(h * NT + t) * kConvLd + lane + 64 * i] = ok;
+          if (col_ok<kMask, kV>(lane, i, W)) s_in[(h * NT + t) * kConvLd + lane + 64 * i] = ok;
         }
       }
 #pragma unroll
@@ -1359,14 +1443,25 @@ extern "C" int mvml_layernorm_bwd(int64_t rows, int D, const float* x, int64_t l
   return check_launch("layernorm_bwd_kernel");
 }
 
+// The head width the token-attention and fused kernels take: a multiple of 4 in [16, 384]
+// (the GAT / Set2Set kernels upstream emit multiples of 4; 384 is the conv kernels' LDS row).
+// dk = 384 launches the unmasked instance, every other width the masked one of its group count.
+#define MVML_BY_WIDTH(KERN, dk)                                                                  \
+  ((dk) == kFuseW ? KERN<false, 6> : (dk) > 320 ? KERN<true, 6> : (dk) > 256 ? KERN<true, 5>    \
+   : (dk) > 192 ? KERN<true, 4> : (dk) > 128 ? KERN<true, 3> : (dk) > 64 ? KERN<true, 2>         \
+                                                                         : KERN<true, 1>)
+static bool fuse_dk_ok(int dk) { return dk >= 16 && dk <= 64 * kDkVpl && dk % 4 == 0; }
+#define MVML_DK_SET "dk must be a multiple of 4 in [16, 384]"
+static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 extern "C" int mvml_token_attn_fwd(int64_t B, int H, int dk, const float* qkv, int64_t ld,
                                    float scale, float* att, float* P, void* stream) {
   clear_error();
-  MVML_REQUIRE(B >= 0 && H > 0 && dk == 64 * kDkVpl && ld >= 3 * (int64_t)H * dk,
-               "token_attn_fwd: dk must be %d and ld >= 3*H*dk", 64 * kDkVpl);
+  MVML_REQUIRE(B >= 0 && H > 0 && fuse_dk_ok(dk) && ld >= 3 * (int64_t)H * dk,
+               "token_attn_fwd: " MVML_DK_SET " and ld >= 3*H*dk");
   if (B == 0) return MVML_OK;
-  token_attn_fwd_kernel<<<(unsigned)ceil_div(B * H, 4), 256, 0, as_stream(stream)>>>(
-      B, H, dk, qkv, ld, scale, att, P);
+  auto kern = MVML_BY_WIDTH(token_attn_fwd_kernel, dk);
+  kern<<<(unsigned)ceil_div(B * H, 4), 256, 0, as_stream(stream)>>>(B, H, dk, qkv, ld, scale, att, P);
   return check_launch("token_attn_fwd_kernel");
 }
 
@@ -1374,12 +1469,13 @@ extern "C" int mvml_token_attn_bwd(int64_t B, int H, int dk, const float* qkv, i
                                    float scale, const float* P, const float* g_att,
                                    float* g_qkv, int64_t ldg, void* stream) {
   clear_error();
-  MVML_REQUIRE(B >= 0 && H > 0 && dk == 64 * kDkVpl && ld >= 3 * (int64_t)H * dk &&
+  MVML_REQUIRE(B >= 0 && H > 0 && fuse_dk_ok(dk) && ld >= 3 * (int64_t)H * dk &&
                    ldg >= 3 * (int64_t)H * dk,
-               "token_attn_bwd: bad shape");
+               "token_attn_bwd: bad shape (" MVML_DK_SET ")");
   if (B == 0) return MVML_OK;
-  token_attn_bwd_kernel<<<(unsigned)ceil_div(B * H, 4), 256, 0, as_stream(stream)>>>(
-      B, H, dk, qkv, ld, scale, P, g_att, g_qkv, ldg);
+  auto kern = MVML_BY_WIDTH(token_attn_bwd_kernel, dk);
+  kern<<<(unsigned)ceil_div(B * H, 4), 256, 0, as_stream(stream)>>>(B, H, dk, qkv, ld, scale, P, g_att,
+                                                                     g_qkv, ldg);
   return check_launch("token_attn_bwd_kernel");
 }
 
@@ -1387,11 +1483,11 @@ extern "C" int mvml_token_attn_fold_fwd(int64_t B, int H, int dk, const float* p
                                         const float* x, int64_t ldx, float scale, float* att,
                                         float* P, void* stream) {
   clear_error();
-  MVML_REQUIRE(B >= 0 && H > 0 && dk == 64 * kDkVpl && ld >= 2 * (int64_t)H * dk && ldx >= dk,
-               "token_attn_fold_fwd: dk must be %d, ld >= 2*H*dk", 64 * kDkVpl);
+  MVML_REQUIRE(B >= 0 && H > 0 && fuse_dk_ok(dk) && ld >= 2 * (int64_t)H * dk && ldx >= dk,
+               "token_attn_fold_fwd: " MVML_DK_SET ", ld >= 2*H*dk");
   if (B == 0) return MVML_OK;
-  token_attn_fold_fwd_kernel<<<(unsigned)ceil_div(B, 4), 256, 0, as_stream(stream)>>>(
-      B, H, dk, pv, ld, x, ldx, scale, att, P);
+  auto kern = MVML_BY_WIDTH(token_attn_fold_fwd_kernel, dk);
+  kern<<<(unsigned)ceil_div(B, 4), 256, 0, as_stream(stream)>>>(B, H, dk, pv, ld, x, ldx, scale, att, P);
   return check_launch("token_attn_fold_fwd_kernel");
 }
 
@@ -1400,12 +1496,13 @@ extern "C" int mvml_token_attn_fold_bwd(int64_t B, int H, int dk, const float* p
                                         const float* g_att, float* g_pv, int64_t ldg, float* g_k,
                                         int64_t ldgk, uint32_t* gpv_amax, void* stream) {
   clear_error();
-  MVML_REQUIRE(B >= 0 && H > 0 && dk == 64 * kDkVpl && ld >= 2 * (int64_t)H * dk && ldx >= dk &&
+  MVML_REQUIRE(B >= 0 && H > 0 && fuse_dk_ok(dk) && ld >= 2 * (int64_t)H * dk && ldx >= dk &&
                    ldg >= 2 * (int64_t)H * dk && ldgk >= dk,
-               "token_attn_fold_bwd: bad shape");
+               "token_attn_fold_bwd: bad shape (" MVML_DK_SET ")");
   if (B == 0) return MVML_OK;
-  token_attn_fold_bwd_kernel<<<(unsigned)ceil_div(B, 4), 256, 0, as_stream(stream)>>>(
-      B, H, dk, pv, ld, x, ldx, scale, P, g_att, g_pv, ldg, g_k, ldgk, gpv_amax);
+  auto kern = MVML_BY_WIDTH(token_attn_fold_bwd_kernel, dk);
+  kern<<<(unsigned)ceil_div(B, 4), 256, 0, as_stream(stream)>>>(B, H, dk, pv, ld, x, ldx, scale, P, g_att,
+                                                                 g_pv, ldg, g_k, ldgk, gpv_amax);
   return check_launch("token_attn_fold_bwd_kernel");
 }
 
@@ -1472,14 +1569,15 @@ extern "C" int mvml_attn_conv_fwd(int64_t B, int H, int dk, const float* pv, int
                                   const float* bias, float* P, float* out, double drop_p,
                                   int64_t drop_seed, void* stream) {
   clear_error();
-  MVML_REQUIRE(B >= 0 && H == kConvC && dk == 64 * kDkVpl && ld >= 2 * (int64_t)H * dk && ldx >= dk,
-               "attn_conv_fwd: H must be %d, dk %d, ld >= 2*H*dk, ldx >= dk", kConvC, 64 * kDkVpl);
+  MVML_REQUIRE(B >= 0 && H == kConvC && fuse_dk_ok(dk) && ld >= 2 * (int64_t)H * dk && ldx >= dk,
+               "attn_conv_fwd: H must be %d, " MVML_DK_SET ", ld >= 2*H*dk, ldx >= dk", kConvC);
   MVML_REQUIRE(drop_p >= 0.0 && drop_p < 1.0, "attn_conv_fwd: dropout p must be in [0, 1)");
   if (B == 0) return MVML_OK;
   const int64_t nblk = fused_blocks(B), per = ceil_div(B, nblk);
-  attn_conv_fwd_kernel<<<(unsigned)ceil_div(B, per), kFuseThreads, 0, as_stream(stream)>>>(
+  auto kern = MVML_BY_WIDTH(attn_conv_fwd_kernel, dk);
+  kern<<<(unsigned)ceil_div(B, per), kFuseThreads, 0, as_stream(stream)>>>(
       B, per, pv, ld, x, ldx, scale, weight, bias, P, out, drop_p > 0.0 ? dropout_threshold(drop_p) : 0u,
-      dropout_scale(drop_p), (uint64_t)drop_seed);
+      dropout_scale(drop_p), (uint64_t)drop_seed, dk);
   return check_launch("attn_conv_fwd_kernel");
 }
 
@@ -1495,10 +1593,13 @@ extern "C" int mvml_attn_conv_bwd(int64_t B, int H, int dk, const float* pv, int
                                   float* g_bias, void* workspace, size_t workspace_bytes,
                                   void* stream) {
   clear_error();
-  MVML_REQUIRE(B >= 0 && H == kConvC && dk == 64 * kDkVpl && ld >= 2 * (int64_t)H * dk &&
+  MVML_REQUIRE(B >= 0 && H == kConvC && fuse_dk_ok(dk) && ld >= 2 * (int64_t)H * dk &&
                    ldx >= dk && ldg >= 2 * (int64_t)H * dk && ldgk >= dk,
-               "attn_conv_bwd: H must be %d, dk %d, ld / ldg >= 2*H*dk, ldx / ldgk >= dk", kConvC,
-               64 * kDkVpl);
+               "attn_conv_bwd: H must be %d, " MVML_DK_SET ", ld / ldg >= 2*H*dk, ldx / ldgk >= dk",
+               kConvC);
+  // the staging reads pv's v columns, P, out and g_out as 16-byte pieces
+  MVML_REQUIRE(ld % 4 == 0 && aligned16(pv) && aligned16(P) && aligned16(out) && aligned16(g_out),
+               "attn_conv_bwd: pv, P, out and g_out must be 16-byte aligned and ld a multiple of 4");
   if (B == 0) return MVML_OK;
   if (!workspace || workspace_bytes < mvml_attn_conv_bwd_workspace_size(B)) {
     set_error("attn_conv_bwd: workspace of mvml_attn_conv_bwd_workspace_size bytes required");
@@ -1508,9 +1609,10 @@ extern "C" int mvml_attn_conv_bwd(int64_t B, int H, int dk, const float* pv, int
   const int64_t nblk = fused_blocks(B), per = ceil_div(B, nblk);
   const int64_t used = ceil_div(B, per);
   float* part = static_cast<float*>(workspace);
-  attn_conv_bwd_kernel<<<(unsigned)used, kFuseThreads, 0, st>>>(
+  auto kern = MVML_BY_WIDTH(attn_conv_bwd_kernel, dk);
+  kern<<<(unsigned)used, kFuseThreads, 0, st>>>(
       B, per, pv, ld, x, ldx, scale, P, weight, out, g_out, g_scale, g_pv, ldg, g_k, ldgk, g_pv_amax,
-      part, g_pv_rows);
+      part, g_pv_rows, dk);
   int rc = check_launch("attn_conv_bwd_kernel");
   if (rc) return rc;
   partial_sum_kernel<<<(unsigned)ceil_div(kConvWg, 256), 256, 0, st>>>(

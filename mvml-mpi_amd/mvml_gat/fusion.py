@@ -3,11 +3,15 @@ consumer of the graph view.
 
     MVFusion(final_hidden_feats=384, num_heads=12, num_classes=11, dropout)(smiles_x, graph_x, fp_x)
 
-takes the three RAW view embeddings (B, 384) (what MVP gets from RNNModule, GNNModule and
+takes the three RAW view embeddings (B, D), D = final_hidden_feats (what MVP gets from RNNModule, GNNModule and
 FPNModule before its shared LayerNorm, model.py:54-56) and returns the logits (B, num_classes)
 of model.py:72.  Parameter names / shapes equal MVP's, so ``MVP.state_dict()`` entries under
 ``norm_layer_module.``, ``conv.``, ``linear_{q,k,v}.``, ``norm_layer.``, ``mlp.`` load unchanged.
 ``bce_with_logits`` is main.py:91's BCEWithLogitsLoss.
+
+Supported sizes: D a multiple of 4 with 16 <= D <= 384 (``FUSION_WIDTHS``; the default 384 runs
+the kernels' unmasked instances, every other width their masked ones) and num_heads = 12 (the
+reference's Conv2d(12, 12, 3) is fixed, model.py:28, whatever ``head`` says).
 """
 import math
 import os
@@ -65,7 +69,7 @@ class LinearFunction(torch.autograd.Function):
 # gradient and the weight gradient; False = the literal Q / K / V path (kept, tested).
 FOLD_QK = True
 # With FOLD_QK: the token attention and the Conv2d + ReLU run as ONE kernel each way
-# (mvml_attn_conv_fwd / _bwd), the (B, 12, 3, 384) attention cube never leaves LDS; False = the
+# (mvml_attn_conv_fwd / _bwd), the (B, 12, 3, D) attention cube never leaves LDS; False = the
 # separate mvml_token_attn_fold_* and mvml_conv3_* launches (kept, tested).
 FUSE_ATTN_CONV = os.environ.get("MVML_FUSE_ATTN_CONV", "1") != "0"
 
@@ -170,9 +174,18 @@ class FusionAttnConvFunction(torch.autograd.Function):
         f32 = dict(dtype=torch.float32, device=dev)
         L = _lib.lib()
         g_out = _c(g_out)
+        if fused and g_out.data_ptr() % 16:  # mvml_attn_conv_bwd stages it in 16-byte pieces
+            g_out = g_out.clone()
         g_cw = torch.empty_like(conv_w)
         g_cb = torch.empty((H,), **f32)
         if not fused:
+            if ctx.g_scale != 1.0:
+                # the Dropout after the ReLU ran in place on out: g_pre = g_out * scale where the
+                # dropped output is > 0 (the fused kernel's arithmetic; mvml_conv3_bwd's own
+                # out > 0 mask then changes nothing)
+                g_pre = torch.empty_like(g_out)
+                call("mvml_relu_bwd", g_out.numel(), ptr(out), ptr(g_out), ptr(g_pre), float(ctx.g_scale), st)
+                g_out = g_pre
             g_att = torch.empty_like(att)
             wp, wn = _lib.ws_ptr_size(L.mvml_conv3_bwd_workspace_size(B), dev)
             call("mvml_conv3_bwd", B, H, H, D, ptr(att), ptr(_c(conv_w)), ptr(out), ptr(g_out),
@@ -275,15 +288,32 @@ def bce_with_logits(logits, labels):
     return BCEWithLogitsFunction.apply(logits, labels)
 
 
+FUSION_HEADS = 12
+FUSION_WIDTHS = "hidden_feats[-1] a multiple of 4 with 16 <= hidden_feats[-1] <= 384"
+
+
+def fusion_width_ok(d):
+    """The widths mvml_token_attn_* / mvml_attn_conv_* accept (include/mvml_gat.h)."""
+    return isinstance(d, int) and 16 <= d <= 384 and d % 4 == 0
+
+
 class MVFusion(nn.Module):
-    """The fusion part of MVP (model.py:23, 27-48, 54-72) with MVP's parameter names."""
+    """The fusion part of MVP (model.py:23, 27-48, 54-72) with MVP's parameter names, for view
+    embeddings (B, D) with D = final_hidden_feats in the supported set (FUSION_WIDTHS)."""
 
     def __init__(self, final_hidden_feats=384, num_heads=12, num_classes=11, dropout=0.2):
         super().__init__()
-        if final_hidden_feats != 384 or num_heads != 12:
+        if not fusion_width_ok(final_hidden_feats):
             raise ValueError(
-                "the HIP fusion kernels are built for the reference configuration (config.py: "
-                f"hidden_feats[-1] = 384, head = 12); got {final_hidden_feats} / {num_heads}")
+                f"hidden_feats[-1] = {final_hidden_feats}: the HIP fusion kernels take "
+                f"{FUSION_WIDTHS} (the GAT / Set2Set kernels emit multiples of 4, and 384 is the "
+                "Conv2d kernels' LDS row)")
+        if num_heads != FUSION_HEADS:
+            raise ValueError(
+                f"head = {num_heads}: the fusion head takes num_heads = 12 only, with "
+                f"{FUSION_WIDTHS}; the reference builds nn.Conv2d(12, 12, kernel_size=3) "
+                "whatever num_heads is (model.py:28), so any other value fails there with a "
+                "channel mismatch")
         d = final_hidden_feats
         self.final_hidden_feats, self.num_heads = d, num_heads
         self.norm_layer_module = nn.LayerNorm(d)

@@ -194,13 +194,15 @@ def parse(argv=None):
     p.add_argument("-e", "--epoch", type=int, default=100, help="the max number of epoch")
     p.add_argument("-s", "--seed", type=int, default=1, help="random seed")
     p.add_argument("--hidden_feats", type=int, nargs="+", default=[192, 384],
-                   help="the size of node representations after the i-th GAT layer")
+                   help="the size of node representations after the i-th GAT layer (the last one, "
+                        "the fusion head's width: a multiple of 4 in [16, 384])")
     p.add_argument("--rnn_embed_dim", type=int, default=128, help="the embedding size of each SMILES token")
     p.add_argument("--rnn_hidden_dim", type=int, default=384,
                    help="the number of features in the RNN hidden state")
     p.add_argument("--rnn_layers", type=int, default=2, help="the number of rnn layers")
     p.add_argument("--fp_dim", type=int, default=512, help="the hidden size of fingerprints module")
-    p.add_argument("--head", type=int, default=12, help="the head size of attention")
+    p.add_argument("--head", type=int, default=12, help="the head size of attention; must be 12 (the reference's Conv2d(12, 12, 3) is "
+                        "fixed whatever this says)")
     p.add_argument("--p", type=float, default=0.5, help="dropout probability")
     p.add_argument("--lr", type=float, default=1e-3, help="learning rate")
     p.add_argument("--weight_decay", type=float, default=1e-4)

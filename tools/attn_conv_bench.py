@@ -3,7 +3,10 @@ molecules: the fused kernels (mvml_attn_conv_fwd / _bwd, the attention cube on c
 separate launches they replace (mvml_token_attn_fold_fwd + mvml_conv3_fwd, mvml_conv3_bwd +
 mvml_token_attn_fold_bwd), ms per launch with HIP events and GB/s of each one's algorithmic bytes.
 
-    python tools/attn_conv_bench.py [--B 65536] [--reps 10] [--only fused|separate]
+    python tools/attn_conv_bench.py [--B 65536] [--D 384] [--reps 10] [--only fused|separate]
+
+--D: the head width hidden_feats[-1], a multiple of 4 in [16, 384] (other than 384: the kernels'
+masked instances).
 """
 import argparse
 import math
@@ -22,10 +25,11 @@ from mvml_gat.fusion import attn_conv_bytes  # noqa: E402
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=65536)
+    ap.add_argument("--D", type=int, default=384, help="head width: a multiple of 4 in [16, 384]")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--only", choices=["fused", "separate"], default=None)
     a = ap.parse_args()
-    B, H, D = a.B, 12, 384
+    B, H, D = a.B, 12, a.D
     HD = H * D
     dev = "cuda"
     g = torch.Generator(device=dev).manual_seed(0)
