@@ -337,9 +337,11 @@ int mvml_gat_unfold_grads(const float* gWcat, const float* attn_lr, int H, int F
 /* The projection GEMM (X [N, K] with row stride ldx, Wcat [C, K] with row stride ldw, K = the
  * padded feature count) + GATConv's attention logits from the result:
  *   el[n,h] = <Z[n,h,:], attn_l[h,:]>,  er[n,h] = <Z[n,h,:], attn_r[h,:]>
- * (`(feat_src * attn_l).sum(-1)`), computed in the GEMM epilogue as per-32-column partial dots
- * of the fp32 Z tile and summed per head in fixed order — no second pass over Z.
- * attn_lr: [2, H*F] = [attn_l | attn_r]; elr: [N, 2H] = [el | er].  F % 32 == 0.
+ * (`(feat_src * attn_l).sum(-1)`), computed in the GEMM epilogue as per-W-column partial dots
+ * of the fp32 Z tile (W = the largest power of two <= 32 that divides F: 32 at F % 32 == 0, down
+ * to 4) and summed per head in fixed order — no second pass over Z.
+ * attn_lr: [2, H*F] = [attn_l | attn_r]; elr: [N, 2H] = [el | er].  H in {1, 2, 4, 8},
+ * F % 4 == 0.
  * algo MVML_GEMM_F16X2: amax_x / amax_w = bits of max |X| / max |Wcat| (mvml_absmax_f32), or
  * both NULL (computed here); w_planes must be NULL (w_plane ignored: the two-plane weight image
  * was removed in round 6).
@@ -374,6 +376,14 @@ int mvml_gat_attn_grad(int64_t num_nodes, int H, int F, const float* Y, int64_t 
  * once per row (no atomics; the per-row scales of the next products, mvml_gemm_f16x2_rows).
  * node_groups is the plan mvml_build_node_groups built from the same in_rowptr (a plan of
  * another graph is undefined behaviour); num_groups = mvml_node_group_count(num_nodes).
+ * Supported shapes (forward and backward, every mode and every kernel-path option): H in
+ * {1, 2, 4, 8}, F a positive multiple of 4, H*F <= 2048; anything else returns MVML_ERR_INVALID
+ * before any launch and writes nothing.  The options only choose among kernels that hold the
+ * shape: the destination-wave forward (MVML_OPT_DST_FWD) holds head-mean rows up to F = 512
+ * (H >= 2) or 1024 (H = 1) and the source-atom head-mean backward (MVML_OPT_MEAN_SRC) up to
+ * F = 1024; wider head-mean shapes take the window / gather kernels whatever the option says.
+ * The LDS backward runs at F % 32 == 0 and the big windows at H <= 4, F % 16 == 0; other shapes
+ * take the per-atom kernels.
  * ------------------------------------------------------------------------------------- */
 int mvml_gat_agg_fwd(int64_t num_nodes, const int32_t* node_groups, int64_t num_groups,
                      const int32_t* in_rowptr, const int32_t* in_src, const float* Y, int64_t ldy,
@@ -477,7 +487,10 @@ int mvml_lstm_cell_bwd(int64_t B, int D, const float* act, const float* c, const
                        float* gb_part, void* stream);
 /* Readout segment pass (one wavefront per molecule): e_n = <x_n, q_g>, alpha = softmax over
  * the molecule's atoms (softmax_nodes), r_g = sum_n alpha_n x_n (sum_nodes).  Writes r into
- * qstar[:, D:2D] (ld ldq, q itself already sits in qstar[:, 0:D]) and lse[g] for backward. */
+ * qstar[:, D:2D] (ld ldq, q itself already sits in qstar[:, 0:D]) and lse[g] for backward.
+ * D (here and in the two entry points below): a positive multiple of 4, <= 1024.  A molecule
+ * without atoms gets r = 0 and lse = -inf; its backward adds nothing to g_q and touches no
+ * alpha / g_e entry. */
 int mvml_set2set_seg_fwd(int64_t B, int D, const int64_t* node_offsets, const float* X,
                          float* qstar, int64_t ldq, float* lse, void* stream);
 /* Backward of one segment pass: from g_qstar[:, D:2D] (= dL/dr) computes dL/dq into

@@ -2260,7 +2260,12 @@ int launch_fwd(int64_t N, const int32_t* groups, int64_t G, const int32_t* rp, c
                const float* Y, int64_t ldy, int F, const float* bias, float slope, int mode,
                float* out, float* attn, const float* elr, uint32_t* out_amax, uint32_t* out_rows,
                hipStream_t st) {
-  if (option(MVML_OPT_DST_FWD) && H * F <= 2048) {  // one wave per destination atom, every atom
+  // The destination-wave kernel holds at most 4 float4 column slots per lane in mean mode (half-
+  // waves over the heads for H >= 2: F <= 512; H = 1: F <= 1024) and 8 in the flatten modes
+  // (H F <= 2048).  Wider head-mean shapes take the window / gather kernels below, whatever the
+  // option says: decided here, before anything is launched.
+  const bool dst_fits = H * F <= 2048 && (mode != 1 || ceil_div(F / 4, H >= 2 ? 32 : 64) <= 4);
+  if (option(MVML_OPT_DST_FWD) && dst_fits) {  // one wave per destination atom, every atom
     const unsigned b4 = (unsigned)ceil_div(N, 4);
     const int HF = H * F;
     const bool sm = option(MVML_OPT_DST_FWD) == 1;  // 2: the softmax as its own launch first
@@ -2307,8 +2312,7 @@ int launch_fwd(int64_t N, const int32_t* groups, int64_t G, const int32_t* rp, c
               N, rp, src, Y, ldy, F, bias, elr, slope, attn, out, blk_amax, out_rows);
       }
       else if (nj == 3) MVML_DST_FWD(1, 3, 1);  // one row in flight: fewest registers, most waves
-      else if (nj <= 4) MVML_DST_FWD(1, 4, 2);
-      else { set_error("gat_agg_fwd: dst path needs F <= %d in mean mode", H >= 2 ? 512 : 1024); return MVML_ERR_INVALID; }
+      else MVML_DST_FWD(1, 4, 2);  // nj == 4 (dst_fits)
     } else {
       const int nj = (int)ceil_div(HF / 4, 64);
 #define MVML_DST_FWD_F(NJ, U) do { if (mode == 0) MVML_DST_FWD(0, NJ, U); else MVML_DST_FWD(2, NJ, U); } while (0)

@@ -593,7 +593,8 @@ class GATLayerFunction(torch.autograd.Function):
         if mean_res:  # every head's bias sees g_out / H: one column sum, replicated over heads
             if not bias_done:
                 colsum(gY, N, F, ldg, g_bias, offset=HF, alpha=1.0 / H)
-            copy2d(g_bias.view(H, F)[1:], g_bias[:F].view(1, F).expand(H - 1, F))
+            if H > 1:
+                copy2d(g_bias.view(H, F)[1:], g_bias[:F].view(1, F).expand(H - 1, F))
         elif not bias_done:
             colsum(gY, N, HF, ldg, g_bias, offset=HF)
         gX = None
@@ -826,6 +827,9 @@ class Set2SetFunction(torch.autograd.Function):
                      amax=None if amax_g is None else (slot(amax_g, l), slot(amax_x, 0)))
                 copy2d(gW_ih[l], gWcat[:, :kin])
                 copy2d(gW_hh[l], gWcat[:, kin:])
+            else:  # n_iters = 1: layer 0's only step reads q*_{-1} = 0 and h_0(-1) = 0
+                zero_(gW_ih[l])
+                zero_(gW_hh[l])
             colsum(gb_part[l], T * R, 4 * D, 4 * D, gb[l])
         gX = torch.empty((N, D), **f32)
         call("mvml_set2set_gx", N, D, T, ptr(g.node_graph), ptr(g.node_offsets), B, ptr(qs), 3 * D, B * 3 * D,

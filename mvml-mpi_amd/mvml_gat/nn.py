@@ -31,6 +31,11 @@ class GATConv(nn.Module):
             raise NotImplementedError(
                 "GATConv: only residual=True with a projecting res_fc and bias=True (the "
                 "dgllife GAT defaults used by model.py:81) are implemented")
+        # the aggregation kernels' range (csrc/gat_agg.hip check_shapes): refuse here, not in forward
+        if num_heads not in (1, 2, 4, 8) or out_feats <= 0 or out_feats % 4 or num_heads * out_feats > 2048:
+            raise ValueError(
+                f"GATConv: num_heads must be 1, 2, 4 or 8 and out_feats a positive multiple of 4 with "
+                f"num_heads * out_feats <= 2048 (got num_heads={num_heads}, out_feats={out_feats})")
         self._num_heads = num_heads
         self._in_feats = in_feats
         self._out_feats = out_feats
@@ -171,6 +176,9 @@ class Set2Set(nn.Module):
 
     def __init__(self, input_dim, n_iters, n_layers):
         super().__init__()
+        # the segment kernels' range (csrc/set2set.hip check_d): refuse here, not in forward
+        if input_dim <= 0 or input_dim % 4 or input_dim > 1024:
+            raise ValueError(f"Set2Set: input_dim must be a positive multiple of 4 <= 1024 (got {input_dim})")
         self.input_dim = input_dim
         self.output_dim = 2 * input_dim
         self.n_iters = n_iters

@@ -91,6 +91,32 @@ def gatconv_ref(src, dst, X, fc_w, res_w, attn_l, attn_r, bias, num_heads, out_f
     return rst
 
 
+def gat_agg_ref(src, dst, Z, R, elr, bias, H, F, mode, slope=0.2, branch=None):
+    """GATConv from apply_edges to the layer's output, at the cut of mvml_gat_agg_fwd: the
+    projection's Z [N, H, F], residual R ([N, H*F], or [N, F] = its head mean for mode 1) and
+    logits elr [N, 2H] = [el | er] are INPUTS (leaves for the aggregation's own gradients).
+    mode 0 flatten + ELU, 1 head mean, 2 flatten.  Returns (out, attn) with attn [E, H] in in-CSR
+    slot order: the edges stably sorted by dst (mvml_build_csr).  With leaf inputs,
+    out.backward(g) leaves in Z.grad, R.grad, elr.grad[:, :H] and elr.grad[:, H:] the four blocks
+    [dZ through update_all only | dR | d el | d er] of mvml_gat_agg_bwd's gY."""
+    src = _as_long(src, Z.device)
+    dst = _as_long(dst, Z.device)
+    n = Z.shape[0]
+    s = elr[:, :H][src] + elr[:, H:][dst]
+    e = nn.functional.leaky_relu(s, slope) if branch is None else leaky_relu_branch(s, slope, branch)
+    a = edge_softmax_ref(e, dst, n)
+    agg = torch.zeros((n, H, F), dtype=Z.dtype, device=Z.device).index_add(
+        0, dst, a.unsqueeze(-1) * Z.view(n, H, F)[src])
+    b = bias.view(H, F)
+    if mode == 1:
+        out = agg.mean(1) + R + b.mean(0)
+    else:
+        out = (agg + R.view(n, H, F) + b).flatten(1)
+        if mode == 0:
+            out = nn.functional.elu(out)
+    return out, a[torch.argsort(dst, stable=True)]
+
+
 def _bf16_round(x):
     """x rounded to bf16 (round-to-nearest-even, via fp32 as the product sees its fp32 operands),
     carried in x's dtype."""

@@ -1,7 +1,8 @@
 """mvml_gat_layer_bwd: a GATConv's whole backward as ONE C call, called
 through the ctypes handle of libmvml_gat.so with the forward's saved tensors, is BITWISE the
 gradient the Python layer (GATLayerFunction.backward: the same launches) gives — for the
-flatten + ELU layer on the 74 atom features and the head-mean layer on 768-wide rows."""
+flatten + ELU layer on the 74 atom features and the head-mean layer on 768-wide rows, and for
+one layer of each kind at another head count (H = 8 flatten, H = 2 head mean)."""
 import ctypes
 
 import pytest
@@ -19,21 +20,26 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
 
-@pytest.mark.parametrize("layer", [0, 1])
+# layer 0 / 1: GNNModule's default layers; the others: head counts off the default, one of each kind
+LAYERS = {0: (74, 4, 192, 0), 1: (768, 4, 384, 1), "flatten-H8-F8": (74, 8, 8, 0), "mean-H2-F24": (74, 2, 24, 1)}
+
+
+@pytest.mark.parametrize("layer", list(LAYERS))
 @pytest.mark.parametrize("case", ["config2", "config5"])
 def test_gat_layer_bwd_one_call_bitwise(layer, case):
     sb = synth.config2(96, seed=3) if case == "config2" else synth.config5(2, seed=4)
     g = sb.to_graph().to(DEV)
     N, E = g.num_nodes(), g.num_edges()
-    torch.manual_seed(layer)
-    H = 4
+    torch.manual_seed(layer if isinstance(layer, int) else 2)
+    Fin, H, Fo, mean = LAYERS[layer]
+    layer = mean  # (below: 0 = flatten + ELU, 1 = head mean)
     if layer == 0:
-        Fin, Fo = 74, 192
         m = GATLayer(Fin, Fo, H, agg_mode="flatten", activation=F.elu).to(DEV)
+    else:
+        m = GATLayer(Fin, Fo, H, agg_mode="mean").to(DEV)
+    if Fin == 74:
         X = torch.as_tensor(sb.feats, dtype=torch.float32, device=DEV)
     else:
-        Fin, Fo = 768, 384
-        m = GATLayer(Fin, Fo, H, agg_mode="mean").to(DEV)
         X = torch.randn(N, Fin, device=DEV)
     X = X.clone().requires_grad_()
     out = m(g, X)

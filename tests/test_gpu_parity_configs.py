@@ -88,11 +88,12 @@ def _check_kink_flips(gd, branches, layer_inputs64, layer_params64, H=4):
     return flips
 
 
-def _module_case(sb, group_size=None, seed=3):
-    prod, ref = model_pair(seed=seed)
+def _module_case(sb, group_size=None, seed=3, hidden_feats=(192, 384)):
+    hidden = list(hidden_feats)
+    prod, ref = model_pair(hidden=hidden, seed=seed)
     prod.eval()
     ref.eval()
-    ref32 = type(ref)(74, [192, 384], 0.5, 6, 3).eval()
+    ref32 = type(ref)(74, hidden, 0.5, 6, 3).eval()
     ref32.load_state_dict(ref.state_dict())
     ref64 = ref.double()
     gd = graph_dict(sb, group_size=group_size)
@@ -111,7 +112,7 @@ def _module_case(sb, group_size=None, seed=3):
     torch.cuda.synchronize()
     with torch.no_grad():
         lp = ref64.layer_params()
-        h1 = gnn_ref.gat_layer_ref(gd["src"], gd["dst"], X, lp[0], 4, 192, "flatten",
+        h1 = gnn_ref.gat_layer_ref(gd["src"], gd["dst"], X, lp[0], 4, hidden[0], "flatten",
                                    torch.nn.functional.elu)
     flips = _check_kink_flips(gd, br, [X, h1], lp)
 
@@ -125,7 +126,8 @@ def _module_case(sb, group_size=None, seed=3):
         budget = max(TOL, 4 * rel_err(p32[n].grad, p64[n].grad))
         margins[n] = (e, budget)
     worst = max(margins.items(), key=lambda kv: kv[1][0] / kv[1][1])
-    print(f"worst err/budget {worst[0]}: {worst[1][0]:.2e} / {worst[1][1]:.2e}; "
+    print(f"worst err/budget {worst[0]}: {worst[1][0]:.2e} / {worst[1][1]:.2e} = "
+          f"{worst[1][0] / worst[1][1]:.3f}; "
           f"{flips} LeakyReLU sides differ from float64 (all at the kink)")
     for n, (e, b) in margins.items():
         assert e < b, (n, e, b)
@@ -149,43 +151,101 @@ def test_gnn_module_config3_graphnorm_groups():
     _module_case(sb, group_size=64, seed=7)
 
 
-def _layer_case(layer, sb, seed=0, x_grad=True):
-    """x_grad=False: layer 0 as GNNModule runs it, on the atom features (no input gradient)."""
-    prod, ref = model_pair(seed=seed)
-    conv_p = prod.conv.gnn_layers[layer]
-    conv_r = ref.conv.gnn_layers[layer].gat_conv
-    Fin = 74 if layer == 0 else 768
+def test_gnn_module_other_widths():
+    """GNNModule(74, [20, 260]): the flatten layer on the CW 4 windows, the head-mean layer and
+    Set2Set at a width with a partly masked last slot (260 = 256 + 4), GraphNorm / fc at 520."""
+    _module_case(batch_of_sizes([25, 1, 40, 7, 23, 3, 64, 2, 5], seed=1), seed=4, hidden_feats=(20, 260))
+
+
+def _layer_case(layer, sb, seed=0, x_grad=True, shape=None):
+    """One GAT layer, forward and every gradient, against float64.  layer 0 / 1: the layer of
+    GNNModule's default stack (Fin = 74, H = 4, F = 192, flatten + ELU / Fin = 768, F = 384, head
+    mean), bar 1e-5 on everything.  shape = (Fin, H, F, agg_mode): a mvml_gat.nn.GATLayer of that
+    shape built directly (flatten + ELU, or mean without activation); bar 1e-5, or 4 x the error
+    of the same oracle run in fp32 on the CPU where that is larger; prints and returns the worst
+    err / budget.  x_grad=False: layer 0 as GNNModule runs it, on the atom features (no input
+    gradient)."""
     n = int(sb.num_nodes.sum())
     g = torch.Generator().manual_seed(seed)
-    if layer == 0:
+    if shape is None:
+        prod, ref = model_pair(seed=seed)
+        conv_p = prod.conv.gnn_layers[layer]
+        conv_r = ref.conv.gnn_layers[layer].gat_conv
+        Fin, H, Fo = (74, 4, 192) if layer == 0 else (768, 4, 384)
+        mode = "flatten" if layer == 0 else "mean"
+    else:
+        from mvml_gat.nn import GATLayer
+        from _util import randomize_
+        Fin, H, Fo, mode = shape
+        torch.manual_seed(seed)
+        conv_p = GATLayer(Fin, Fo, H, agg_mode=mode,
+                          activation=torch.nn.functional.elu if mode == "flatten" else None)
+        randomize_(conv_p, seed)
+        conv_r = conv_p.gat_conv
+    act = torch.nn.functional.elu if mode == "flatten" else None
+    if Fin == 74:
         X = torch.as_tensor(sb.feats, dtype=torch.float64)
     else:
         X = torch.randn(n, Fin, generator=g, dtype=torch.float64)
     gd = graph_dict(sb)
-    H, Fo = 4, (192 if layer == 0 else 384)
     params = {"fc.weight": conv_r.fc.weight, "res_fc.weight": conv_r.res_fc.weight,
               "attn_l": conv_r.attn_l, "attn_r": conv_r.attn_r, "bias": conv_r.bias}
     p64 = {k: v.detach().double().requires_grad_() for k, v in params.items()}
+    p32 = {k: v.detach().cpu().clone().requires_grad_() for k, v in params.items()}
     conv_p = conv_p.to(DEV)
     gdev = sb.to_graph().to(DEV)
     Xp = X.float().to(DEV).requires_grad_(x_grad)
     out_p, elrs = _capture(lambda: conv_p(gdev, Xp))
-    br = _branches(gd, elrs)
-    _check_kink_flips(gd, br, [X], [p64])
+    br = _branches(gd, elrs, H)
+    _check_kink_flips(gd, br, [X], [p64], H)
     Xr = X.clone().requires_grad_()
-    act = torch.nn.functional.elu if layer == 0 else None
-    mode = "flatten" if layer == 0 else "mean"
     out_r = gnn_ref.gat_layer_ref(gd["src"], gd["dst"], Xr, p64, H, Fo, mode, act, branch=br[0])
     gout = torch.randn(out_r.shape, generator=g, dtype=torch.float64)
     out_r.backward(gout)
     out_p.backward(gout.float().to(DEV))
-    assert rel_err(out_p, out_r) < TOL, "forward"
-    if x_grad:
-        assert rel_err(Xp.grad, Xr.grad) < TOL, "dX"
     c = conv_p.gat_conv
+    got = {"forward": (out_p, out_r)}
+    if x_grad:
+        got["dX"] = (Xp.grad, Xr.grad)
     for name, pp in (("fc.weight", c.fc.weight), ("res_fc.weight", c.res_fc.weight),
                      ("attn_l", c.attn_l), ("attn_r", c.attn_r), ("bias", c.bias)):
-        assert rel_err(pp.grad, p64[name].grad) < TOL, name
+        got[name] = (pp.grad, p64[name].grad)
+    budget = {k: TOL for k in got}
+    if shape is not None:
+        X32 = X.float().requires_grad_()
+        gnn_ref.gat_layer_ref(gd["src"], gd["dst"], X32, p32, H, Fo, mode, act, branch=br[0]).backward(gout.float())
+        for k in got:
+            if k not in ("forward", "dX"):
+                budget[k] = max(TOL, 4 * rel_err(p32[k].grad, p64[k].grad))
+        if x_grad:
+            budget["dX"] = max(TOL, 4 * rel_err(X32.grad, Xr.grad))
+    errs = {k: rel_err(a, b) for k, (a, b) in got.items()}
+    worst = max(errs, key=lambda k: errs[k] / budget[k])
+    if shape is not None:
+        print(f"LAYER {shape} worst err/budget {worst}: {errs[worst]:.2e} / {budget[worst]:.2e} = "
+              f"{errs[worst] / budget[worst]:.3f}")
+    for k in got:
+        assert errs[k] < budget[k], (k, errs[k], budget[k])
+    return errs[worst] / budget[worst]
+
+
+_SHAPE_GRAPHS = {"mixed": lambda: batch_of_sizes([25, 1, 40, 7, 23, 3, 64, 2, 5], seed=1),
+                 "hubs": lambda: batch_of_sizes([150, 90], seed=7, hubs=True)}
+LAYER_SHAPES = [(74, 1, 4, "flatten"), (74, 2, 12, "flatten"), (74, 8, 8, "flatten"), (30, 4, 72, "flatten"),
+                (100, 8, 256, "flatten"), (74, 2, 24, "mean"), (80, 4, 132, "mean"), (64, 8, 64, "mean"),
+                (768, 1, 260, "mean"), (288, 4, 388, "mean"),
+                # past the destination-wave forward's slots: the window kernels on the default policy
+                (96, 2, 1024, "mean")]
+
+
+@pytest.mark.parametrize("graph", list(_SHAPE_GRAPHS))
+@pytest.mark.parametrize("shape", LAYER_SHAPES, ids=lambda s: f"Fin{s[0]}-H{s[1]}-F{s[2]}-{s[3]}")
+def test_gat_layer_other_heads_and_widths(shape, graph):
+    """mvml_gat.nn.GATLayer at head counts 1 / 2 / 8 and widths off the defaults, on the default
+    kernel policy: mvml_gat_fold_weights / mvml_gat_unfold_grads with the head-mean residual at
+    H != 4, the attention-vector gradient, the small-K projection at other column counts and
+    Fin % 4 != 0 — forward and every gradient against float64."""
+    _layer_case(None, _SHAPE_GRAPHS[graph](), seed=3, shape=shape)
 
 
 @pytest.mark.parametrize("layer", [0, 1])
@@ -233,39 +293,66 @@ def test_gat_layer_dst_fwd(case, layer, kind, monkeypatch):
         _layer_case(layer, sb, seed=8 + layer)
 
 
-def _agg_outputs(sb, H, F, mode, seed=0):
+def _agg_outputs(sb, H, F, mode, seed=0, inputs=None, fill=None, graph=None, full=False):
     """One aggregation forward + backward through the C ABI on seeded projection rows:
-    (out, attn, gY[:, :C + 2H])."""
+    (out, attn, gY[:, :C + 2H], out_amax, out_row_amax, gy_amax, gy_row_amax).
+
+    inputs: dict with device tensors "Y" ([N, ldy], ldy >= C a multiple of 4), "elr" [N, 2H],
+    "bias" [H F] and "g_out", used instead of the seeded ones.  fill: value written into out, attn
+    and ALL of gY before the calls (default: out / attn uninitialised, gY zeros).  graph: sb's
+    device graph, built once by the caller.  full=True appends a dict with the inputs used, the
+    whole gY (pad columns included) and the two status codes, and returns instead of raising when
+    an entry point refuses the call (status != 0: the later call is not made)."""
     from mvml_gat._lib import call, lib, ptr, stream_ptr
     L = lib()
-    g = sb.to_graph().to(DEV)
+    g = graph if graph is not None else sb.to_graph().to(DEV)
     N, E = g.num_nodes(), g.num_edges()
     gen = torch.Generator(device=DEV).manual_seed(seed)
     C = L.mvml_gat_proj_cols(H, F, int(mode == 1))
-    ldy = (C + 63) // 64 * 64
-    Y = torch.randn((N, ldy), device=DEV, generator=gen) * 0.3
-    elr = torch.randn((N, 2 * H), device=DEV, generator=gen)
-    bias = torch.randn(H * F, device=DEV, generator=gen) * 0.1
     oc = F if mode == 1 else H * F
+    if inputs is None:
+        ldy = (C + 63) // 64 * 64
+        Y = torch.randn((N, ldy), device=DEV, generator=gen) * 0.3
+        elr = torch.randn((N, 2 * H), device=DEV, generator=gen)
+        bias = torch.randn(H * F, device=DEV, generator=gen) * 0.1
+    else:
+        Y, elr, bias = inputs["Y"], inputs["elr"], inputs["bias"]
+        ldy = Y.shape[1]
     out = torch.empty((N, oc), device=DEV)
     attn = torch.empty((E, H), device=DEV)
+    if fill is not None:
+        out.fill_(fill)
+        attn.fill_(fill)
     st = stream_ptr()
     orow = torch.zeros(N, dtype=torch.int32, device=DEV)
     omx = torch.zeros(1, dtype=torch.int32, device=DEV)
-    call("mvml_gat_agg_fwd", N, ptr(g.node_groups), g.num_node_groups, ptr(g.in_rowptr), ptr(g.in_src),
-         ptr(Y), ldy, H, F, ptr(elr), ptr(bias), 0.2, mode, ptr(out), ptr(attn), ptr(omx), ptr(orow), st)
-    g_out = torch.randn((N, oc), device=DEV, generator=gen)
+    fwd_args = ("mvml_gat_agg_fwd", N, ptr(g.node_groups), g.num_node_groups, ptr(g.in_rowptr), ptr(g.in_src),
+                ptr(Y), ldy, H, F, ptr(elr), ptr(bias), 0.2, mode, ptr(out), ptr(attn), ptr(omx), ptr(orow), st)
+    g_out = torch.randn((N, oc), device=DEV, generator=gen) if inputs is None else inputs["g_out"]
     ldg = (C + 2 * H + 63) // 64 * 64
-    gY = torch.zeros((N, ldg), device=DEV)
+    gY = torch.zeros((N, ldg), device=DEV) if fill is None else torch.full((N, ldg), fill, device=DEV)
     wsz = L.mvml_gat_agg_bwd_workspace_size(E, H)
-    ws = torch.empty(wsz, dtype=torch.uint8, device=DEV)
+    ws = torch.empty(max(wsz, 1), dtype=torch.uint8, device=DEV)
     gmx = torch.zeros(1, dtype=torch.int32, device=DEV)
     grow = torch.zeros(N, dtype=torch.int32, device=DEV)
-    call("mvml_gat_agg_bwd", N, ptr(g.node_groups), g.num_node_groups, ptr(g.in_rowptr), ptr(g.in_src),
-         ptr(g.out_rowptr), ptr(g.out_dst), ptr(g.out_inslot), ptr(Y), ldy, ptr(elr), ptr(attn), ptr(out),
-         ptr(g_out), H, F, 0.2, mode, ptr(gY), ldg, ptr(gmx), ptr(grow), ptr(ws), wsz, st)
+    bwd_args = ("mvml_gat_agg_bwd", N, ptr(g.node_groups), g.num_node_groups, ptr(g.in_rowptr), ptr(g.in_src),
+                ptr(g.out_rowptr), ptr(g.out_dst), ptr(g.out_inslot), ptr(Y), ldy, ptr(elr), ptr(attn), ptr(out),
+                ptr(g_out), H, F, 0.2, mode, ptr(gY), ldg, ptr(gmx), ptr(grow), ptr(ws), wsz, st)
+    res = (out, attn, gY[:, :C + 2 * H], omx, orow, gmx, grow)
+    if not full:
+        call(*fwd_args)
+        call(*bwd_args)
+        torch.cuda.synchronize()
+        return res
+    rc_f = getattr(L, fwd_args[0])(*fwd_args[1:])
+    err = L.mvml_last_error().decode(errors="replace") if rc_f else ""
+    rc_b = None
+    if rc_f == 0:
+        rc_b = getattr(L, bwd_args[0])(*bwd_args[1:])
+        err = L.mvml_last_error().decode(errors="replace") if rc_b else ""
     torch.cuda.synchronize()
-    return out, attn, gY[:, :C + 2 * H], omx, orow, gmx, grow
+    return res + ({"Y": Y, "elr": elr, "bias": bias, "g_out": g_out, "gY": gY, "C": C,
+                   "rc_fwd": rc_f, "rc_bwd": rc_b, "error": err},)
 
 
 @pytest.mark.parametrize("case", ["config2", "config3"])
