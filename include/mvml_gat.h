@@ -329,6 +329,32 @@ int mvml_gemm_f16x2_amax_colsum(int64_t M, int64_t N, int64_t K, const float* A,
  * G_r[h,:], G = [d el | d er]^T X.
  * ------------------------------------------------------------------------------------- */
 int mvml_gat_proj_cols(int H, int F, int mean_residual);
+/* Residual kinds of a GAT layer (dgl 0.9.1 GATConv.__init__): res_fc projects (a bias-free Linear,
+ * in_feats != H*F), is the identity (in_feats == H*F: rst += feat.view(N, H, F)), or is absent
+ * (residual=False).  Only a projecting res_fc has rows in Wcat and columns in Y / gY: the `res`
+ * argument of the *_res entries below is MVML_RES_PROJ (H*F residual rows), MVML_RES_MEAN (their
+ * head mean, F rows: a 'mean' GATLayer) or MVML_RES_NONE (identity or absent residual:
+ * Wcat = [fc.weight ; A_l ; A_r], C = H*F; res_fc_w / g_res_fc_w are not read / written and may
+ * be NULL).  The identity residual itself is an input of mvml_gat_agg_fwd_res (R = X, or
+ * mvml_head_mean_f32 of X for a 'mean' layer).  mvml_gat_fold_weights / mvml_gat_unfold_grads
+ * are the *_res entries with res = mean_residual ? MVML_RES_MEAN : MVML_RES_PROJ. */
+#define MVML_RES_PROJ 0
+#define MVML_RES_MEAN 1
+#define MVML_RES_NONE 2
+int mvml_gat_proj_cols_res(int H, int F, int res);
+int mvml_gat_fold_weights_res(const float* fc_w, const float* res_fc_w, const float* attn_lr, int H,
+                              int F, int Fin, int ldw, int res, float* Wcat, void* stream);
+int mvml_gat_unfold_grads_res(const float* gWcat, const float* attn_lr, int H, int F, int Fin,
+                              int ldg, int res, float* g_fc_w, float* g_res_fc_w, void* stream);
+/* Head mean of a flattened [N, H*F] matrix and its backward (the identity residual of a 'mean'
+ * GATLayer whose in_feats == H*F):  R[n, f] = (1/H) sum_h X[n, h*F + f] (heads summed in order,
+ * then / H, as torch's mean(1));  mvml_head_mean_bwd_f32 WRITES gX[n, h*F + f] = gR[n, f] / H
+ * (the caller's data-gradient product then accumulates onto it with beta = 1).  F % 4 == 0, rows
+ * 16-B aligned (ldx, ldr, ldgr, ldgx multiples of 4). */
+int mvml_head_mean_f32(int64_t N, int H, int F, const float* X, int64_t ldx, float* R, int64_t ldr,
+                       void* stream);
+int mvml_head_mean_bwd_f32(int64_t N, int H, int F, const float* gR, int64_t ldgr, float* gX,
+                           int64_t ldgx, void* stream);
 int mvml_gat_fold_weights(const float* fc_w, const float* res_fc_w, const float* attn_lr, int H,
                           int F, int Fin, int ldw, int mean_residual, float* Wcat, void* stream);
 int mvml_gat_unfold_grads(const float* gWcat, const float* attn_lr, int H, int F, int Fin,
@@ -345,6 +371,8 @@ int mvml_gat_unfold_grads(const float* gWcat, const float* attn_lr, int H, int F
  * algo MVML_GEMM_F16X2: amax_x / amax_w = bits of max |X| / max |Wcat| (mvml_absmax_f32), or
  * both NULL (computed here); w_planes must be NULL (w_plane ignored: the two-plane weight image
  * was removed in round 6).
+ * mean_residual may also be MVML_RES_NONE: Wcat and Y then hold no residual rows / columns
+ * (C = H*F, an identity or absent residual).
  * workspace: mvml_gat_proj_fwd_workspace_size(N, H, F) bytes. */
 size_t mvml_gat_proj_fwd_workspace_size(int64_t num_nodes, int H, int F);
 int mvml_gat_proj_fwd(int64_t num_nodes, const float* X, int64_t ldx, int64_t K,
@@ -390,6 +418,25 @@ int mvml_gat_agg_fwd(int64_t num_nodes, const int32_t* node_groups, int64_t num_
                      int H, int F, const float* elr, const float* bias, float slope, int mode,
                      float* out, float* attn, uint32_t* out_amax, uint32_t* out_row_amax,
                      void* stream);
+/* mvml_gat_agg_fwd with the residual as an input of its own and an optional bias: the three
+ * residual kinds of dgl 0.9.1 GATConv (projected / identity / none) and bias=False.
+ *   R, ldr: the residual rows, H*F wide in modes 0 / 2 and F wide in mode 1 (the caller supplies
+ *           the head mean, as the projection-row layout does: mvml_head_mean_f32), 16-byte
+ *           aligned, ldr a multiple of 4 and >= that width.  R == NULL: no residual.
+ *   bias:   [H*F], or NULL: no bias.
+ *   Y:      needs only [Z] (ldy >= H*F); elr is a separate argument as before.
+ * mvml_gat_agg_fwd(Y, ...) IS this entry with R = Y + H*F, ldr = ldy: that layout, with a bias,
+ * runs the kernels compiled for it under every option, bitwise as before.  Any other R, R == NULL
+ * or bias == NULL runs the destination-wave kernel's separate-residual instances (one wave per
+ * atom; MVML_OPT_DST_FWD 2: the softmax as its own launch first, 0 and 1: inside the wave) at
+ * every supported shape; the window / gather kernels are not built for it, so every option value
+ * is redirected there before anything is launched.  Shapes, maxima and the MVML_ERR_INVALID
+ * contract as mvml_gat_agg_fwd; a misaligned R / ldr is refused the same way. */
+int mvml_gat_agg_fwd_res(int64_t num_nodes, const int32_t* node_groups, int64_t num_groups,
+                         const int32_t* in_rowptr, const int32_t* in_src, const float* Y,
+                         int64_t ldy, int H, int F, const float* elr, const float* R, int64_t ldr,
+                         const float* bias, float slope, int mode, float* out, float* attn,
+                         uint32_t* out_amax, uint32_t* out_row_amax, void* stream);
 /* Backward of mvml_gat_agg_fwd (DGL GSpMM / GSDDMM / EdgeSoftmax backward + torch autograd of
  * residual, bias, ELU, mean).  Atomic-free: the u_mul_e-sum transpose is a gather over the
  * out-CSR; one workgroup per node group reads Z, g_out and writes dZ once (molecule groups).
@@ -412,7 +459,34 @@ int mvml_gat_agg_bwd(int64_t num_nodes, const int32_t* node_groups, int64_t num_
                      const float* g_out, int H, int F, float slope, int mode, float* gY,
                      int64_t ldgy, uint32_t* gy_amax, uint32_t* gy_row_amax, void* workspace,
                      size_t workspace_bytes, void* stream);
-/* A GATConv's whole backward in one call (SURVEY §8(b)'s proj_bwd; the autograd of dgl GATConv /
+/* Backward of mvml_gat_agg_fwd_res: dR leaves through an argument of its own.
+ *   gY[n] = [ dZ_agg (H*F) | ... | d el (H) | d er (H) ] with [d el | d er] at column elr_col
+ *           (>= H*F; ldgy >= elr_col + 2H): H*F for an identity or absent residual, C for the
+ *           projection-row layout.
+ *   gR, ldgr: receives exactly what the dR block of mvml_gat_agg_bwd's gY receives (g_rst in
+ *           modes 0 / 2, H*F wide; g_out in mode 1, F wide); 16-byte aligned, ldgr a multiple of 4
+ *           and >= that width.  The identity residual's share of dL/dX is gR (mode 1:
+ *           mvml_head_mean_bwd_f32 of it), the bias gradient its column sums (mode 1: / H).
+ *           gR == NULL: not formed (no residual and no bias).
+ *   gy_amax / gy_row_amax cover the columns that exist: dZ_agg, d el, d er, and dR only where it
+ *           lies in gY's rows (gR == gY + H*F, ldgr == ldgy).
+ * mvml_gat_agg_bwd(gY, ...) IS this entry with gR = gY + H*F, ldgr = ldgy, elr_col = C, which
+ * runs the kernels of that layout under every option, bitwise as before.  A dR apart from gY (or
+ * none) is native in the LDS molecule window, the per-atom pair and both source-atom kernels;
+ * redirected before anything is launched: a head-mean layer always runs by source atom
+ * (MVML_OPT_MEAN_SRC 0 as 1, at every F), and the big windows are off (MVML_OPT_BIG_WINDOW 1 as
+ * 0: their groups take the per-atom pair). */
+int mvml_gat_agg_bwd_res(int64_t num_nodes, const int32_t* node_groups, int64_t num_groups,
+                         const int32_t* in_rowptr, const int32_t* in_src, const int32_t* out_rowptr,
+                         const int32_t* out_dst, const int32_t* out_inslot, const float* Y,
+                         int64_t ldy, const float* elr, const float* attn, const float* out,
+                         const float* g_out, int H, int F, float slope, int mode, float* gY,
+                         int64_t ldgy, int64_t elr_col, float* gR, int64_t ldgr, uint32_t* gy_amax,
+                         uint32_t* gy_row_amax, void* workspace, size_t workspace_bytes, void* stream);
+/* (Projected residual with a bias only: the identity / absent residual and bias=False layers of
+ * mvml_gat_agg_fwd_res run their backward through mvml_gat.functional.GATLayerFunction or the
+ * separate entry points; extending this entry to them is not done.)
+ * A GATConv's whole backward in one call (SURVEY §8(b)'s proj_bwd; the autograd of dgl GATConv /
  * dgllife GATLayer, model.py:81, 91): from the forward's X ([N][Fp], Fp = Fin rounded up to 4,
  * zero-padded), Wcat and attn_lr (mvml_gat_fold_weights' inputs / output), Y (ldy), elr, attn, out
  * and g_out = dL/d out, it writes g_X ([N][Fin]; NULL: not formed), g_fc and g_res ([H F][Fin]:

@@ -5,6 +5,14 @@
 //   Y[n] = [ Z (H*F) | R (RW) ]            RW = H*F (flatten modes) or F (mean mode)
 // In mean mode (dgllife's last GATLayer, agg 'mean') only the head-mean of the residual is ever
 // used, so the GEMM produces R_mean = X * mean_h(W_res_h)^T directly (F columns instead of H*F).
+// That is GATConv's projecting res_fc.  Its other two residual kinds (dgl 0.9.1 GATConv.__init__:
+// nn.Identity() when in_feats == H*F, none with residual=False) and bias=False have no residual
+// columns: mvml_gat_agg_fwd_res / mvml_gat_agg_bwd_res take R (its own row stride; NULL: none),
+// dR (gR; NULL: not formed) and an optional bias as arguments, and Y / gY hold [Z] / [dZ | d el |
+// d er] only.  The projection-row entries are those called with R = Y + H*F, gR = gY + H*F.
+// Native for a separate residual: the destination-wave forward and the LDS backward (compile-time
+// SEP instances; the in-row instances are unchanged), the per-atom pair and the source-atom
+// backwards (run-time gR); launch_fwd / launch_bwd redirect every other option value.
 //
 // Forward, per destination v (rows of the in-CSR, in-edges in ascending edge id):
 //   el[n,h] = <Z[n,h,:], attn_l[h,:]>, er[n,h] = <Z[n,h,:], attn_r[h,:]>   GATConv el / er, from
@@ -889,13 +897,17 @@ gat_agg_fwd_gather_kernel(const int32_t* __restrict__ plan, int64_t G, const int
 // (12 fewer VGPRs live across the gather loop in mean mode: five waves per SIMD instead of four)
 // (measured: the head-mean form held to six waves per SIMD spills 17 VGPRs with the fused softmax
 // and ran 6.1 -> 7.6-8.1 ms on config 5; even without it)
-template <int H, int MODE, int NJ, int U, bool SM, bool LR = false>
+// SEP (mvml_gat_agg_fwd_res): the residual rows come from R (row stride ldr; NULL: no residual)
+// instead of Y's columns past H F, and bias may be NULL.  !SEP is the in-row layout with a
+// bias, compiled exactly as before (R / ldr unused).
+template <int H, int MODE, int NJ, int U, bool SM, bool LR = false, bool SEP = false>
 __global__ void __launch_bounds__(256, LR ? (MODE == 1 ? 5 : 8) : 1)
 gat_agg_fwd_dst_kernel(int64_t N, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ in_src,
                        const float* __restrict__ Y, int64_t ldy, int F, const float* __restrict__ bias,
                        const float* __restrict__ elr, float slope, float* __restrict__ attn,
                        float* __restrict__ out, uint32_t* __restrict__ out_amax,
-                       uint32_t* __restrict__ out_rows) {
+                       uint32_t* __restrict__ out_rows, const float* __restrict__ R = nullptr,
+                       int64_t ldr = 0) {
   constexpr bool PAIR = MODE == 1 && H >= 2;
   constexpr int NH = PAIR ? H / 2 : 1;  // heads per lane (mean mode); 1 register set (flatten)
   const int lane = threadIdx.x & 63;
@@ -909,6 +921,16 @@ gat_agg_fwd_dst_kernel(int64_t N, const int32_t* __restrict__ rowptr, const int3
     const int hp = PAIR ? lane >> 5 : 0;       // mean: this lane's half (heads hp H/2 ..)
     const int ql = PAIR ? (lane & 31) : lane;  // mean: f-float4 base of this lane
     const float* yv = Y + v * ldy;
+    // this atom's residual row (SEP: NULL without a residual) and the bias (SEP: may be NULL)
+    const float* rv = SEP ? (R ? R + v * ldr : nullptr) : yv + HF;
+    auto ldres = [&](int c) -> float4 {
+      if constexpr (SEP) return rv ? ld4nt(rv + c) : f4(0.f);
+      else return ld4nt(rv + c);
+    };
+    auto ldbias = [&](int c) -> float4 {
+      if constexpr (SEP) return bias ? ld4(bias + c) : f4(0.f);
+      else return ld4(bias + c);
+    };
     bool ok[NJ];
     int hc[NJ];   // flatten: the head of each column slot
     int cz[NJ];   // float offset of slot j in a projection row (mean: of head hp * NH)
@@ -921,13 +943,13 @@ gat_agg_fwd_dst_kernel(int64_t N, const int32_t* __restrict__ rowptr, const int3
         hc[j] = 0;
         cz[j] = hp * NH * F + 4 * q;
         // the residual first (its HBM latency overlaps the softmax); the lower half stores out
-        if constexpr (!LR) res[j] = (ok[j] && hp == 0) ? ld4nt(yv + HF + 4 * q) : f4(0.f);
+        if constexpr (!LR) res[j] = (ok[j] && hp == 0) ? ldres(4 * q) : f4(0.f);
       } else {
         const int c = lane + 64 * j;
         ok[j] = 4 * c < HF;
         hc[j] = ok[j] ? 4 * c / F : 0;
         cz[j] = 4 * c;
-        if constexpr (!LR) res[j] = ok[j] ? ld4nt(yv + HF + 4 * c) : f4(0.f);
+        if constexpr (!LR) res[j] = ok[j] ? ldres(4 * c) : f4(0.f);
       }
 #pragma unroll
       for (int h = 0; h < NH; ++h) acc[h][j] = f4(0.f);
@@ -1051,9 +1073,9 @@ gat_agg_fwd_dst_kernel(int64_t N, const int32_t* __restrict__ rowptr, const int3
       for (int j = 0; j < NJ; ++j) {
         if constexpr (MODE == 1) {
           const int q = ql + (PAIR ? 32 : 64) * j;
-          res[j] = (ok[j] && hp == 0) ? ld4nt(yv + HF + 4 * q) : f4(0.f);
+          res[j] = (ok[j] && hp == 0) ? ldres(4 * q) : f4(0.f);
         } else {
-          res[j] = ok[j] ? ld4nt(yv + HF + 4 * (lane + 64 * j)) : f4(0.f);
+          res[j] = ok[j] ? ldres(4 * (lane + 64 * j)) : f4(0.f);
         }
       }
     }
@@ -1065,7 +1087,7 @@ gat_agg_fwd_dst_kernel(int64_t N, const int32_t* __restrict__ rowptr, const int3
         const int qc = ok[j] ? 4 * q : 0;
         float4 t[NH];
 #pragma unroll
-        for (int h = 0; h < NH; ++h) t[h] = add4(acc[h][j], ld4(bias + (hp * NH + h) * F + qc));
+        for (int h = 0; h < NH; ++h) t[h] = add4(acc[h][j], ldbias((hp * NH + h) * F + qc));
         float4 tot = t[0];
 #pragma unroll
         for (int h = 1; h < NH; ++h) tot = add4(tot, t[h]);
@@ -1082,7 +1104,7 @@ gat_agg_fwd_dst_kernel(int64_t N, const int32_t* __restrict__ rowptr, const int3
         st4nt(out + v * F + 4 * q, o);
       } else {
         if (!ok[j]) continue;
-        o = add4(add4(acc[0][j], res[j]), ld4(bias + cz[j]));
+        o = add4(add4(acc[0][j], res[j]), ldbias(cz[j]));
         if (MODE == 0) o = make_float4(elu(o.x), elu(o.y), elu(o.z), elu(o.w));
         st4nt(out + v * HF + cz[j], o);
       }
@@ -1222,8 +1244,11 @@ __device__ __forceinline__ float grp_sum_hi(float v) {
 // source row slice once per in-edge: half the LDS bytes of an edge-per-thread dot.
 // BIG: the out-CSR (s_odst / s_oslot) is read from global memory (g_odst / g_oslot, group
 // edge base e0, first atom a0) instead of LDS, which the big window needs for its rows.
+// SEP (mvml_gat_agg_bwd_res): dR goes to its own rows (resource rR, row pitch ldri floats; an
+// empty resource when it is not formed: the stores are dropped) and stays out of the |max|
+// bookkeeping, which then covers gY's columns only.
 template <int H, int MODE, int NPA, int CW, int NT = 16 * CW, int WIN = kWinL, int ECAP = kECap,
-          bool BIG = false>
+          bool BIG = false, bool SEP = false>
 __device__ __forceinline__ float bwd_lds_chunks(
     float4* zs, float4* gs, const float* s_att, const int* s_odst, const int* s_oslot,
     const int* s_orp, const int* s_rp, const uint16_t* s_src, float* s_ga,
@@ -1232,7 +1257,8 @@ __device__ __forceinline__ float bwd_lds_chunks(
     const int32_t* __restrict__ g_oslot = nullptr, int e0 = 0, int a0 = 0,
     const uint32_t* s_segI = nullptr, int nsegI = 0, const uint32_t* s_segO = nullptr,
     int nsegO = 0, const int* s_rs = nullptr, float4* s_part = nullptr,
-    const uint32_t* s_oxe = nullptr, const uint16_t* s_oxb = nullptr, float* s_rmx = nullptr) {
+    const uint32_t* s_oxe = nullptr, const uint16_t* s_oxb = nullptr, float* s_rmx = nullptr,
+    __amdgpu_buffer_rsrc_t rR = __amdgpu_buffer_rsrc_t(), int ldri = 0) {
   static_assert(kEC == 5, "in-edge writer lanes assume 5 cached in-edges");
   constexpr int LPD = CW / 4, DPP = NT / LPD;
   auto odst = [&](int o) -> int { if constexpr (BIG) return g_odst[e0 + o] - a0; else return s_odst[o]; };
@@ -1249,6 +1275,8 @@ __device__ __forceinline__ float bwd_lds_chunks(
   // unconditional, so the compiler's vmcnt counts are exact
   const uint32_t noY = 4u * (uint32_t)(nr * ldyi), noGo = 4u * (uint32_t)(nr * ocols);
   const uint32_t noO = 4u * (uint32_t)(nr * HF), noG = 4u * (uint32_t)(nr * ldgi);
+  auto rrow = [&](int p) { return 4u * (uint32_t)((ds + DPP * p) * ldri); };  // SEP: dR rows
+  const uint32_t noR = 4u * (uint32_t)(nr * ldri);
   float gmx = 0.f;  // |max| of this thread's stores into gY (live rows, real chunks)
   float rmx[NPA];   // ... per row (s_rmx: the rows' |max| over dZ and dR, for per-row scales)
   bool live[NPA];
@@ -1342,12 +1370,20 @@ __device__ __forceinline__ float bwd_lds_chunks(
       zs[r * LPD + (q ^ bwd_sw<LPD>(r))] = R.z[p];
       if (MODE != 1) {
         gs[r * LPD + (q ^ bwd_sw<LPD>(r))] = g;
-        buf_st4(rG, ok ? grow(p) + 4u * (uint32_t)(HF + col_of(k)) : noG, g);
-        if (ok && r < nr) rmx[p] = amax4(rmx[p], g);
+        if constexpr (SEP) {
+          buf_st4(rR, ok ? rrow(p) + 4u * (uint32_t)col_of(k) : noR, g);
+        } else {
+          buf_st4(rG, ok ? grow(p) + 4u * (uint32_t)(HF + col_of(k)) : noG, g);
+          if (ok && r < nr) rmx[p] = amax4(rmx[p], g);
+        }
       } else if (h == 0) {  // uniform branch: an all-out-of-range store is not free
         gs[r * LPD + (q ^ bwd_sw<LPD>(r))] = g;
-        buf_st4(rG, ok ? grow(p) + 4u * (uint32_t)(HF + fc * CW + 4 * q) : noG, R.g[p]);
-        if (ok && r < nr) rmx[p] = amax4(rmx[p], R.g[p]);
+        if constexpr (SEP) {
+          buf_st4(rR, ok ? rrow(p) + 4u * (uint32_t)(fc * CW + 4 * q) : noR, R.g[p]);
+        } else {
+          buf_st4(rG, ok ? grow(p) + 4u * (uint32_t)(HF + fc * CW + 4 * q) : noG, R.g[p]);
+          if (ok && r < nr) rmx[p] = amax4(rmx[p], R.g[p]);
+        }
       }
     }
   };
@@ -1486,7 +1522,8 @@ __device__ __forceinline__ float bwd_lds_chunks(
 // chunks, 1024 threads (two passes of 256 rows), out-CSR and logits read from global memory
 // (LDS holds the rows, the attention, the edge gradients and the in-CSR), one workgroup per CU
 // walking the list.
-template <int H, int MODE, int CW, int NT = 16 * CW, int WIN = kWinL, int ECAP = kECap, bool BIG = false>
+template <int H, int MODE, int CW, int NT = 16 * CW, int WIN = kWinL, int ECAP = kECap, bool BIG = false,
+          bool SEP = false>
 __global__ void __launch_bounds__(NT, MVML_BWD_WAVES)
 gat_agg_bwd_lds_kernel(const int32_t* __restrict__ plan, int64_t G, const int32_t* __restrict__ rowptr,
                        const int32_t* __restrict__ in_src, const int32_t* __restrict__ out_rowptr,
@@ -1495,7 +1532,8 @@ gat_agg_bwd_lds_kernel(const int32_t* __restrict__ plan, int64_t G, const int32_
                        const float* __restrict__ attn, const float* __restrict__ out,
                        const float* __restrict__ g_out, float slope, float* __restrict__ gY,
                        int64_t ldgy, int C, uint32_t* __restrict__ gy_amax,
-                       uint32_t* __restrict__ gy_rows) {
+                       uint32_t* __restrict__ gy_rows, float* __restrict__ gR = nullptr,
+                       int64_t ldgr = 0) {
   constexpr int LPD = CW / 4;
   constexpr int DPP = NT / LPD;
   constexpr int NPM = WIN / DPP;  // passes over a full window
@@ -1560,6 +1598,10 @@ gat_agg_bwd_lds_kernel(const int32_t* __restrict__ plan, int64_t G, const int32_
   const __amdgpu_buffer_rsrc_t rG = make_rsrc(gY + (int64_t)a0 * ldgy, (uint32_t)(nr * ldgi) * 4u);
   const __amdgpu_buffer_rsrc_t rGo = make_rsrc(g_out + (int64_t)a0 * ocols, (uint32_t)(nr * ocols) * 4u);
   const __amdgpu_buffer_rsrc_t rO = make_rsrc(out + (int64_t)a0 * HF, MODE == 0 ? (uint32_t)(nr * HF) * 4u : 0u);
+  // SEP: the dR rows of the group (not formed: an empty range over gY, every store dropped)
+  const int ldri = SEP && gR ? (int)ldgr : 0;
+  const __amdgpu_buffer_rsrc_t rR =
+      make_rsrc(SEP && gR ? gR + (int64_t)a0 * ldgr : gY, SEP && gR ? (uint32_t)(nr * ldri) * 4u : 0u);
   for (int i = tid; i < ne * H; i += NT) s_ga[i] = 0.f;
   __syncthreads();  // CSR / attention staged
   int nsegI = 0, nsegO = 0;
@@ -1586,10 +1628,10 @@ gat_agg_bwd_lds_kernel(const int32_t* __restrict__ plan, int64_t G, const int32_
     __syncthreads();
   }
 #define MVML_BWD_CHUNKS(NPA)                                                                       \
-  gmx = fmaxf(gmx, bwd_lds_chunks<H, MODE, NPA, CW, NT, WIN, ECAP, BIG>(zs, gs, s_att, s_odst, s_oslot, s_orp, s_rp,  \
+  gmx = fmaxf(gmx, bwd_lds_chunks<H, MODE, NPA, CW, NT, WIN, ECAP, BIG, SEP>(zs, gs, s_att, s_odst, s_oslot, s_orp, s_rp,  \
                                                        s_src, s_ga, rY, ldyi, rGo, rO, rG, ldgi, nr, F, \
                                                        out_dst, out_inslot, e0, a0, s_segI, nsegI, \
-                                                       s_segO, nsegO, s_rs, s_part, s_oxe, s_oxb, s_rmx))
+                                                       s_segO, nsegO, s_rs, s_part, s_oxe, s_oxb, s_rmx, rR, ldri))
   if (nr <= DPP) MVML_BWD_CHUNKS(1);
   else if (NPM == 2 || nr <= 2 * DPP) MVML_BWD_CHUNKS(2);
   else if (nr <= 3 * DPP) MVML_BWD_CHUNKS((NPM > 2 ? 3 : 2));
@@ -1650,7 +1692,8 @@ gat_agg_bwd_dst_kernel(int64_t N, const int32_t* __restrict__ groups, int64_t G,
                        const float* __restrict__ g_out, int F, float slope, int mode,
                        float* __restrict__ gpre, float* __restrict__ gY, int64_t ldgy,
                        float* __restrict__ gelr, int64_t ldgl, int skip_big,
-                       uint32_t* __restrict__ gy_amax, uint32_t* __restrict__ gy_rows) {
+                       uint32_t* __restrict__ gy_amax, uint32_t* __restrict__ gy_rows,
+                       float* gR, int64_t ldgr, int ramax) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   float gmx = 0.f;  // |max| of this thread's gY stores (block-uniform early returns only)
   // G > 0: one block per backward fallback group of the plan; G == 0: one wave per atom over
@@ -1687,20 +1730,22 @@ gat_agg_bwd_dst_kernel(int64_t N, const int32_t* __restrict__ groups, int64_t G,
   }
   // dR[v]: per-head g_rst (flatten modes) or g_out (head-mean residual).  Written here so the
   // source pass can gather finished g_rst rows from gY instead of re-deriving them per edge.
-  float* gyv = gY + v * ldgy;
+  // gR: the dR rows (gY + H F with ldgr = ldgy in the projection-row layout; NULL: not formed);
+  // ramax: whether they count in the |max| bookkeeping (they do where they are part of gY)
+  float* grv = gR ? gR + v * ldgr : nullptr;
   float rmx = 0.f;  // this row's |max| (dR, d er) for gy_rows
 #pragma unroll
   for (int c = 0; c < VPL; ++c) {
     const int col = 4 * (lane + 64 * c);
     if (mode != 1) {
-      if (okc[c]) {
-        st4(gyv + HF + col, gr[c]);
-        rmx = amax4(rmx, gr[c]);
+      if (okc[c] && grv) {
+        st4(grv + col, gr[c]);
+        if (ramax) rmx = amax4(rmx, gr[c]);
       }
-    } else if (col < F) {
+    } else if (col < F && grv) {
       const float4 go = ld4(g_out + v * F + col);
-      st4(gyv + HF + col, go);
-      rmx = amax4(rmx, go);
+      st4(grv + col, go);
+      if (ramax) rmx = amax4(rmx, go);
     }
   }
   float er[H];
@@ -1802,7 +1847,7 @@ gat_agg_bwd_src_kernel(int64_t N, const int32_t* __restrict__ groups, int64_t G,
                        const float* __restrict__ out, const float* __restrict__ g_out, int F,
                        int mode, float* __restrict__ gY, int64_t ldgy, float* __restrict__ gelr,
                        int64_t ldgl, int skip_big, uint32_t* __restrict__ gy_amax,
-                       uint32_t* __restrict__ gy_rows) {
+                       uint32_t* __restrict__ gy_rows, const float* gR, int64_t ldgr) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   float gmx = 0.f;  // |max| of this thread's gY stores (block-uniform early returns only)
   // G > 0: one block per backward fallback group of the plan; G == 0: one wave per atom over
@@ -1863,14 +1908,16 @@ gat_agg_bwd_src_kernel(int64_t N, const int32_t* __restrict__ groups, int64_t G,
       float a0[H], a1[H];
 #pragma unroll
       for (int h = 0; h < H; ++h) { a0[h] = rl(a_l[h], j); a1[h] = rl(a_l[h], j1); }
-      const float* gw0 = gY + (int64_t)w0 * ldgy + HF;  // g_rst rows written by the dst pass
-      const float* gw1 = gY + (int64_t)w1 * ldgy + HF;
+      // g_rst rows written by the dst pass (gR == NULL: dR is not formed, re-derived per edge)
+      const bool derive = mode == 1 || !gR;
+      const float* gw0 = gR + (int64_t)w0 * ldgr;
+      const float* gw1 = gR + (int64_t)w1 * ldgr;
       float4 g0[VPL], g1[VPL];
 #pragma unroll
       for (int c = 0; c < VPL; ++c) {
         const int col = 4 * (lane + 64 * c);
-        g0[c] = !okc[c] ? f4(0.f) : (mode == 1) ? grst_of(g_out, out, w0, col, HF, F, H, mode) : ld4(gw0 + col);
-        g1[c] = !okc[c] ? f4(0.f) : (mode == 1) ? grst_of(g_out, out, w1, col, HF, F, H, mode) : ld4(gw1 + col);
+        g0[c] = !okc[c] ? f4(0.f) : derive ? grst_of(g_out, out, w0, col, HF, F, H, mode) : ld4(gw0 + col);
+        g1[c] = !okc[c] ? f4(0.f) : derive ? grst_of(g_out, out, w1, col, HF, F, H, mode) : ld4(gw1 + col);
       }
 #pragma unroll
       for (int c = 0; c < VPL; ++c)
@@ -1922,12 +1969,13 @@ gat_mean_bwd_src_kernel(int64_t N, const int32_t* __restrict__ out_rowptr,
                         const float* __restrict__ Y, int64_t ldy, const float* __restrict__ attn,
                         const float* __restrict__ g_out, int F, float* __restrict__ ga,
                         float* __restrict__ gY, int64_t ldgy, uint32_t* __restrict__ gy_amax,
-                        uint32_t* __restrict__ gy_rows) {
+                        uint32_t* __restrict__ gy_rows, float* gR, int64_t ldgr, int ramax) {
   const int lane = threadIdx.x & 63;
   const int64_t u = xcd_block(blockIdx.x, gridDim.x) * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   float gmx = 0.f;
   if (u < N) {  // (no early return: block_amax_commit below has a barrier)
     const int nf4 = F / 4, HF = H * F;
+    float* gru = gR ? gR + u * ldgr : nullptr;  // dR row (gat_agg_bwd_dst_kernel: gR / ramax)
     const float hh = (float)H;
     bool okj[NJ];
     float4 z[H][NJ], dz[H][NJ];
@@ -1943,10 +1991,10 @@ gat_mean_bwd_src_kernel(int64_t N, const int32_t* __restrict__ out_rowptr,
         z[h][j] = okj[j] ? ld4nt(zu + h * F + 4 * fj) : f4(0.f);
         dz[h][j] = f4(0.f);
       }
-      if (okj[j]) {  // dR[u] = g_out[u] (the head-mean residual's gradient)
+      if (okj[j] && gru) {  // dR[u] = g_out[u] (the head-mean residual's gradient)
         const float4 go = ld4(g_out + u * F + 4 * fj);
-        st4nt(gyu + HF + 4 * fj, go);
-        rmx = amax4(rmx, go);
+        st4nt(gru + 4 * fj, go);
+        if (ramax) rmx = amax4(rmx, go);
       }
     }
     const int ob = out_rowptr[u], oe = out_rowptr[u + 1];
@@ -2088,7 +2136,8 @@ gat_flat_bwd_src1_kernel(int64_t N, const int32_t* __restrict__ out_rowptr,
                          const float* __restrict__ Y, int64_t ldy, const float* __restrict__ attn,
                          const float* __restrict__ out, const float* __restrict__ g_out, int F,
                          float* __restrict__ ga, float* __restrict__ gY, int64_t ldgy,
-                         uint32_t* __restrict__ gy_amax, uint32_t* __restrict__ gy_rows) {
+                         uint32_t* __restrict__ gy_amax, uint32_t* __restrict__ gy_rows,
+                         float* gR, int64_t ldgr, int ramax) {
   const int lane = threadIdx.x & 63;
   const int64_t u = xcd_block(blockIdx.x, gridDim.x) * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   float gmx = 0.f;
@@ -2117,10 +2166,10 @@ gat_flat_bwd_src1_kernel(int64_t N, const int32_t* __restrict__ out_rowptr,
       hc[c] = okc[c] ? col / F : 0;
       z[c] = okc[c] ? ld4nt(Y + u * ldy + col) : f4(0.f);
       dz[c] = f4(0.f);
-      if (okc[c]) {  // dR[u] = g_rst[u]
+      if (okc[c] && gR) {  // dR[u] = g_rst[u] (gat_agg_bwd_dst_kernel: gR / ramax)
         const float4 g = grst(u, c);
-        st4nt(gY + u * ldgy + HF + col, g);
-        rmx = amax4(rmx, g);
+        st4nt(gR + u * ldgr + col, g);
+        if (ramax) rmx = amax4(rmx, g);
       }
     }
     const int ob = out_rowptr[u], oe = out_rowptr[u + 1];
@@ -2179,7 +2228,7 @@ int launch_flat_src1(int64_t N, const int32_t* rp, const int32_t* src, const int
                      const int32_t* odst, const int32_t* oslot, const float* Y, int64_t ldy,
                      const float* elr, const float* attn, const float* out, const float* g_out, int F,
                      float slope, int mode, float* gpre, float* gY, int64_t ldgy, int C, uint32_t* gy_amax,
-                     uint32_t* gy_rows, hipStream_t st) {
+                     uint32_t* gy_rows, hipStream_t st, float* gR, int64_t ldgr, int ramax) {
   const int HF = H * F;
   const int nj = (int)ceil_div(HF / 4, 64);
   const unsigned b4 = (unsigned)ceil_div(N, 4), b256 = (unsigned)ceil_div(N, 256);
@@ -2189,16 +2238,16 @@ int launch_flat_src1(int64_t N, const int32_t* rp, const int32_t* src, const int
   do {                                                                                                       \
     if (mode == 0 && u1)                                                                                     \
       gat_flat_bwd_src1_kernel<H, NJ, 0, 1><<<b4, 256, 0, st>>>(                                              \
-          N, orp, odst, oslot, Y, ldy, attn, out, g_out, F, gpre, gY, ldgy, blk_amax, gy_rows);               \
+          N, orp, odst, oslot, Y, ldy, attn, out, g_out, F, gpre, gY, ldgy, blk_amax, gy_rows, gR, ldgr, ramax); \
     else if (mode == 0)                                                                                      \
       gat_flat_bwd_src1_kernel<H, NJ, 0><<<b4, 256, 0, st>>>(                                                 \
-          N, orp, odst, oslot, Y, ldy, attn, out, g_out, F, gpre, gY, ldgy, blk_amax, gy_rows);               \
+          N, orp, odst, oslot, Y, ldy, attn, out, g_out, F, gpre, gY, ldgy, blk_amax, gy_rows, gR, ldgr, ramax); \
     else if (u1)                                                                                             \
       gat_flat_bwd_src1_kernel<H, NJ, 2, 1><<<b4, 256, 0, st>>>(                                              \
-          N, orp, odst, oslot, Y, ldy, attn, out, g_out, F, gpre, gY, ldgy, blk_amax, gy_rows);               \
+          N, orp, odst, oslot, Y, ldy, attn, out, g_out, F, gpre, gY, ldgy, blk_amax, gy_rows, gR, ldgr, ramax); \
     else                                                                                                     \
       gat_flat_bwd_src1_kernel<H, NJ, 2><<<b4, 256, 0, st>>>(                                                 \
-          N, orp, odst, oslot, Y, ldy, attn, out, g_out, F, gpre, gY, ldgy, blk_amax, gy_rows);               \
+          N, orp, odst, oslot, Y, ldy, attn, out, g_out, F, gpre, gY, ldgy, blk_amax, gy_rows, gR, ldgr, ramax); \
   } while (0)
   switch (nj) {
     case 1: MVML_FLAT_SRC1(1); break;
@@ -2228,14 +2277,19 @@ int launch_mean_src(int64_t N, const int32_t* rp, const int32_t* src, const int3
                     const int32_t* odst, const int32_t* oslot, const float* Y, int64_t ldy,
                     const float* elr, const float* attn, const float* g_out, int F, float slope,
                     float* gpre, float* gY, int64_t ldgy, int C, uint32_t* gy_amax, uint32_t* gy_rows,
-                    hipStream_t st) {
+                    hipStream_t st, float* gR, int64_t ldgr, int ramax, bool wide = false) {
   const int nj = (int)ceil_div(F / 4, 64);
   const unsigned b4 = (unsigned)ceil_div(N, 4), b256 = (unsigned)ceil_div(N, 256);
   // with per-row maxima requested, max |gY| comes from them at the end (no per-block atomics)
   uint32_t* const blk_amax = gy_rows ? nullptr : gy_amax;
 #define MVML_MEAN_SRC(NJ) \
   gat_mean_bwd_src_kernel<H, NJ><<<b4, 256, 0, st>>>( \
-      N, orp, odst, oslot, Y, ldy, attn, g_out, F, gpre, gY, ldgy, blk_amax, gy_rows)
+      N, orp, odst, oslot, Y, ldy, attn, g_out, F, gpre, gY, ldgy, blk_amax, gy_rows, gR, ldgr, ramax)
+  // wide (mvml_gat_agg_bwd_res with dR apart from gY): F > 1024, which only H = 1 reaches, takes
+  // an 8-slot instance, so that this path holds every shape there
+  if (nj > 4 && wide && H == 1) {
+    if constexpr (H == 1) MVML_MEAN_SRC(8);
+  } else
   switch (nj) {
     case 1: MVML_MEAN_SRC(1); break;
     case 2: MVML_MEAN_SRC(2); break;
@@ -2259,7 +2313,51 @@ template <int H>
 int launch_fwd(int64_t N, const int32_t* groups, int64_t G, const int32_t* rp, const int32_t* src,
                const float* Y, int64_t ldy, int F, const float* bias, float slope, int mode,
                float* out, float* attn, const float* elr, uint32_t* out_amax, uint32_t* out_rows,
-               hipStream_t st) {
+               hipStream_t st, bool sep = false, const float* R = nullptr, int64_t ldr = 0) {
+  // A residual apart from Y's rows, no residual or no bias (mvml_gat_agg_fwd_res): the
+  // destination-wave kernel's SEP instances are the one native path, at every shape (head-mean
+  // rows past 4 slots, H <= 2 only, take an 8-slot instance); every option value is redirected
+  // to them here, before anything is launched (dst_fwd 0 runs as 1: the softmax in the wave).
+  if (sep) {
+    const unsigned b4 = (unsigned)ceil_div(N, 4);
+    const bool sm = option(MVML_OPT_DST_FWD) != 2;
+    uint32_t* const blk_amax = out_rows ? nullptr : out_amax;
+    if (!sm) {
+      gat_softmax_dst_kernel<H><<<(unsigned)ceil_div(N * H, 256), 256, 0, st>>>(N, rp, src, elr, slope, attn);
+      int rc = check_launch("gat_softmax_dst_kernel");
+      if (rc) return rc;
+    }
+#define MVML_DST_FWD_SEP(M, NJ, U)                                                                \
+  do {                                                                                            \
+    if (sm)                                                                                       \
+      gat_agg_fwd_dst_kernel<H, M, NJ, U, true, false, true><<<b4, 256, 0, st>>>(                 \
+          N, rp, src, Y, ldy, F, bias, elr, slope, attn, out, blk_amax, out_rows, R, ldr);        \
+    else                                                                                          \
+      gat_agg_fwd_dst_kernel<H, M, NJ, U, false, false, true><<<b4, 256, 0, st>>>(                \
+          N, rp, src, Y, ldy, F, bias, elr, slope, attn, out, blk_amax, out_rows, R, ldr);        \
+  } while (0)
+    if (mode == 1) {
+      const int nj = (int)ceil_div(F / 4, H >= 2 ? 32 : 64);
+      if (nj == 1) MVML_DST_FWD_SEP(1, 1, 4);
+      else if (nj == 2) MVML_DST_FWD_SEP(1, 2, 2);
+      else if (nj == 3) MVML_DST_FWD_SEP(1, 3, 1);
+      else if (nj == 4) MVML_DST_FWD_SEP(1, 4, 2);
+      else if constexpr (H <= 2) MVML_DST_FWD_SEP(1, 8, 1);  // F > 512 (H = 2) / 1024 (H = 1)
+    } else {
+      const int nj = (int)ceil_div(H * F / 4, 64);
+#define MVML_DST_FWD_SEP_F(NJ, U) do { if (mode == 0) MVML_DST_FWD_SEP(0, NJ, U); else MVML_DST_FWD_SEP(2, NJ, U); } while (0)
+      if (nj == 1) MVML_DST_FWD_SEP_F(1, 4);
+      else if (nj == 2) MVML_DST_FWD_SEP_F(2, 4);
+      else if (nj == 3) MVML_DST_FWD_SEP_F(3, 1);
+      else if (nj == 4) MVML_DST_FWD_SEP_F(4, 2);
+      else MVML_DST_FWD_SEP_F(8, 2);
+#undef MVML_DST_FWD_SEP_F
+    }
+#undef MVML_DST_FWD_SEP
+    int rc = check_launch("gat_agg_fwd_dst_kernel");
+    if (rc) return rc;
+    return launch_rows_amax(N, out_rows, out_amax, st);
+  }
   // The destination-wave kernel holds at most 4 float4 column slots per lane in mean mode (half-
   // waves over the heads for H >= 2: F <= 512; H = 1: F <= 1024) and 8 in the flatten modes
   // (H F <= 2048).  Wider head-mean shapes take the window / gather kernels below, whatever the
@@ -2388,15 +2486,25 @@ int launch_bwd(int64_t N, const int32_t* groups, int64_t G, const int32_t* rp, c
                const int32_t* orp, const int32_t* odst, const int32_t* oslot, const float* Y,
                int64_t ldy, const float* elr, const float* attn, const float* out,
                const float* g_out, int F, float slope, int mode, float* gpre, float* gY,
-               int64_t ldgy, int C, uint32_t* gy_amax, uint32_t* gy_rows, hipStream_t st) {
-  if (mode == 1 && option(MVML_OPT_MEAN_SRC) && F <= 1024)  // head-mean layer by source atom
+               int64_t ldgy, int C, uint32_t* gy_amax, uint32_t* gy_rows, hipStream_t st,
+               bool sep = false, float* gR = nullptr, int64_t ldgr = 0) {
+  // dR apart from gY's rows or not formed (mvml_gat_agg_bwd_res, sep): native in the source-atom
+  // kernels, the LDS molecule window and the per-atom pair.  Redirected here, before anything is
+  // launched: a head-mean layer always runs by source atom (mean_src = 0 as 1, at every F), and
+  // the big windows are off (their groups take the per-atom pair).
+  const int ramax = sep ? 0 : 1;
+  if (!sep) {  // the projection-row layout: dR in gY's columns past H F
+    gR = gY + H * F;
+    ldgr = ldgy;
+  }
+  if (mode == 1 && ((option(MVML_OPT_MEAN_SRC) && F <= 1024) || sep))  // head-mean layer by source atom
     return launch_mean_src<H>(N, rp, src, orp, odst, oslot, Y, ldy, elr, attn, g_out, F, slope, gpre, gY,
-                              ldgy, C, gy_amax, gy_rows, st);
+                              ldgy, C, gy_amax, gy_rows, st, gR, ldgr, ramax, sep);
   // flatten layer by source atom, one pass (round 5; the round-4 two-pass form — g_rst rows
   // written first, then gathered — computed the same bits and was measured slower: deleted)
   if (mode != 1 && option(MVML_OPT_FLAT_SRC))
     return launch_flat_src1<H>(N, rp, src, orp, odst, oslot, Y, ldy, elr, attn, out, g_out, F, slope, mode,
-                               gpre, gY, ldgy, C, gy_amax, gy_rows, st);
+                               gpre, gY, ldgy, C, gy_amax, gy_rows, st, gR, ldgr, ramax);
   if (option(MVML_OPT_BWD_ATOMWISE)) G = 0;  // tests: the per-atom pair over every atom
   if (F % 32 == 0 && G > 0) {  // molecule groups: one pass over Z / g_out / dZ per group
 #ifndef MVML_BWD_CW64
@@ -2409,6 +2517,14 @@ int launch_bwd(int64_t N, const int32_t* groups, int64_t G, const int32_t* rp, c
     gat_agg_bwd_lds_kernel<H, M, CW><<<(unsigned)G, 16 * CW, 0, st>>>(groups, G, rp, src, orp, odst, \
                                                                       oslot, Y, ldy, F, elr, attn, \
                                                                       out, g_out, slope, gY, ldgy, C, gy_amax, gy_rows)
+#define MVML_BWD_LDS_SEP(M)                                                                       \
+    gat_agg_bwd_lds_kernel<H, M, 32, 512, kWinL, kECap, false, true><<<(unsigned)G, 512, 0, st>>>(  \
+        groups, G, rp, src, orp, odst, oslot, Y, ldy, F, elr, attn, out, g_out, slope, gY, ldgy, C, \
+        gy_amax, gy_rows, gR, ldgr)
+    if (sep) {  // (flatten modes: a head-mean layer left above)
+      if (mode == 0) MVML_BWD_LDS_SEP(0);
+      else MVML_BWD_LDS_SEP(2);
+    } else
     if (MVML_BWD_CW64 && F % 64 == 0) {
       if (mode == 0) MVML_BWD_LDS(0, 64);
       else if (mode == 1) MVML_BWD_LDS(1, 64);
@@ -2419,12 +2535,13 @@ int launch_bwd(int64_t N, const int32_t* groups, int64_t G, const int32_t* rp, c
       else MVML_BWD_LDS(2, 32);
     }
 #undef MVML_BWD_LDS
+#undef MVML_BWD_LDS_SEP
     int rc = check_launch("gat_agg_bwd_lds_kernel");
     if (rc) return rc;
   } else {
     G = 0;  // no LDS groups: the per-atom pair covers every atom
   }
-  const int big = G > 0 && use_big_window(H, F);
+  const int big = G > 0 && !sep && use_big_window(H, F);
   if constexpr (H <= 4) {
     if (big) {
 #define MVML_BWD_BIG(M)                                                                             \
@@ -2442,12 +2559,12 @@ int launch_bwd(int64_t N, const int32_t* groups, int64_t G, const int32_t* rp, c
   const unsigned blocks = G > 0 ? (unsigned)G : (unsigned)ceil_div(N, kWavesPerBlock);
   gat_agg_bwd_dst_kernel<H, VPL><<<blocks, kWavesPerBlock * 64, 0, st>>>(
       N, groups, G, rp, src, Y, ldy, elr, attn, out, g_out, F, slope, mode, gpre, gY, ldgy, gY + C, ldgy, big,
-      gy_amax, gy_rows);
+      gy_amax, gy_rows, gR, ldgr, ramax);
   int rc = check_launch("gat_agg_bwd_dst_kernel");
   if (rc) return rc;
   gat_agg_bwd_src_kernel<H, VPL><<<blocks, kWavesPerBlock * 64, 0, st>>>(
       N, groups, G, rp, orp, odst, oslot, attn, gpre, out, g_out, F, mode, gY, ldgy, gY + C, ldgy, big,
-      gy_amax, gy_rows);
+      gy_amax, gy_rows, gR, ldgr);
   return check_launch("gat_agg_bwd_src_kernel");
 }
 
@@ -2464,13 +2581,14 @@ int launch_bwd(int64_t N, const int32_t* groups, int64_t G, const int32_t* rp, c
     default: break;                                \
   }
 
-int check_shapes(int H, int F, int mode, int64_t ldy, const void* Y, const char* who) {
+// need_cols: the columns a Y row must hold (default: the projection-row layout's [Z | R])
+int check_shapes(int H, int F, int mode, int64_t ldy, const void* Y, const char* who, int64_t need_cols = -1) {
   MVML_REQUIRE(H == 1 || H == 2 || H == 4 || H == 8, "%s: num_heads must be 1, 2, 4 or 8 (got %d)", who, H);
   MVML_REQUIRE(F > 0 && F % 4 == 0, "%s: out_feats must be a positive multiple of 4 (got %d)", who, F);
   MVML_REQUIRE(H * F <= 2048, "%s: H*F must be <= 2048 (got %d)", who, H * F);
   MVML_REQUIRE(ldy < (1 << 20), "%s: leading dimension too large", who);
   MVML_REQUIRE(mode >= 0 && mode <= 2, "%s: bad mode %d", who, mode);
-  const int64_t need = (int64_t)mvml_gat_proj_cols(H, F, mode == 1);
+  const int64_t need = need_cols >= 0 ? need_cols : (int64_t)mvml_gat_proj_cols(H, F, mode == 1);
   MVML_REQUIRE(ldy >= need && ldy % 4 == 0, "%s: leading dimension %lld < %lld or not a multiple of 4",
                who, (long long)ldy, (long long)need);
   MVML_REQUIRE(((uintptr_t)Y & 15) == 0, "%s: tensors must be 16-byte aligned", who);
@@ -2526,13 +2644,13 @@ int attn_grad_splits(int64_t N, int HF) {
   return (int)std::max<int64_t>(1, s);
 }
 
-// Wcat rows: [0,HF) fc.weight | [HF,HF+RW) res_fc.weight (RW = HF) or its head mean (RW = F);
-// columns Fin..ldw-1 are zero.
+// Wcat rows: [0,HF) fc.weight | [HF,HF+RW) res_fc.weight (RW = HF) or its head mean (RW = F) or
+// nothing (mean_res == MVML_RES_NONE: RW = 0, res_w unused); columns Fin..ldw-1 are zero.
 __global__ void fold_weights_kernel(const float* __restrict__ fc_w, const float* __restrict__ res_w,
                                     const float* __restrict__ attn_lr, int H, int F, int Fin,
                                     int ldw, int mean_res, float* __restrict__ Wcat) {
   const int HF = H * F;
-  const int RW = mean_res ? F : HF;
+  const int RW = mean_res == MVML_RES_NONE ? 0 : mean_res ? F : HF;
   const int64_t total = (int64_t)(HF + RW + (attn_lr ? 2 * H : 0)) * ldw;
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total;
        e += (int64_t)gridDim.x * blockDim.x) {
@@ -2569,7 +2687,7 @@ __global__ void unfold_w_kernel(const float* __restrict__ gW, const float* __res
                                 int H, int F, int Fin, int ldg, int mean_res,
                                 float* __restrict__ g_fc, float* __restrict__ g_res) {
   const int HF = H * F;
-  const int C = HF + (mean_res ? F : HF);
+  const int C = HF + (mean_res == MVML_RES_NONE ? 0 : mean_res ? F : HF);
   const int64_t total = (int64_t)HF * Fin;
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total;
        e += (int64_t)gridDim.x * blockDim.x) {
@@ -2581,9 +2699,49 @@ __global__ void unfold_w_kernel(const float* __restrict__ gW, const float* __res
       gf = fmaf(attn_lr[HF + row], gW[(int64_t)(C + H + h) * ldg + k], gf);
     }
     g_fc[e] = gf;
+    if (mean_res == MVML_RES_NONE) continue;  // no residual rows: g_res is not written
     g_res[e] = mean_res ? gW[(int64_t)(HF + row % F) * ldg + k] / (float)H
                         : gW[(int64_t)(HF + row) * ldg + k];
   }
+}
+
+// Head mean of flattened rows (the identity residual of a head-mean layer) and its backward:
+// one thread per (atom, f-float4); heads summed in order, then / H (torch mean(1)).
+__global__ void __launch_bounds__(256)
+head_mean_kernel(int64_t N, int H, int F, const float* __restrict__ X, int64_t ldx,
+                 float* __restrict__ R, int64_t ldr) {
+  const int nf4 = F / 4;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= N * nf4) return;
+  const int64_t n = i / nf4;
+  const int c = 4 * (int)(i % nf4);
+  float4 s = ld4(X + n * ldx + c);
+  for (int h = 1; h < H; ++h) s = add4(s, ld4(X + n * ldx + h * F + c));
+  const float hh = (float)H;
+  st4(R + n * ldr + c, make_float4(s.x / hh, s.y / hh, s.z / hh, s.w / hh));
+}
+
+__global__ void __launch_bounds__(256)
+head_mean_bwd_kernel(int64_t N, int H, int F, const float* __restrict__ gR, int64_t ldgr,
+                     float* __restrict__ gX, int64_t ldgx) {
+  const int nf4 = F / 4;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= N * nf4) return;
+  const int64_t n = i / nf4;
+  const int c = 4 * (int)(i % nf4);
+  const float4 g = ld4(gR + n * ldgr + c);
+  const float hh = (float)H;
+  const float4 v = make_float4(g.x / hh, g.y / hh, g.z / hh, g.w / hh);
+  for (int h = 0; h < H; ++h) st4(gX + n * ldgx + h * F + c, v);
+}
+
+int check_head_mean(int64_t N, int H, int F, const void* a, int64_t lda, int64_t wa, const void* b,
+                    int64_t ldb, int64_t wb, const char* who) {
+  MVML_REQUIRE(N >= 0 && H > 0 && F > 0 && F % 4 == 0, "%s: H > 0 and F a positive multiple of 4", who);
+  MVML_REQUIRE(lda >= wa && ldb >= wb && lda % 4 == 0 && ldb % 4 == 0 && ((uintptr_t)a & 15) == 0 &&
+                   ((uintptr_t)b & 15) == 0,
+               "%s: rows must be 16-byte aligned (pointers and row strides)", who);
+  return MVML_OK;
 }
 
 }  // namespace
@@ -2591,8 +2749,31 @@ __global__ void unfold_w_kernel(const float* __restrict__ gW, const float* __res
 
 using namespace mvml;
 
+extern "C" int mvml_head_mean_f32(int64_t N, int H, int F, const float* X, int64_t ldx, float* R,
+                                  int64_t ldr, void* stream) {
+  clear_error();
+  int rc = check_head_mean(N, H, F, X, ldx, (int64_t)H * F, R, ldr, F, "head_mean");
+  if (rc || N == 0) return rc;
+  head_mean_kernel<<<(unsigned)ceil_div(N * (F / 4), 256), 256, 0, as_stream(stream)>>>(N, H, F, X, ldx, R, ldr);
+  return check_launch("head_mean_kernel");
+}
+
+extern "C" int mvml_head_mean_bwd_f32(int64_t N, int H, int F, const float* gR, int64_t ldgr, float* gX,
+                                      int64_t ldgx, void* stream) {
+  clear_error();
+  int rc = check_head_mean(N, H, F, gR, ldgr, F, gX, ldgx, (int64_t)H * F, "head_mean_bwd");
+  if (rc || N == 0) return rc;
+  head_mean_bwd_kernel<<<(unsigned)ceil_div(N * (F / 4), 256), 256, 0, as_stream(stream)>>>(N, H, F, gR, ldgr, gX,
+                                                                                         ldgx);
+  return check_launch("head_mean_bwd_kernel");
+}
+
 extern "C" int mvml_gat_proj_cols(int H, int F, int mean_residual) {
   return H * F + (mean_residual ? F : H * F);
+}
+
+extern "C" int mvml_gat_proj_cols_res(int H, int F, int res) {
+  return res == MVML_RES_NONE ? H * F : mvml_gat_proj_cols(H, F, res == MVML_RES_MEAN);
 }
 
 extern "C" size_t mvml_gat_proj_fwd_workspace_size(int64_t num_nodes, int H, int F) {
@@ -2610,7 +2791,7 @@ extern "C" int mvml_gat_proj_fwd(int64_t num_nodes, const float* X, int64_t ldx,
   MVML_REQUIRE(H == 1 || H == 2 || H == 4 || H == 8, "gat_proj_fwd: num_heads must be 1, 2, 4 or 8 (got %d)", H);
   MVML_REQUIRE(F > 0 && F % 4 == 0, "gat_proj_fwd: out_feats must be a positive multiple of 4 (got %d)", F);
   MVML_REQUIRE(num_nodes >= 0 && K > 0 && ldx >= K && ldw >= K, "gat_proj_fwd: bad shape");
-  const int C = mvml_gat_proj_cols(H, F, mean_residual);
+  const int C = mvml_gat_proj_cols_res(H, F, mean_residual);  // (0 / 1, or MVML_RES_NONE)
   MVML_REQUIRE(ldy >= C, "gat_proj_fwd: ldy < %d", C);
   if (num_nodes == 0) return MVML_OK;
   if (!workspace || workspace_bytes < mvml_gat_proj_fwd_workspace_size(num_nodes, H, F)) {
@@ -2647,10 +2828,29 @@ extern "C" int mvml_gat_agg_fwd(int64_t num_nodes, const int32_t* node_groups, i
                                 float slope, int mode, float* out, float* attn, uint32_t* out_amax,
                                 uint32_t* out_row_amax, void* stream) {
   clear_error();
-  int rc = check_shapes(H, F, mode, ldy, Y, "gat_agg_fwd");
+  int rc = check_shapes(H, F, mode, ldy, Y, "gat_agg_fwd");  // Y rows hold [Z | R]
   if (rc) return rc;
+  return mvml_gat_agg_fwd_res(num_nodes, node_groups, num_groups, in_rowptr, in_src, Y, ldy, H, F, elr,
+                              Y + H * F, ldy, bias, slope, mode, out, attn, out_amax, out_row_amax, stream);
+}
+
+extern "C" int mvml_gat_agg_fwd_res(int64_t num_nodes, const int32_t* node_groups, int64_t num_groups,
+                                    const int32_t* in_rowptr, const int32_t* in_src, const float* Y,
+                                    int64_t ldy, int H, int F, const float* elr, const float* R,
+                                    int64_t ldr, const float* bias, float slope, int mode, float* out,
+                                    float* attn, uint32_t* out_amax, uint32_t* out_row_amax,
+                                    void* stream) {
+  clear_error();
+  int rc = check_shapes(H, F, mode, ldy, Y, "gat_agg_fwd", (int64_t)H * F);
+  if (rc) return rc;
+  const int RW = mode == 1 ? F : H * F;
   MVML_REQUIRE(((uintptr_t)out & 15) == 0 && ((uintptr_t)bias & 15) == 0,
                "gat_agg_fwd: out / bias must be 16-byte aligned");
+  MVML_REQUIRE(R == nullptr || (((uintptr_t)R & 15) == 0 && ldr % 4 == 0 && ldr >= RW && ldr < (1 << 20)),
+               "gat_agg_fwd: R must be 16-byte aligned with a row stride ldr >= %d that is a multiple of 4", RW);
+  // the projection-row layout with a bias runs the instances compiled for it; a residual apart
+  // from Y, no residual or no bias the SEP ones (launch_fwd)
+  const bool sep = !(R == Y + H * F && ldr == ldy && bias != nullptr);
   MVML_REQUIRE(attn != nullptr && elr != nullptr, "gat_agg_fwd: elr input and attn output are required");
   MVML_REQUIRE(num_groups == mvml_node_group_count(num_nodes) && (num_groups == 0 || node_groups),
                "gat_agg_fwd: node_groups must come from mvml_build_node_groups (%lld groups expected)",
@@ -2658,10 +2858,10 @@ extern "C" int mvml_gat_agg_fwd(int64_t num_nodes, const int32_t* node_groups, i
   if (num_nodes == 0) return MVML_OK;
   hipStream_t st = as_stream(stream);
   switch (H) {
-    case 1: return launch_fwd<1>(num_nodes, node_groups, num_groups, in_rowptr, in_src, Y, ldy, F, bias, slope, mode, out, attn, elr, out_amax, out_row_amax, st);
-    case 2: return launch_fwd<2>(num_nodes, node_groups, num_groups, in_rowptr, in_src, Y, ldy, F, bias, slope, mode, out, attn, elr, out_amax, out_row_amax, st);
-    case 4: return launch_fwd<4>(num_nodes, node_groups, num_groups, in_rowptr, in_src, Y, ldy, F, bias, slope, mode, out, attn, elr, out_amax, out_row_amax, st);
-    case 8: return launch_fwd<8>(num_nodes, node_groups, num_groups, in_rowptr, in_src, Y, ldy, F, bias, slope, mode, out, attn, elr, out_amax, out_row_amax, st);
+    case 1: return launch_fwd<1>(num_nodes, node_groups, num_groups, in_rowptr, in_src, Y, ldy, F, bias, slope, mode, out, attn, elr, out_amax, out_row_amax, st, sep, R, ldr);
+    case 2: return launch_fwd<2>(num_nodes, node_groups, num_groups, in_rowptr, in_src, Y, ldy, F, bias, slope, mode, out, attn, elr, out_amax, out_row_amax, st, sep, R, ldr);
+    case 4: return launch_fwd<4>(num_nodes, node_groups, num_groups, in_rowptr, in_src, Y, ldy, F, bias, slope, mode, out, attn, elr, out_amax, out_row_amax, st, sep, R, ldr);
+    case 8: return launch_fwd<8>(num_nodes, node_groups, num_groups, in_rowptr, in_src, Y, ldy, F, bias, slope, mode, out, attn, elr, out_amax, out_row_amax, st, sep, R, ldr);
   }
   set_error("gat_agg_fwd: unsupported shape");
   return MVML_ERR_INVALID;
@@ -2680,11 +2880,39 @@ extern "C" int mvml_gat_agg_bwd(int64_t num_nodes, const int32_t* node_groups, i
                                 int64_t ldgy, uint32_t* gy_amax, uint32_t* gy_row_amax, void* workspace,
                                 size_t workspace_bytes, void* stream) {
   clear_error();
-  int rc = check_shapes(H, F, mode, ldy, Y, "gat_agg_bwd");
+  int rc = check_shapes(H, F, mode, ldy, Y, "gat_agg_bwd");  // Y rows hold [Z | R]
   if (rc) return rc;
   const int C = mvml_gat_proj_cols(H, F, mode == 1);
   MVML_REQUIRE(ldgy >= C + 2 * H && ldgy % 4 == 0 && ldgy < (1 << 20),
                "gat_agg_bwd: ldgy must be >= proj_cols + 2H = %d and a multiple of 4", C + 2 * H);
+  return mvml_gat_agg_bwd_res(num_nodes, node_groups, num_groups, in_rowptr, in_src, out_rowptr, out_dst,
+                              out_inslot, Y, ldy, elr, attn, out, g_out, H, F, slope, mode, gY, ldgy, C,
+                              gY + H * F, ldgy, gy_amax, gy_row_amax, workspace, workspace_bytes, stream);
+}
+
+extern "C" int mvml_gat_agg_bwd_res(int64_t num_nodes, const int32_t* node_groups, int64_t num_groups,
+                                    const int32_t* in_rowptr, const int32_t* in_src,
+                                    const int32_t* out_rowptr, const int32_t* out_dst,
+                                    const int32_t* out_inslot, const float* Y, int64_t ldy,
+                                    const float* elr, const float* attn, const float* out,
+                                    const float* g_out, int H, int F, float slope, int mode, float* gY,
+                                    int64_t ldgy, int64_t elr_col, float* gR, int64_t ldgr,
+                                    uint32_t* gy_amax, uint32_t* gy_row_amax, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+  clear_error();
+  int rc = check_shapes(H, F, mode, ldy, Y, "gat_agg_bwd", (int64_t)H * F);
+  if (rc) return rc;
+  const int RW = mode == 1 ? F : H * F;
+  // dR inside gY's rows (the projection-row layout): the instances compiled for it, and dR
+  // counts in the maxima; apart from them or not formed: the SEP forms (launch_bwd)
+  const bool sep = !(gR == gY + H * F && ldgr == ldgy);
+  MVML_REQUIRE(elr_col >= (sep ? H * F : H * F + RW) && ldgy >= elr_col + 2 * H && ldgy % 4 == 0 &&
+                   ldgy < (1 << 20) && ((uintptr_t)gY & 15) == 0,
+               "gat_agg_bwd: gY must be 16-byte aligned, its [d el | d er] column %lld past dZ (and dR) and "
+               "ldgy >= that + 2H, a multiple of 4", (long long)elr_col);
+  MVML_REQUIRE(gR == nullptr || (((uintptr_t)gR & 15) == 0 && ldgr % 4 == 0 && ldgr >= RW && ldgr < (1 << 20)),
+               "gat_agg_bwd: gR must be 16-byte aligned with a row stride ldgr >= %d that is a multiple of 4", RW);
+  const int C = (int)elr_col;
   MVML_REQUIRE(attn != nullptr && elr != nullptr, "gat_agg_bwd: attn / elr from the forward are required");
   MVML_REQUIRE(mode != 0 || out != nullptr, "gat_agg_bwd: mode 0 needs the forward output");
   MVML_REQUIRE(num_groups == mvml_node_group_count(num_nodes) && (num_groups == 0 || node_groups),
@@ -2698,10 +2926,10 @@ extern "C" int mvml_gat_agg_bwd(int64_t num_nodes, const int32_t* node_groups, i
   float* gpre = static_cast<float*>(workspace);
   const int vpl = (int)ceil_div(H * F, 256);
   switch (H) {
-    case 1: { MVML_VPL_CASES(launch_bwd, 1, num_nodes, node_groups, num_groups, in_rowptr, in_src, out_rowptr, out_dst, out_inslot, Y, ldy, elr, attn, out, g_out, F, slope, mode, gpre, gY, ldgy, C, gy_amax, gy_row_amax, st) break; }
-    case 2: { MVML_VPL_CASES(launch_bwd, 2, num_nodes, node_groups, num_groups, in_rowptr, in_src, out_rowptr, out_dst, out_inslot, Y, ldy, elr, attn, out, g_out, F, slope, mode, gpre, gY, ldgy, C, gy_amax, gy_row_amax, st) break; }
-    case 4: { MVML_VPL_CASES(launch_bwd, 4, num_nodes, node_groups, num_groups, in_rowptr, in_src, out_rowptr, out_dst, out_inslot, Y, ldy, elr, attn, out, g_out, F, slope, mode, gpre, gY, ldgy, C, gy_amax, gy_row_amax, st) break; }
-    case 8: { MVML_VPL_CASES(launch_bwd, 8, num_nodes, node_groups, num_groups, in_rowptr, in_src, out_rowptr, out_dst, out_inslot, Y, ldy, elr, attn, out, g_out, F, slope, mode, gpre, gY, ldgy, C, gy_amax, gy_row_amax, st) break; }
+    case 1: { MVML_VPL_CASES(launch_bwd, 1, num_nodes, node_groups, num_groups, in_rowptr, in_src, out_rowptr, out_dst, out_inslot, Y, ldy, elr, attn, out, g_out, F, slope, mode, gpre, gY, ldgy, C, gy_amax, gy_row_amax, st, sep, gR, ldgr) break; }
+    case 2: { MVML_VPL_CASES(launch_bwd, 2, num_nodes, node_groups, num_groups, in_rowptr, in_src, out_rowptr, out_dst, out_inslot, Y, ldy, elr, attn, out, g_out, F, slope, mode, gpre, gY, ldgy, C, gy_amax, gy_row_amax, st, sep, gR, ldgr) break; }
+    case 4: { MVML_VPL_CASES(launch_bwd, 4, num_nodes, node_groups, num_groups, in_rowptr, in_src, out_rowptr, out_dst, out_inslot, Y, ldy, elr, attn, out, g_out, F, slope, mode, gpre, gY, ldgy, C, gy_amax, gy_row_amax, st, sep, gR, ldgr) break; }
+    case 8: { MVML_VPL_CASES(launch_bwd, 8, num_nodes, node_groups, num_groups, in_rowptr, in_src, out_rowptr, out_dst, out_inslot, Y, ldy, elr, attn, out, g_out, F, slope, mode, gpre, gY, ldgy, C, gy_amax, gy_row_amax, st, sep, gR, ldgr) break; }
   }
   set_error("gat_agg_bwd: unsupported shape");
   return MVML_ERR_INVALID;
@@ -2738,9 +2966,25 @@ extern "C" int mvml_gat_fold_weights(const float* fc_w, const float* res_fc_w, c
   clear_error();
   MVML_REQUIRE(H > 0 && F > 0 && Fin > 0 && ldw >= Fin, "gat_fold_weights: bad shape");
   hipStream_t st = as_stream(stream);
-  const int64_t total = (int64_t)(mvml_gat_proj_cols(H, F, mean_residual) + (attn_lr ? 2 * H : 0)) * ldw;
+  const int res = mean_residual ? MVML_RES_MEAN : MVML_RES_PROJ;
+  const int64_t total = (int64_t)(mvml_gat_proj_cols_res(H, F, res) + (attn_lr ? 2 * H : 0)) * ldw;
   const unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(total, 256), 8192);
-  fold_weights_kernel<<<blocks, 256, 0, st>>>(fc_w, res_fc_w, attn_lr, H, F, Fin, ldw, mean_residual, Wcat);
+  fold_weights_kernel<<<blocks, 256, 0, st>>>(fc_w, res_fc_w, attn_lr, H, F, Fin, ldw, res, Wcat);
+  return check_launch("fold_weights_kernel");
+}
+
+extern "C" int mvml_gat_fold_weights_res(const float* fc_w, const float* res_fc_w, const float* attn_lr,
+                                         int H, int F, int Fin, int ldw, int res, float* Wcat,
+                                         void* stream) {
+  clear_error();
+  MVML_REQUIRE(H > 0 && F > 0 && Fin > 0 && ldw >= Fin, "gat_fold_weights: bad shape");
+  MVML_REQUIRE(res == MVML_RES_PROJ || res == MVML_RES_MEAN || res == MVML_RES_NONE,
+               "gat_fold_weights: bad residual kind %d", res);
+  MVML_REQUIRE(res == MVML_RES_NONE || res_fc_w != nullptr, "gat_fold_weights: res_fc_w is required");
+  hipStream_t st = as_stream(stream);
+  const int64_t total = (int64_t)(mvml_gat_proj_cols_res(H, F, res) + (attn_lr ? 2 * H : 0)) * ldw;
+  const unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(total, 256), 8192);
+  fold_weights_kernel<<<blocks, 256, 0, st>>>(fc_w, res_fc_w, attn_lr, H, F, Fin, ldw, res, Wcat);
   return check_launch("fold_weights_kernel");
 }
 
@@ -2752,6 +2996,22 @@ extern "C" int mvml_gat_unfold_grads(const float* gWcat, const float* attn_lr, i
   hipStream_t st = as_stream(stream);
   const int64_t total = (int64_t)H * F * Fin;
   const unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(total, 256), 8192);
-  unfold_w_kernel<<<blocks, 256, 0, st>>>(gWcat, attn_lr, H, F, Fin, ldg, mean_residual, g_fc_w, g_res_fc_w);
+  unfold_w_kernel<<<blocks, 256, 0, st>>>(gWcat, attn_lr, H, F, Fin, ldg,
+                                          mean_residual ? MVML_RES_MEAN : MVML_RES_PROJ, g_fc_w, g_res_fc_w);
+  return check_launch("unfold_w_kernel");
+}
+
+extern "C" int mvml_gat_unfold_grads_res(const float* gWcat, const float* attn_lr, int H, int F,
+                                         int Fin, int ldg, int res, float* g_fc_w, float* g_res_fc_w,
+                                         void* stream) {
+  clear_error();
+  MVML_REQUIRE(H > 0 && F > 0 && Fin > 0 && ldg >= Fin, "gat_unfold_grads: bad shape");
+  MVML_REQUIRE(res == MVML_RES_PROJ || res == MVML_RES_MEAN || res == MVML_RES_NONE,
+               "gat_unfold_grads: bad residual kind %d", res);
+  MVML_REQUIRE(res == MVML_RES_NONE || g_res_fc_w != nullptr, "gat_unfold_grads: g_res_fc_w is required");
+  hipStream_t st = as_stream(stream);
+  const int64_t total = (int64_t)H * F * Fin;
+  const unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(total, 256), 8192);
+  unfold_w_kernel<<<blocks, 256, 0, st>>>(gWcat, attn_lr, H, F, Fin, ldg, res, g_fc_w, g_res_fc_w);
   return check_launch("unfold_w_kernel");
 }

@@ -15,6 +15,10 @@ from . import _lib
 from ._lib import call, ptr
 
 MODE_FLATTEN_ELU, MODE_MEAN, MODE_FLATTEN = 0, 1, 2
+# residual kinds of a GAT layer (dgl 0.9.1 GATConv.__init__): res_fc a bias-free Linear, the
+# identity (in_feats == H * F), or absent (residual=False); include/mvml_gat.h MVML_RES_*
+RES_PROJ, RES_IDENTITY, RES_NONE = "proj", "identity", "none"
+_MVML_RES_NONE = 2
 
 
 def _check_cuda_f32(t, name):
@@ -368,12 +372,28 @@ def _elu_link_of(X):
 class GATLayerFunction(torch.autograd.Function):
     """dgllife GATLayer(GATConv) forward/backward (model.py:79-81): projection GEMM (fc and
     res_fc as one MFMA GEMM) + fused el/er, edge-softmax, aggregation, residual, bias and
-    flatten/ELU or head-mean kernel."""
+    flatten/ELU or head-mean kernel.
+
+    res_kind: RES_PROJ (res_w = res_fc.weight: its rows ride in the projection GEMM),
+    RES_IDENTITY (in_feats == H F: the input itself, or its head mean in a head-mean layer, is
+    the residual; res_w None) or RES_NONE (res_w None).  bias may be None.  The identity / absent
+    kinds build the narrower Wcat = [fc ; A_l ; A_r], Y = [Z | el | er] and gY = [dZ | d el | d er]
+    and pass the residual to the aggregation as an input of its own (mvml_gat_agg_fwd_res /
+    mvml_gat_agg_bwd_res); their parameters that do not exist get None gradients."""
 
     @staticmethod
-    def forward(ctx, X, fc_w, res_w, attn_l, attn_r, bias, g, H, F, slope, mode, algo=None):
-        for t, n in ((X, "feat"), (fc_w, "fc.weight"), (res_w, "res_fc.weight")):
-            _check_cuda_f32(t, n)
+    def forward(ctx, X, fc_w, res_w, attn_l, attn_r, bias, g, H, F, slope, mode, algo=None,
+                res_kind=RES_PROJ):
+        if res_kind not in (RES_PROJ, RES_IDENTITY, RES_NONE):
+            raise ValueError(f"GATLayerFunction: unknown residual kind {res_kind!r}")
+        sep = res_kind != RES_PROJ  # no residual rows in Wcat / Y / gY
+        if (res_w is None) != sep:
+            raise ValueError("GATLayerFunction: res_fc.weight goes with the projected residual only")
+        if sep and (algo or GEMM_ALGO) == "bf16":
+            raise NotImplementedError("GATLayerFunction: the bf16 projection needs a projected residual")
+        for t, n in ((X, "feat"), (fc_w, "fc.weight"), (res_w, "res_fc.weight"), (bias, "bias")):
+            if t is not None:
+                _check_cuda_f32(t, n)
         # the batch's atom features may already sit in a zero-padded 16-B-row buffer
         Xpad = zero_padded(X, _round4(X.shape[1])) if X.dim() == 2 else None
         if Xpad is None:
@@ -381,8 +401,10 @@ class GATLayerFunction(torch.autograd.Function):
         N, Fin = X.shape
         dev = X.device
         HF = H * F
+        if res_kind == RES_IDENTITY and Fin != HF:
+            raise ValueError(f"GATLayerFunction: the identity residual needs in_feats == H F ({Fin} != {HF})")
         mean_res = int(mode == MODE_MEAN)
-        C = _lib.lib().mvml_gat_proj_cols(H, F, mean_res)
+        C = HF if sep else _lib.lib().mvml_gat_proj_cols(H, F, mean_res)
         st = _stream(dev)
         # Pad the feature dimension to a multiple of 4 (e.g. 74 atom features -> 76) so every
         # GEMM operand row is 16-B aligned and the LDS-DMA path applies; pad columns are zero.
@@ -405,8 +427,12 @@ class GATLayerFunction(torch.autograd.Function):
         # [fc.weight ; res_fc.weight (or its head mean) ; A_l ; A_r]: the projection GEMM uses
         # the first C rows, the backward all C + 2H (the el / er paths, see mvml_gat_agg_bwd)
         Wcat = torch.empty((C + 2 * H, Fp), dtype=torch.float32, device=dev)
-        call("mvml_gat_fold_weights", ptr(_c(fc_w)), ptr(_c(res_w)), ptr(attn_lr), H, F, Fin, Fp,
-             mean_res, ptr(Wcat), st)
+        if sep:
+            call("mvml_gat_fold_weights_res", ptr(_c(fc_w)), None, ptr(attn_lr), H, F, Fin, Fp,
+                 _MVML_RES_NONE, ptr(Wcat), st)
+        else:
+            call("mvml_gat_fold_weights", ptr(_c(fc_w)), ptr(_c(res_w)), ptr(attn_lr), H, F, Fin, Fp,
+                 mean_res, ptr(Wcat), st)
         L = _lib.lib()
         # split-fp16: |max| of X, Wcat (all C + 2H rows) and, in the backward, gY — each operand's
         # pass serves all of its products (projection, dL/dW, dL/dX)
@@ -439,9 +465,12 @@ class GATLayerFunction(torch.autograd.Function):
             # Wcat split once: the projection's tiles and the backward's dL/dX read the image
             wil = split_il4(Wcat, C + 2 * H, Fp, Fp, slot(amx, 1))
         # claim the previous layer's ELU link only where the fused data-gradient product will
-        # run (per-row scales and the interleaved weight image: see backward)
+        # run (per-row scales and the interleaved weight image: see backward).  An identity-
+        # residual layer never claims: its residual's share of dL/dX is added to the product
+        # (beta = 1), and the fused epilogue (mvml_gemm_f16x2_ex) has no accumulate, so ELU'
+        # would not see the whole sum
         if (link is not None and not link.claimed and Fp == Fin and amx is not None
-                and wil is not None):
+                and wil is not None and res_kind != RES_IDENTITY):
             link.claimed = True
             ctx.elu_claim = link
         bf16_elr = (algo or GEMM_ALGO) == "bf16" and PROJ_ELR_GEMM
@@ -471,7 +500,8 @@ class GATLayerFunction(torch.autograd.Function):
             elr = torch.empty((N, 2 * H), dtype=torch.float32, device=dev)
             wp, wn = _lib.ws_ptr_size(L.mvml_gat_proj_fwd_workspace_size(N, H, F), dev)
             _lib.call_tag[0] = {"flops": 2 * N * C * Fp}
-            call("mvml_gat_proj_fwd", N, ptr(Xp), Fp, Fp, ptr(Wcat), Fp, ptr(attn_lr), H, F, mean_res,
+            call("mvml_gat_proj_fwd", N, ptr(Xp), Fp, Fp, ptr(Wcat), Fp, ptr(attn_lr), H, F,
+                 _MVML_RES_NONE if sep else mean_res,
                  _GEMM_ENTRY[algo or GEMM_ALGO][1], ptr(Y), ldy, ptr(elr),
                  None if ax is None else slot(*ax), slot(amx, 1), None, 0, wp, wn, st)
         out_cols = F if mode == MODE_MEAN else HF
@@ -480,11 +510,28 @@ class GATLayerFunction(torch.autograd.Function):
         attn = torch.empty((E, H), dtype=torch.float32, device=dev)
         # per-row max |out| for the consumer's per-row split-fp16 GEMMs (next layer, Set2Set)
         orows = torch.empty(max(N, 1), dtype=torch.int32, device=dev) if (amx is not None and ROW_SCALES) else None
-        _lib.call_tag[0] = {"layer": f"H{H}xF{F}", "bytes": agg_fwd_bytes(N, E, H, F, out_cols, C - HF)}
+        # the residual rows: Y's columns past H F (projected), the input itself or its head mean
+        # (identity), or none
+        rw = out_cols
+        R, ldr = None, 0
+        if res_kind == RES_IDENTITY and mode == MODE_MEAN:
+            R, ldr = torch.empty((N, F), dtype=torch.float32, device=dev), F
+            call("mvml_head_mean_f32", N, H, F, ptr(Xp), Fp, ptr(R), ldr, st)
+        elif res_kind == RES_IDENTITY:
+            R, ldr = Xp, Fp
+        _lib.call_tag[0] = {"layer": f"H{H}xF{F}",
+                            "bytes": agg_fwd_bytes(N, E, H, F, out_cols, 0 if res_kind == RES_NONE else rw)}
         with _fwd_path(g, mode):
-            call("mvml_gat_agg_fwd", N, ptr(g.node_groups), g.num_node_groups, ptr(g.in_rowptr),
-                 ptr(g.in_src), ptr(Y), ldy, H, F, ptr(elr), ptr(_c(bias)), float(slope), int(mode),
-                 ptr(out), ptr(attn), slot(amx, 3), ptr(orows), st)
+            if not sep and bias is not None:
+                call("mvml_gat_agg_fwd", N, ptr(g.node_groups), g.num_node_groups, ptr(g.in_rowptr),
+                     ptr(g.in_src), ptr(Y), ldy, H, F, ptr(elr), ptr(_c(bias)), float(slope), int(mode),
+                     ptr(out), ptr(attn), slot(amx, 3), ptr(orows), st)
+            else:
+                rp = ctypes.c_void_p(Y.data_ptr() + 4 * HF) if not sep else ptr(R)
+                call("mvml_gat_agg_fwd_res", N, ptr(g.node_groups), g.num_node_groups, ptr(g.in_rowptr),
+                     ptr(g.in_src), ptr(Y), ldy, H, F, ptr(elr), rp, ldr if sep else ldy,
+                     ptr(_c(bias)) if bias is not None else None, float(slope), int(mode),
+                     ptr(out), ptr(attn), slot(amx, 3), ptr(orows), st)
         if amx is not None:  # max |out| for the consumer's split-fp16 GEMMs (next layer, Set2Set)
             fold_amax(out, amx, 3)
         if orows is not None:
@@ -503,6 +550,7 @@ class GATLayerFunction(torch.autograd.Function):
         ctx.Fin = Fin
         ctx.g, ctx.H, ctx.F, ctx.slope, ctx.mode, ctx.ldy = g, H, F, slope, mode, ldy
         ctx.algo = algo
+        ctx.res_kind, ctx.has_bias = res_kind, bias is not None
         ctx.amx = amx
         ctx.ax = ax
         ctx.wil = wil
@@ -530,7 +578,9 @@ class GATLayerFunction(torch.autograd.Function):
         HF = H * F
         mean_res = int(mode == MODE_MEAN)
         L = _lib.lib()
-        C = L.mvml_gat_proj_cols(H, F, mean_res)
+        res_kind, has_bias = ctx.res_kind, ctx.has_bias
+        sep = res_kind != RES_PROJ
+        C = HF if sep else L.mvml_gat_proj_cols(H, F, mean_res)
         CE = C + 2 * H  # + [d el | d er]
         ldg = _row_pitch(CE)
         st = _stream(dev)
@@ -547,11 +597,30 @@ class GATLayerFunction(torch.autograd.Function):
             gyr = torch.empty(max(N, 1), dtype=torch.int32, device=dev)
         _lib.call_tag[0] = {"layer": f"H{H}xF{F}",
                             "bytes": agg_bwd_bytes(N, g.num_edges(), H, F, g_out.shape[1], mode)}
+        # Identity / absent residual: dR leaves through gR (mvml_gat_agg_bwd_res).  A flatten
+        # layer's gR = g_rst is the identity residual's share of dL/dX — written straight into gX,
+        # which the data-gradient product below then accumulates onto (beta = 1) — and its column
+        # sums are the bias gradient (no residual but a bias: a scratch buffer; neither: not
+        # formed).  A head-mean layer's dR is g_out itself, so nothing is formed there.
+        gX = gR = None
+        ldgr = 0
+        if sep and mode != MODE_MEAN:
+            if res_kind == RES_IDENTITY and ctx.needs_input_grad[0]:
+                gX = torch.empty((N, Fin), dtype=torch.float32, device=dev)
+                gR, ldgr = gX, Fin
+            elif has_bias:
+                gR, ldgr = torch.empty((N, HF), dtype=torch.float32, device=dev), HF
         with (_lib.option("flat_src", 2) if flat_src else contextlib.nullcontext()):
-            call("mvml_gat_agg_bwd", N, ptr(g.node_groups), g.num_node_groups, ptr(g.in_rowptr),
-                 ptr(g.in_src), ptr(g.out_rowptr), ptr(g.out_dst), ptr(g.out_inslot), ptr(Y), ldy,
-                 ptr(elr), ptr(attn), ptr(out), ptr(g_out), H, F, float(ctx.slope), int(mode), ptr(gY),
-                 ldg, slot(ctx.amx, 2), ptr(gyr), wp, wn, st)
+            if sep:
+                call("mvml_gat_agg_bwd_res", N, ptr(g.node_groups), g.num_node_groups, ptr(g.in_rowptr),
+                     ptr(g.in_src), ptr(g.out_rowptr), ptr(g.out_dst), ptr(g.out_inslot), ptr(Y), ldy,
+                     ptr(elr), ptr(attn), ptr(out), ptr(g_out), H, F, float(ctx.slope), int(mode), ptr(gY),
+                     ldg, C, ptr(gR), ldgr, slot(ctx.amx, 2), ptr(gyr), wp, wn, st)
+            else:
+                call("mvml_gat_agg_bwd", N, ptr(g.node_groups), g.num_node_groups, ptr(g.in_rowptr),
+                     ptr(g.in_src), ptr(g.out_rowptr), ptr(g.out_dst), ptr(g.out_inslot), ptr(Y), ldy,
+                     ptr(elr), ptr(attn), ptr(out), ptr(g_out), H, F, float(ctx.slope), int(mode), ptr(gY),
+                     ldg, slot(ctx.amx, 2), ptr(gyr), wp, wn, st)
         amx = ctx.amx  # slot 2 = max |gY|, folded in by mvml_gat_agg_bwd's stores
         if DEBUG_CAPTURE is not None and amx is not None:
             DEBUG_CAPTURE.setdefault("gy_amax", []).append((gY[:, :CE].clone(), amx[2:3].clone()))
@@ -561,10 +630,11 @@ class GATLayerFunction(torch.autograd.Function):
         # sums of gY's residual columns (g_rst; mean: g_out / H for every head), formed with it
         # where the product's own reads can (mvml_gemm_f16x2_amax_colsum: layer 1)
         gW = torch.empty((CE, Fp), dtype=torch.float32, device=dev)
-        g_bias = torch.empty((HF,), dtype=torch.float32, device=dev)
+        g_bias = torch.empty((HF,), dtype=torch.float32, device=dev) if has_bias else None
         bias_done = False
-        if amx is not None and (ctx.algo or GEMM_ALGO) == "f16x2" and COLSUM_FUSED and \
-                L.mvml_gemm_colsum_fused(CE, Fp, N):
+        # (the fused column sums read gY's residual block: the projected layout with a bias only)
+        if amx is not None and (ctx.algo or GEMM_ALGO) == "f16x2" and COLSUM_FUSED and has_bias and \
+                not sep and L.mvml_gemm_colsum_fused(CE, Fp, N):
             sum_n = F if mean_res else HF
             _lib.call_tag[0] = {"flops": 2 * CE * Fp * N, "shape": (CE, Fp, N, 1, 1),
                                 "bytes": 4 * (CE * Fp + CE * N + Fp * N), "role": "gat_dw"}
@@ -576,9 +646,14 @@ class GATLayerFunction(torch.autograd.Function):
             gemm(gY, Xp, CE, Fp, N, 1, 1, ldg, Fp, gW, Fp, algo=ctx.algo,
                  amax=None if amx is None else (slot(amx, 2), slot(*ctx.ax)), role="gat_dw")
         g_fc = torch.empty((HF, Fin), dtype=torch.float32, device=dev)
-        g_res = torch.empty((HF, Fin), dtype=torch.float32, device=dev)
-        call("mvml_gat_unfold_grads", ptr(gW), ptr(attn_lr), H, F, Fin, Fp, mean_res, ptr(g_fc),
-             ptr(g_res), st)
+        g_res = None
+        if sep:
+            call("mvml_gat_unfold_grads_res", ptr(gW), ptr(attn_lr), H, F, Fin, Fp, _MVML_RES_NONE,
+                 ptr(g_fc), None, st)
+        else:
+            g_res = torch.empty((HF, Fin), dtype=torch.float32, device=dev)
+            call("mvml_gat_unfold_grads", ptr(gW), ptr(attn_lr), H, F, Fin, Fp, mean_res, ptr(g_fc),
+                 ptr(g_res), st)
         gelr = gY[:, C:CE]
         # dL/dattn_l[h, f] = sum_n d el[n, h] Z[n, h, f] = sum_k G_l[h, k] fc.weight[h F + f, k]
         # with G_l = [d el]^T X — rows C .. C+H of gW, already formed by the dW GEMM (and G_r
@@ -590,16 +665,25 @@ class GATLayerFunction(torch.autograd.Function):
         g_ar = g_alr[1].view_as(attn_r)
         if DEBUG_CAPTURE is not None:
             DEBUG_CAPTURE.update(elr=elr, gelr=gelr, attn=attn)
-        if mean_res:  # every head's bias sees g_out / H: one column sum, replicated over heads
-            if not bias_done:
+        if has_bias and mean_res:  # every head's bias sees g_out / H: one column sum, replicated over heads
+            if sep:  # (dR = g_out)
+                colsum(g_out, N, F, F, g_bias, alpha=1.0 / H)
+            elif not bias_done:
                 colsum(gY, N, F, ldg, g_bias, offset=HF, alpha=1.0 / H)
             if H > 1:
                 copy2d(g_bias.view(H, F)[1:], g_bias[:F].view(1, F).expand(H - 1, F))
-        elif not bias_done:
+        elif has_bias and sep:  # (before the product below accumulates onto gR where it is gX)
+            colsum(gR, N, HF, ldgr, g_bias)
+        elif has_bias and not bias_done:
             colsum(gY, N, HF, ldg, g_bias, offset=HF)
-        gX = None
         if ctx.needs_input_grad[0]:
-            gX = torch.empty((N, Fin), dtype=torch.float32, device=dev)
+            # the identity residual's share is in gX already (flatten: gR above; head mean:
+            # g_out / H spread over the heads) and the product accumulates onto it
+            beta = 1.0 if res_kind == RES_IDENTITY else 0.0
+            if gX is None:
+                gX = torch.empty((N, Fin), dtype=torch.float32, device=dev)
+                if beta:
+                    call("mvml_head_mean_bwd_f32", N, H, F, ptr(g_out), F, ptr(gX), Fin, st)
             link = ctx.elu_claim
             if link is not None and amx is not None and ROW_SCALES and ctx.wil is not None:
                 # the previous layer's ELU backward in this product's epilogue: gX leaves as its
@@ -612,11 +696,13 @@ class GATLayerFunction(torch.autograd.Function):
                 link.g_rst = gX
             elif amx is not None and ROW_SCALES:  # every atom's gradient row at its own scale
                 gemm(gY, Wcat, N, Fin, CE, 0, 1, ldg, Fp, gX, Fin, amax=(None, slot(amx, 1)),
-                     arows=gyr if gyr is not None else absmax_rows(gY, N, CE, ldg), bil4=ctx.wil)
+                     arows=gyr if gyr is not None else absmax_rows(gY, N, CE, ldg), bil4=ctx.wil, beta=beta)
             else:
                 gemm(gY, Wcat, N, Fin, CE, 0, 1, ldg, Fp, gX, Fin, algo=ctx.algo,
-                     amax=None if amx is None else (slot(amx, 2), slot(amx, 1)))
-        return gX, g_fc, g_res, g_al, g_ar, g_bias, None, None, None, None, None, None
+                     amax=None if amx is None else (slot(amx, 2), slot(amx, 1)), beta=beta)
+        else:
+            gX = None
+        return gX, g_fc, g_res, g_al, g_ar, g_bias, None, None, None, None, None, None, None
 
 
 # GAT layer weight + bias gradients from one read of gY where the product's plan allows

@@ -17,9 +17,12 @@ from .batching import BatchedMolGraph
 
 
 class GATConv(nn.Module):
-    """dgl.nn.pytorch.GATConv (0.9.1) parameters for the configuration dgllife uses here:
-    residual=True (res_fc is a bias-free Linear when in_feats != heads*out_feats), explicit
-    bias, feat/attn dropout 0.  forward() returns rst (N, H, F) like DGL (activation None)."""
+    """dgl.nn.pytorch.GATConv (0.9.1) parameters, with feat/attn dropout 0.  The residual kind
+    follows DGL's rule: residual=True makes res_fc a bias-free Linear when in_feats !=
+    heads*out_feats and nn.Identity() when they are equal (rst += feat.view(N, H, F)); residual=
+    False registers res_fc as a None buffer; bias=False registers bias as one.  So the state_dict
+    has res_fc.weight only for a projecting residual and bias only with bias=True, as DGL's.
+    forward() returns rst (N, H, F) like DGL (activation None)."""
 
     def __init__(self, in_feats, out_feats, num_heads, feat_drop=0.0, attn_drop=0.0,
                  negative_slope=0.2, residual=False, activation=None,
@@ -27,10 +30,6 @@ class GATConv(nn.Module):
         super().__init__()
         if feat_drop or attn_drop:
             raise NotImplementedError("GATConv: feat_drop/attn_drop > 0 are not on the fused path")
-        if not residual or not bias or in_feats == out_feats * num_heads:
-            raise NotImplementedError(
-                "GATConv: only residual=True with a projecting res_fc and bias=True (the "
-                "dgllife GAT defaults used by model.py:81) are implemented")
         # the aggregation kernels' range (csrc/gat_agg.hip check_shapes): refuse here, not in forward
         if num_heads not in (1, 2, 4, 8) or out_feats <= 0 or out_feats % 4 or num_heads * out_feats > 2048:
             raise ValueError(
@@ -45,8 +44,19 @@ class GATConv(nn.Module):
         self.fc = nn.Linear(in_feats, out_feats * num_heads, bias=False)
         self.attn_l = nn.Parameter(torch.empty(1, num_heads, out_feats))
         self.attn_r = nn.Parameter(torch.empty(1, num_heads, out_feats))
-        self.bias = nn.Parameter(torch.empty(num_heads * out_feats))
-        self.res_fc = nn.Linear(in_feats, num_heads * out_feats, bias=False)
+        if bias:
+            self.bias = nn.Parameter(torch.empty(num_heads * out_feats))
+        else:
+            self.register_buffer("bias", None)
+        if not residual:
+            self.res_kind = Fn.RES_NONE
+            self.register_buffer("res_fc", None)
+        elif in_feats == num_heads * out_feats:
+            self.res_kind = Fn.RES_IDENTITY
+            self.res_fc = nn.Identity()
+        else:
+            self.res_kind = Fn.RES_PROJ
+            self.res_fc = nn.Linear(in_feats, num_heads * out_feats, bias=False)
         # GEMM operand precision of fc / res_fc (forward and both backward products): None =
         # fp32-accurate (the reference's fp32), torch.bfloat16 = bf16 operands with fp32
         # accumulation (BASELINE config 4, accuracy bar 2e-2).  Parameters stay fp32.
@@ -58,9 +68,10 @@ class GATConv(nn.Module):
         """Accept both DGL GATConv parameter layouts.  dgl 0.9.1 (README.md pins) keeps an
         explicit ``bias`` and a bias-free ``res_fc``; later DGL releases fold the bias into the
         residual Linear (``res_fc.bias``, no ``bias``) when ``res_fc`` projects.  The arithmetic
-        is the same (res_fc(x) + b), so the folded form loads into ``bias`` here."""
+        is the same (res_fc(x) + b), so the folded form loads into ``bias`` here (a projecting
+        res_fc with a bias only: the other kinds have no res_fc keys at all)."""
         rb, b = prefix + "res_fc.bias", prefix + "bias"
-        if rb in state_dict and b not in state_dict:
+        if self.res_kind == Fn.RES_PROJ and self.bias is not None and rb in state_dict and b not in state_dict:
             state_dict[b] = state_dict.pop(rb)
         super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys,
                                       unexpected_keys, error_msgs)
@@ -70,8 +81,10 @@ class GATConv(nn.Module):
         nn.init.xavier_normal_(self.fc.weight, gain=gain)
         nn.init.xavier_normal_(self.attn_l, gain=gain)
         nn.init.xavier_normal_(self.attn_r, gain=gain)
-        nn.init.constant_(self.bias, 0)
-        nn.init.xavier_normal_(self.res_fc.weight, gain=gain)
+        if self.bias is not None:
+            nn.init.constant_(self.bias, 0)
+        if isinstance(self.res_fc, nn.Linear):
+            nn.init.xavier_normal_(self.res_fc.weight, gain=gain)
 
     def _check_graph(self, graph):
         if not isinstance(graph, BatchedMolGraph):
@@ -87,10 +100,12 @@ class GATConv(nn.Module):
 
     def fused(self, graph, feat, mode):
         self._check_graph(graph)
-        return Fn.GATLayerFunction.apply(feat, self.fc.weight, self.res_fc.weight, self.attn_l,
+        res_w = self.res_fc.weight if self.res_kind == Fn.RES_PROJ else None
+        return Fn.GATLayerFunction.apply(feat, self.fc.weight, res_w, self.attn_l,
                                          self.attn_r, self.bias, graph, self._num_heads,
                                          self._out_feats, self.negative_slope, mode,
-                                         "bf16" if self.proj_dtype == torch.bfloat16 else None)
+                                         "bf16" if self.proj_dtype == torch.bfloat16 else None,
+                                         self.res_kind)
 
     def forward(self, graph, feat):
         rst = self.fused(graph, feat, Fn.MODE_FLATTEN).view(-1, self._num_heads, self._out_feats)
@@ -126,7 +141,10 @@ class GATLayer(nn.Module):
 
 class GAT(nn.Module):
     """dgllife.model.gnn.gat.GAT (0.3.0) with its defaults: 4 heads per layer, alpha 0.2,
-    residual, 'flatten' + ELU for all but the last layer, 'mean' + no activation last."""
+    residual, 'flatten' + ELU for all but the last layer, 'mean' + no activation last.
+    ``residuals`` / ``biases`` are passed through per layer; a layer whose input width equals
+    heads * hidden gets DGL's identity residual (e.g. every layer after the first of
+    hidden_feats = [64, 64])."""
 
     def __init__(self, in_feats, hidden_feats=None, num_heads=None, feat_drops=None,
                  attn_drops=None, alphas=None, residuals=None, agg_modes=None, activations=None,
@@ -255,6 +273,11 @@ class GNNModule(nn.Module):
         (bf16 operands on MFMA, fp32 accumulate — BASELINE config 4)."""
         if dtype not in (None, torch.float32, torch.bfloat16):
             raise ValueError("proj_dtype must be None, torch.float32 or torch.bfloat16")
+        if dtype == torch.bfloat16 and any(layer.gat_conv.res_kind != Fn.RES_PROJ
+                                           for layer in self.conv.gnn_layers):
+            raise NotImplementedError(
+                "GNNModule: the bf16 projection is implemented for projected residuals only (a layer "
+                "here has an identity or no residual, which is exact and not rounded through Wcat)")
         for layer in self.conv.gnn_layers:
             layer.gat_conv.proj_dtype = None if dtype == torch.float32 else dtype
 
