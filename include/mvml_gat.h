@@ -585,6 +585,39 @@ int mvml_set2set_gx(int64_t num_nodes, int D, int T, const int32_t* node_graph,
                     const float* g_qstars, int64_t ldgq, int64_t g_qstar_stride,
                     const float* alphas, const float* g_es, float* gX, void* stream);
 
+/* Weighted-sum-and-max readout (dgllife 0.3.0 WeightedSumAndMax = WeightAndSum | max_nodes; a
+ * second readout beside Set2Set, same output width 2 D).  One wavefront per molecule reads its
+ * atoms' rows once, in atom order.  For molecule g with atoms n in [node_offsets[g],
+ * node_offsets[g + 1]), gate weight W [D] and bias [1] (atom_weighting = Linear(D, 1) + Sigmoid):
+ *   gate[n]       = sigmoid(<W, x_n> + bias[0])                       [N], saved for backward
+ *   out[g][0:D]   = sum_n gate[n] x_n
+ *   out[g][D:2D]  = max_n x_n (per column)
+ *   argmax[g][c]  = the global atom index n that owns column c's max  int32 [B][lda]
+ * Ties: the LOWEST atom index attaining the maximum owns the column (a strict > walking the atoms
+ * in order), so on given fp32 inputs argmax is a fixed function of X.  A molecule without atoms
+ * gets sum = 0, max = 0 and argmax = -1, and takes no gradient.  X [N][ldx], out [B][ldo];
+ * D: a positive multiple of 4, <= 1024; every row pitch a multiple of 4 (ldx, lda >= D, ldo >=
+ * 2 D); N (atoms) <= 2^31 - 1.  B == 0 or N == 0: returns MVML_OK without a launch and writes
+ * nothing. */
+int mvml_wsum_max_fwd(int64_t B, int64_t N, int D, const int64_t* node_offsets, const float* X,
+                      int64_t ldx, const float* W, const float* bias, float* out, int64_t ldo,
+                      float* gate, int32_t* argmax, int64_t lda, void* stream);
+/* Backward of the readout, one pass (each atom row read once, each gX row written once).  With
+ * g_s = g_out[g][0:D], g_m = g_out[g][D:2D] (g_out [B][ldgo]), t_n = <g_s, x_n> and
+ * c_n = gate[n] (1 - gate[n]) t_n:
+ *   gX[n] = gate[n] g_s + c_n W + [argmax[g][c] == n] g_m[c]          [N][ldgx]
+ *   part  = per-workgroup partial sums, [mvml_wsum_max_bwd_part_rows(B)][ldp], ldp >= D + 4 (a
+ *           multiple of 4): columns [0, D) hold sum_n c_n x_n, column D holds sum_n c_n over the
+ *           workgroup's four molecules (added in a fixed order).  dL/dW = column sums of
+ *           part[:, 0:D], dL/dbias = column sum of part[:, D] (mvml_colsum_f32).
+ * No atomics: every output is bitwise reproducible.  Same D range, pitches and B == 0 / N == 0
+ * rule as the forward. */
+int64_t mvml_wsum_max_bwd_part_rows(int64_t B);
+int mvml_wsum_max_bwd(int64_t B, int64_t N, int D, const int64_t* node_offsets, const float* X,
+                      int64_t ldx, const float* W, const float* gate, const int32_t* argmax,
+                      int64_t lda, const float* g_out, int64_t ldgo, float* gX, int64_t ldgx,
+                      float* part, int64_t ldp, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * GraphNorm (torch_geometric 2.2.0, eps, batch=None at model.py:93): independent statistics
  * per normalisation group (group_offsets int64[G+1], in rows); the reference's group is its

@@ -82,8 +82,8 @@ def copy2d(dst, src):
 # Diagnostics hook (tools/diag_golden.py, the parity tests' kink-branch capture): when a dict,
 # GATLayerFunction.forward appends each layer's el/er to DEBUG_CAPTURE["elr_fwd"] and the
 # backward stores its saved el/er, attention and el/er gradients; LinearReLUFunction appends its
-# post-ReLU output to ["relu_out"] and the fusion its Conv2d+ReLU output to ["conv_out"].  None
-# in normal use.
+# post-ReLU output to ["relu_out"], the fusion its Conv2d+ReLU output to ["conv_out"] and
+# WeightedSumAndMaxFunction its forward's argmax to ["readout_argmax"].  None in normal use.
 DEBUG_CAPTURE = None
 
 
@@ -924,6 +924,69 @@ class Set2SetFunction(torch.autograd.Function):
         for l in range(Lr):
             grads += [gW_ih[l], gW_hh[l], gb[l], copy2d(torch.empty_like(gb[l]), gb[l])]
         return (gX, None, None, None, *grads)
+
+
+def _rows_f32(t):
+    """t as a float32 matrix the row-pitched kernels can read in place (unit column stride, a row
+    stride and a base address that keep float4 accesses aligned), else a contiguous copy."""
+    if t.dim() == 2 and t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.stride(0) >= t.shape[1] \
+            and t.data_ptr() % 16 == 0:
+        return t
+    return t.contiguous()
+
+
+class WeightedSumAndMaxFunction(torch.autograd.Function):
+    """dgllife WeightedSumAndMax.forward: [sum_nodes(sigmoid(Linear(x)) * x) | max_nodes(x)] in one
+    pass over the atom rows (mvml_wsum_max_fwd), and its backward in one more (mvml_wsum_max_bwd
+    plus the column sums of its partials for the gate's weight and bias).  weight [1, D], bias [1]
+    (atom_weighting[0] of WeightAndSum); returns (B, 2 D)."""
+
+    @staticmethod
+    def forward(ctx, X, weight, bias, g):
+        _check_cuda_f32(X, "feats")
+        X = _rows_f32(X)
+        N, D = X.shape
+        B = g.batch_size
+        dev = X.device
+        weight, bias = _c(weight), _c(bias)
+        out = torch.empty((B, 2 * D), dtype=torch.float32, device=dev)
+        gate = torch.empty(N, dtype=torch.float32, device=dev)
+        argmax = torch.empty((B, D), dtype=torch.int32, device=dev)
+        if B == 0 or N == 0:  # no launch: every molecule is empty (sum 0, max 0, argmax -1)
+            if B:
+                zero_(out)
+                argmax.fill_(-1)
+        else:
+            call("mvml_wsum_max_fwd", B, N, D, ptr(g.node_offsets), ptr(X), X.stride(0), ptr(weight),
+                 ptr(bias), ptr(out), 2 * D, ptr(gate), ptr(argmax), D, _stream(dev))
+        if DEBUG_CAPTURE is not None:  # the atoms the product took at the max's kinks (ties)
+            DEBUG_CAPTURE.setdefault("readout_argmax", []).append(argmax.detach().clone())
+        ctx.save_for_backward(X, weight, gate, argmax)
+        ctx.g = g
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        X, weight, gate, argmax = ctx.saved_tensors
+        g = ctx.g
+        N, D = X.shape
+        B = g.batch_size
+        dev = X.device
+        g_out = _rows_f32(g_out)
+        gX = torch.empty((N, D), dtype=torch.float32, device=dev)
+        gW = torch.empty((1, D), dtype=torch.float32, device=dev)
+        gb = torch.empty(1, dtype=torch.float32, device=dev)
+        if B == 0 or N == 0:
+            return gX, zero_(gW), zero_(gb), None
+        R = _lib.lib().mvml_wsum_max_bwd_part_rows(B)
+        ldp = D + 4
+        part = torch.empty((R, ldp), dtype=torch.float32, device=dev)
+        call("mvml_wsum_max_bwd", B, N, D, ptr(g.node_offsets), ptr(X), X.stride(0), ptr(weight),
+             ptr(gate), ptr(argmax), D, ptr(g_out), g_out.stride(0), ptr(gX), D, ptr(part), ldp,
+             _stream(dev))
+        colsum(part, R, D, ldp, gW)
+        colsum(part, R, 1, ldp, gb, offset=D)
+        return gX, gW, gb, None
 
 
 class GraphNormFunction(torch.autograd.Function):

@@ -3,6 +3,7 @@
 Drop-in replacements, on the MI355X HIP path, for
   * dgl 0.9.1 ``GATConv`` and dgllife 0.3.0 ``GATLayer`` / ``GAT`` (model.py:6, 81, 91),
   * dgl 0.9.1 ``Set2Set`` (model.py:7, 82-84, 92),
+  * dgllife 0.3.0 ``WeightAndSum`` / ``WeightedSumAndMax`` (a second readout; not in model.py),
   * torch_geometric 2.2.0 ``GraphNorm`` (model.py:10, 85, 93),
   * ``GNNModule`` itself (model.py:77-95).
 Parameter names/shapes/registration order follow the reference so a ``net_i.pkl``
@@ -218,6 +219,43 @@ class Set2Set(nn.Module):
         return Fn.Set2SetFunction.apply(feat, graph, self.n_iters, self.n_layers, *self.lstm_params())
 
 
+class WeightAndSum(nn.Module):
+    """dgllife.model.readout.WeightAndSum (0.3.0): atom_weighting = Linear(in_feats, 1) + Sigmoid,
+    forward(bg, feats) = sum_nodes(atom_weighting(feats) * feats), (B, in_feats).  The module is a
+    parameter container (keys atom_weighting.0.weight [1, D], atom_weighting.0.bias [1]); the
+    gate, the sum and their backward run in the readout kernels (csrc/readout.hip)."""
+
+    def __init__(self, in_feats):
+        super().__init__()
+        # the readout kernels' range (csrc/readout.hip check_d): refuse here, not in forward
+        if in_feats <= 0 or in_feats % 4 or in_feats > 1024:
+            raise ValueError(f"WeightAndSum: in_feats must be a positive multiple of 4 <= 1024 (got {in_feats})")
+        self.in_feats = in_feats
+        self.atom_weighting = nn.Sequential(nn.Linear(in_feats, 1), nn.Sigmoid())
+
+    def _both(self, bg, feats):
+        lin = self.atom_weighting[0]
+        return Fn.WeightedSumAndMaxFunction.apply(feats, lin.weight, lin.bias, bg)
+
+    def forward(self, bg, feats):
+        # the sum half of the fused pass (the max half costs no extra read of the rows)
+        return self._both(bg, feats)[:, :self.in_feats]
+
+
+class WeightedSumAndMax(nn.Module):
+    """dgllife.model.readout.WeightedSumAndMax (0.3.0), GATPredictor's readout:
+    forward(bg, feats) = cat([weight_and_sum(bg, feats), max_nodes(feats)], 1), (B, 2 in_feats)
+    — Set2Set's output width.  A column's max gradient goes to the lowest-index atom attaining
+    it; a molecule without atoms reads 0 in both halves (parity with dgllife/dgl is unpinned)."""
+
+    def __init__(self, in_feats):
+        super().__init__()
+        self.weight_and_sum = WeightAndSum(in_feats)
+
+    def forward(self, bg, feats):
+        return self.weight_and_sum._both(bg, feats)
+
+
 class GraphNorm(nn.Module):
     """torch_geometric.nn.GraphNorm (2.2.0).  forward(x, batch=None) normalises over the whole
     input like the reference (model.py:93); ``group_offsets`` (int64[G+1], rows) evaluates many
@@ -252,17 +290,29 @@ class GNNModule(nn.Module):
     forward(graphs, atom_feats): graphs is a BatchedMolGraph already on the GPU, atom_feats
     (N, in_feats) float32 on the same device; returns (B, hidden_feats[-1]).  GraphNorm
     statistics are per ``graphs.group_offsets`` (default: the whole batch, as model.py:93).
+
+    ``readout``: "set2set" (the reference's, the default) or "weighted_sum_max" (dgllife's
+    WeightedSumAndMax, the same 2 * hidden_feats[-1] output width; num_step_set2set and
+    num_layer_set2set are then unused and the state_dict has readout.weight_and_sum.* instead of
+    readout.lstm.*).
     """
 
+    READOUTS = ("set2set", "weighted_sum_max")
+
     def __init__(self, in_feats=64, hidden_feats=None, dropout=0.2, num_step_set2set=6,
-                 num_layer_set2set=3, proj_dtype=None):
+                 num_layer_set2set=3, proj_dtype=None, readout="set2set"):
         super().__init__()
         if hidden_feats is None:
             raise TypeError("GNNModule needs hidden_feats (the reference indexes hidden_feats[-1])")
+        if readout not in self.READOUTS:
+            raise ValueError(f"GNNModule: readout must be one of {self.READOUTS} (got {readout!r})")
         hidden_feats = list(hidden_feats)
         self.conv = GAT(in_feats, hidden_feats)
-        self.readout = Set2Set(input_dim=hidden_feats[-1], n_iters=num_step_set2set,
-                               n_layers=num_layer_set2set)
+        if readout == "set2set":
+            self.readout = Set2Set(input_dim=hidden_feats[-1], n_iters=num_step_set2set,
+                                   n_layers=num_layer_set2set)
+        else:
+            self.readout = WeightedSumAndMax(hidden_feats[-1])
         self.norm = GraphNorm(hidden_feats[-1] * 2)
         self.fc = nn.Sequential(nn.Linear(hidden_feats[-1] * 2, hidden_feats[-1]), nn.ReLU(),
                                 nn.Dropout(p=dropout))

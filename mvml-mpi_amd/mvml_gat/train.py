@@ -181,6 +181,12 @@ def fit(model, optimizer, scheduler, stopper, train_loader, val_loader, epochs, 
 
 
 # ------------------------------------------------------------------------------------------ CLI
+class _Args(argparse.Namespace):
+    """parse()'s namespace: defaults of the options that are not in config.py."""
+    READOUTS = ("set2set", "weighted_sum_max")
+    graph_readout = "set2set"
+
+
 def parse(argv=None):
     """config.py's flags and defaults, plus --data / --index (the dataset CSV and the split
     file, data_index.txt: three Python lists of row indices, are not shipped)."""
@@ -207,7 +213,12 @@ def parse(argv=None):
     p.add_argument("--lr", type=float, default=1e-3, help="learning rate")
     p.add_argument("--weight_decay", type=float, default=1e-4)
     p.add_argument("--batch_size", type=int, default=64)
-    return p.parse_args(argv)
+    # not one of config.py's flags: the default lives on the namespace's class, so the parsed
+    # attributes of a reference command line are config.py's and nothing else (vars(args))
+    p.add_argument("--graph_readout", type=str, default=argparse.SUPPRESS, choices=list(_Args.READOUTS),
+                   help="the graph view's readout: set2set (the reference's, the default) or "
+                        "weighted_sum_max (dgllife's WeightedSumAndMax: one pass over the atom rows, no LSTM)")
+    return p.parse_args(argv, namespace=_Args())
 
 
 def read_index(path):
@@ -243,7 +254,7 @@ def main(args, log=print):
         model = MVP(num_classes=args.class_num, in_feats=dataset.feat_size, hidden_feats=args.hidden_feats,
                     rnn_embed_dim=args.rnn_embed_dim, blstm_dim=args.rnn_hidden_dim,
                     blstm_layers=args.rnn_layers, fp_2_dim=args.fp_dim, dropout=args.p,
-                    num_heads=args.head, device=device).to(device)
+                    num_heads=args.head, device=device, graph_readout=args.graph_readout).to(device)
         optimizer = FlatAdam(model.parameters(), lr=args.lr, weight_decay=args.weight_decay)
         scheduler = torch.optim.lr_scheduler.ExponentialLR(optimizer, gamma=0.95)
         stopper = EarlyStopping(mode='higher', filename=os.path.join(args.output, f'net_{iteration}.pkl'),
