@@ -512,6 +512,53 @@ int mvml_gat_layer_bwd(int64_t num_nodes, const int32_t* node_groups, int64_t nu
                        size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * GATv2 attention + aggregation (dgl 0.9.1 GATv2Conv.forward after fc_src / fc_dst / res_fc, plus
+ * dgllife 0.3.0 GATv2Layer's flatten / head mean; restated, parity with dgl unpinned), over the
+ * edges e = (u -> v) of the in-CSR:
+ *   p_e = ZL[u] + ZR[v];  s_e[h] = sum_f attn_vec[h, f] * LeakyReLU(p_e[h, f], slope)
+ *   a = edge_softmax by destination (max-subtracted, summed in ascending in-CSR slot order)
+ *   rst[v] = sum_e a_e * ZL[u] (+ R[v]);  out = ELU(rst.flatten) | mean_h(rst) | rst.flatten
+ * ZL / ZR: [N, H*F] with row strides ldzl / ldzr (ZR == ZL allowed: share_weights); attn_vec
+ * [H*F]; R, ldr exactly as in mvml_gat_agg_fwd_res (H*F wide in modes 0 / 2, F wide = the caller's
+ * head mean in mode 1, NULL: no residual); out [N, H*F] (modes 0, 2) or [N, F] (mode 1), dense;
+ * attn [E, H] receives the edge softmax in in-CSR slot order (the backward's input).  There is no
+ * bias argument: GATv2Conv's biases live in its Linears.  A destination without in-edges gets
+ * rst = R (0 without one).  Any in-degree: scores past 64 in-edges pass through attn itself.
+ * Shapes: H in {1, 2, 4, 8}, F a positive multiple of 4, H*F <= 2048, every row 16-byte aligned
+ * (strides multiples of 4); anything else returns MVML_ERR_INVALID before any launch and writes
+ * nothing.  N == 0 returns MVML_OK without a launch.  No float atomics: bitwise repeatable.
+ * ------------------------------------------------------------------------------------- */
+int mvml_gatv2_agg_fwd(int64_t num_nodes, const int32_t* in_rowptr, const int32_t* in_src,
+                       const float* ZL, int64_t ldzl, const float* ZR, int64_t ldzr, int H, int F,
+                       const float* attn_vec, const float* R, int64_t ldr, float slope, int mode,
+                       float* out, float* attn, void* stream);
+/* Backward of mvml_gatv2_agg_fwd from g_out = dL/d out (`out` is read in mode 0 only, for ELU'):
+ *   g_a[e, h] = <ZL[u, h], g_rst[v, h]>;  g_s = a * (g_a - sum_in(v) a g_a)
+ *   d_e[h, f] = g_s[e, h] * attn_vec[h, f] * (p_e[h, f] > 0 ? 1 : slope)
+ *   gZL[u] = sum_out(u) (a_e g_rst[v] + d_e)   (a gather over the out-CSR by source atom)
+ *   gZR[v] = sum_in(v) d_e                     (0 for a destination without in-edges)
+ *   gR[v]  = g_rst[v] (modes 0 / 2, H*F wide) or g_out[v] (mode 1, F wide); gR == NULL: not formed
+ *   g_attn_vec[h, f] = sum_e g_s[e, h] * LeakyReLU(p_e[h, f])
+ * gZL and gZR are two outputs that never alias (they may be column blocks of one row buffer).
+ * g_attn_vec is a two-stage sum: mvml_gatv2_partial_rows(N) per-wave partial rows (a function of
+ * N alone, at most 32768), each over a contiguous atom range in atom order, then mvml_colsum_f32.
+ * workspace: mvml_gatv2_agg_bwd_workspace_size bytes ([E, H] g_s, the partial rows, the column
+ * sum's scratch).  Shapes and the MVML_ERR_INVALID contract as the forward. */
+int64_t mvml_gatv2_partial_rows(int64_t num_nodes);
+size_t mvml_gatv2_agg_bwd_workspace_size(int64_t num_nodes, int64_t num_edges, int H, int F);
+int mvml_gatv2_agg_bwd(int64_t num_nodes, const int32_t* in_rowptr, const int32_t* in_src,
+                       const int32_t* out_rowptr, const int32_t* out_dst, const int32_t* out_inslot,
+                       int64_t num_edges, const float* ZL, int64_t ldzl, const float* ZR,
+                       int64_t ldzr, int H, int F, const float* attn_vec, const float* attn,
+                       const float* out, const float* g_out, float slope, int mode, float* gZL,
+                       int64_t ldgzl, float* gZR, int64_t ldgzr, float* gR, int64_t ldgr,
+                       float* g_attn_vec, void* workspace, size_t workspace_bytes, void* stream);
+/* dst[r][0:cols) += src[r][0:cols) (row pitches lds, ldd; cols % 4 == 0, rows 16-byte aligned):
+ * share_weights adds gZR onto gZL before the single weight block's products. */
+int mvml_add_cols_f32(int64_t rows, int cols, const float* src, int64_t lds, float* dst, int64_t ldd,
+                      void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Set2Set (dgl 0.9.1, model.py:82-84, 92) building blocks.
  * LSTM cell (torch.nn.LSTM gate order i,f,g,o): gates_pre[B, 4D] = x W_ih^T + h W_hh^T (by
  * mvml_gemm_f32), then

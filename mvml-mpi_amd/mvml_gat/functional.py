@@ -1131,3 +1131,221 @@ class LinearReLUFunction(torch.autograd.Function):
             gx = torch.empty_like(x)
             linear_dx(g_pre, weight, gx, M, Nout, K, lm)
         return gx, gw, gb, None
+
+
+def gatv2_fwd_bytes(N, E, H, F, out_cols, res_cols):
+    """Algorithmic HBM bytes of one mvml_gatv2_agg_fwd (re-gathers of rows not counted, SURVEY.md
+    §8d): read ZL, ZR and R once, rowptr, src ids, the attention vector; write out and attn."""
+    return 4 * (2 * N * H * F + N * res_cols + N * out_cols + E * H + E + N + 1 + H * F)
+
+
+def gatv2_bwd_bytes(N, E, H, F, out_cols, res_cols, mode):
+    """Algorithmic bytes of mvml_gatv2_agg_bwd: read ZL, ZR, g_out (+ out for ELU'), attn, both
+    CSRs; write gZL, gZR, gR, g_s (written, then read by source) and the g_attn partial rows."""
+    P = int(_lib.lib().mvml_gatv2_partial_rows(N))
+    return 4 * (4 * N * H * F + N * out_cols * (2 if mode == MODE_FLATTEN_ELU else 1) + N * res_cols
+                + 3 * E * H + 2 * E + 2 * (N + 1) + 2 * P * H * F)
+
+
+class GATv2LayerFunction(torch.autograd.Function):
+    """dgllife GATv2Layer(GATv2Conv) forward / backward: one projection GEMM
+    Y = X [W_src ; W_dst ; W_res]^T + [b_src | b_dst | b_res] (split-fp16 with per-row scales, the
+    biases as its column bias), then mvml_gatv2_agg_fwd / mvml_gatv2_agg_bwd (csrc/gatv2_agg.hip).
+
+    share_weights: w_dst and b_dst are None, Y has no W_dst block and ZR is ZL; the backward adds
+    gZR onto gZL before the single block's products.  res_kind RES_PROJ: w_res (and b_res) ride in
+    the GEMM, as their head mean in a head-mean layer (the layer only ever uses that);
+    RES_IDENTITY: X, or its head mean, is R; RES_NONE: no R.  Parameters that do not exist get None
+    gradients."""
+
+    @staticmethod
+    def forward(ctx, X, w_src, w_dst, w_res, b_src, b_dst, b_res, attn, g, H, F, slope, mode,
+                res_kind=RES_PROJ):
+        if res_kind not in (RES_PROJ, RES_IDENTITY, RES_NONE):
+            raise ValueError(f"GATv2LayerFunction: unknown residual kind {res_kind!r}")
+        if (w_res is None) != (res_kind != RES_PROJ):
+            raise ValueError("GATv2LayerFunction: res_fc.weight goes with the projected residual only")
+        for t, n in ((X, "feat"), (w_src, "fc_src.weight"), (w_dst, "fc_dst.weight"), (w_res, "res_fc.weight"),
+                     (b_src, "fc_src.bias"), (b_dst, "fc_dst.bias"), (b_res, "res_fc.bias"), (attn, "attn")):
+            if t is not None:
+                _check_cuda_f32(t, n)
+        Xpad = zero_padded(X, _round4(X.shape[1])) if X.dim() == 2 else None
+        if Xpad is None:
+            X = _c(X)
+        N, Fin = X.shape
+        dev = X.device
+        st = _stream(dev)
+        HF = H * F
+        if res_kind == RES_IDENTITY and Fin != HF:
+            raise ValueError(f"GATv2LayerFunction: the identity residual needs in_feats == H F ({Fin} != {HF})")
+        mean = mode == MODE_MEAN
+        shared = w_dst is None
+        RW = F if mean else HF
+        c_r = 0 if shared else HF               # ZR's column in Y / gZR's in gY
+        c_res = HF if shared else 2 * HF        # the projected residual's
+        C = c_res + (RW if res_kind == RES_PROJ else 0)
+        Fp = _round4(Fin)
+        Xp = Xpad if Xpad is not None else (X if Fp == Fin else torch.nn.functional.pad(X, (0, Fp - Fin)))
+        # Wcat = [W_src ; W_dst ; W_res (head mean in a head-mean layer)], pad columns zero
+        Wcat = torch.empty((C, Fp), dtype=torch.float32, device=dev)
+        if Fp != Fin:
+            zero_(Wcat)
+        copy2d(Wcat[:HF, :Fin], _c(w_src))
+        if not shared:
+            copy2d(Wcat[HF:2 * HF, :Fin], _c(w_dst))
+        biases = [b for b in (b_src, b_dst, b_res) if b is not None]
+        bcat = zeros(C, device=dev) if biases else None
+        if b_src is not None:
+            copy2d(bcat[:HF], _c(b_src))
+        if b_dst is not None:
+            copy2d(bcat[HF:2 * HF], _c(b_dst))
+        if res_kind == RES_PROJ:
+            if mean:
+                wm = torch.empty((F, Fin), dtype=torch.float32, device=dev)
+                call("mvml_head_mean_f32", 1, H, F * Fin, ptr(_c(w_res)), HF * Fin, ptr(wm), F * Fin, st)
+                copy2d(Wcat[c_res:, :Fin], wm)
+                if b_res is not None:
+                    bm = torch.empty(F, dtype=torch.float32, device=dev)
+                    call("mvml_head_mean_f32", 1, H, F, ptr(_c(b_res)), HF, ptr(bm), F, st)
+                    copy2d(bcat[c_res:], bm)
+            else:
+                copy2d(Wcat[c_res:, :Fin], _c(w_res))
+                if b_res is not None:
+                    copy2d(bcat[c_res:], _c(b_res))
+        # split-fp16 maxima as GATLayerFunction's: every atom row at its own scale
+        rows = GEMM_ALGO == "f16x2" and ROW_SCALES
+        amx = xr = wil = None
+        if rows:
+            amx = zeros(3, dtype=torch.int32, device=dev)  # [X, Wcat, gY (bwd)]
+            xr = known_rows(X)
+            if xr is None:
+                xr = absmax_rows(Xp, N, Fp, Fp)
+            absmax(xr, N, 1, 1, amx, 0)
+            absmax(Wcat, C, Fp, Fp, amx, 1)
+            wil = split_il4(Wcat, C, Fp, Fp, slot(amx, 1))
+        ldy = _row_pitch(C)
+        Y = torch.empty((N, ldy), dtype=torch.float32, device=dev)
+        if rows:
+            gemm(Xp, Wcat, N, C, Fp, 0, 0, Fp, Fp, Y, ldy, bias=bcat, amax=(None, slot(amx, 1)), arows=xr,
+                 bil4=wil, role="gatv2_proj")
+        else:
+            gemm(Xp, Wcat, N, C, Fp, 0, 0, Fp, Fp, Y, ldy, bias=bcat, role="gatv2_proj")
+        # the residual rows: Y's block (projected), the input or its head mean (identity), none
+        R, ldr = None, 0
+        if res_kind == RES_PROJ:
+            R, ldr = Y[:, c_res:], ldy
+        elif res_kind == RES_IDENTITY and mean:
+            R, ldr = torch.empty((N, F), dtype=torch.float32, device=dev), F
+            call("mvml_head_mean_f32", N, H, F, ptr(Xp), Fp, ptr(R), ldr, st)
+        elif res_kind == RES_IDENTITY:
+            R, ldr = Xp, Fp
+        out_cols = F if mean else HF
+        E = g.num_edges()
+        out = torch.empty((N, out_cols), dtype=torch.float32, device=dev)
+        a = torch.empty((max(E, 1), H), dtype=torch.float32, device=dev)[:E]
+        av = _c(attn).reshape(-1)
+        _lib.call_tag[0] = {"layer": f"H{H}xF{F}",
+                            "bytes": gatv2_fwd_bytes(N, E, H, F, out_cols, 0 if res_kind == RES_NONE else RW)}
+        call("mvml_gatv2_agg_fwd", N, ptr(g.in_rowptr), ptr(g.in_src), ptr(Y), ldy, ptr(Y[:, c_r:]), ldy, H, F,
+             ptr(av), ptr(R), ldr, float(slope), int(mode), ptr(out), ptr(a), st)
+        if DEBUG_CAPTURE is not None:
+            DEBUG_CAPTURE.setdefault("zlr_fwd", []).append(
+                (Y[:, :HF].detach().clone(), Y[:, c_r:c_r + HF].detach().clone()))
+        ctx.save_for_backward(Xp, Wcat, Y, a, out, av)
+        ctx.mark_non_differentiable(a)
+        ctx.g, ctx.H, ctx.F, ctx.slope, ctx.mode, ctx.Fin = g, H, F, slope, mode, Fin
+        ctx.res_kind, ctx.shared = res_kind, shared
+        ctx.has_b = (b_src is not None, b_dst is not None, b_res is not None)
+        ctx.attn_shape = attn.shape
+        ctx.amx, ctx.wil = amx, wil
+        return out, a
+
+    @staticmethod
+    def backward(ctx, g_out, _g_a):
+        Xp, Wcat, Y, a, out, av = ctx.saved_tensors
+        g, H, F, mode, Fin = ctx.g, ctx.H, ctx.F, ctx.mode, ctx.Fin
+        res_kind, shared, amx = ctx.res_kind, ctx.shared, ctx.amx
+        g_out = _c(g_out)
+        N, Fp = Xp.shape
+        dev = Xp.device
+        st = _stream(dev)
+        HF = H * F
+        mean = mode == MODE_MEAN
+        RW = F if mean else HF
+        c_r = 0 if shared else HF
+        c_res = HF if shared else 2 * HF
+        C, ldy = Wcat.shape[0], Y.shape[1]
+        E = g.num_edges()
+        L = _lib.lib()
+        ldg = _row_pitch(C)
+        gY = torch.empty((N, ldg), dtype=torch.float32, device=dev)
+        # gZR: its own block of gY, or (share_weights) a buffer that is then added onto gZL
+        gZR, ldgzr = (torch.empty((N, HF), dtype=torch.float32, device=dev), HF) if shared else (gY[:, HF:], ldg)
+        # gR: gY's block (projected); the identity residual's share of dX written straight into gX
+        # (flatten; a head-mean layer's is g_out itself: not formed); none otherwise
+        gX = gR = None
+        ldgr = 0
+        if res_kind == RES_PROJ:
+            gR, ldgr = gY[:, c_res:], ldg
+        elif res_kind == RES_IDENTITY and not mean and ctx.needs_input_grad[0]:
+            gX = torch.empty((N, Fin), dtype=torch.float32, device=dev)
+            gR, ldgr = gX, Fin
+        g_av = torch.empty(HF, dtype=torch.float32, device=dev)
+        wp, wn = _lib.ws_ptr_size(L.mvml_gatv2_agg_bwd_workspace_size(N, E, H, F), dev)
+        _lib.call_tag[0] = {"layer": f"H{H}xF{F}",
+                            "bytes": gatv2_bwd_bytes(N, E, H, F, g_out.shape[1],
+                                                     0 if res_kind == RES_NONE else RW, mode)}
+        call("mvml_gatv2_agg_bwd", N, ptr(g.in_rowptr), ptr(g.in_src), ptr(g.out_rowptr), ptr(g.out_dst),
+             ptr(g.out_inslot), E, ptr(Y), ldy, ptr(Y[:, c_r:]), ldy, H, F, ptr(av), ptr(a), ptr(out), ptr(g_out),
+             float(ctx.slope), int(mode), ptr(gY), ldg, ptr(gZR), ldgzr, ptr(gR), ldgr, ptr(g_av), wp, wn, st)
+        if shared:
+            call("mvml_add_cols_f32", N, HF, ptr(gZR), ldgzr, ptr(gY), ldg, st)
+        has_bs, has_bd, has_br = ctx.has_b
+        f32 = dict(dtype=torch.float32, device=dev)
+        g_bs = g_bd = g_br = None
+        if has_bs:
+            g_bs = torch.empty(HF, **f32)
+            colsum(gY, N, HF, ldg, g_bs)
+        if has_bd:
+            g_bd = torch.empty(HF, **f32)
+            colsum(gY, N, HF, ldg, g_bd, offset=HF)
+        if has_br:
+            g_br = torch.empty(HF, **f32)
+            if mean:  # every head's bias sees g_out / H: one column sum, replicated over the heads
+                colsum(g_out, N, F, F, g_br, alpha=1.0 / H)
+                if H > 1:
+                    copy2d(g_br.view(H, F)[1:], g_br[:F].view(1, F).expand(H - 1, F))
+            else:
+                colsum(gY, N, HF, ldg, g_br, offset=c_res)
+        # dL/dWcat = gY^T X and dL/dX = gY Wcat (+ the identity residual's share)
+        if amx is not None:
+            zero_(amx[2:3])
+            absmax(gY, N, C, ldg, amx, 2)
+        gW = torch.empty((C, Fp), **f32)
+        gemm(gY, Xp, C, Fp, N, 1, 1, ldg, Fp, gW, Fp,
+             amax=None if amx is None else (slot(amx, 2), slot(amx, 0)), role="gatv2_dw")
+        g_ws = copy2d(torch.empty((HF, Fin), **f32), gW[:HF, :Fin])
+        g_wd = None if shared else copy2d(torch.empty((HF, Fin), **f32), gW[HF:2 * HF, :Fin])
+        g_wr = None
+        if res_kind == RES_PROJ:
+            g_wr = torch.empty((HF, Fin), **f32)
+            if mean:
+                gm = copy2d(torch.empty((F, Fin), **f32), gW[c_res:, :Fin])
+                call("mvml_head_mean_bwd_f32", 1, H, F * Fin, ptr(gm), F * Fin, ptr(g_wr), HF * Fin, st)
+            else:
+                copy2d(g_wr, gW[c_res:, :Fin])
+        if ctx.needs_input_grad[0]:
+            beta = 1.0 if res_kind == RES_IDENTITY else 0.0
+            if gX is None:
+                gX = torch.empty((N, Fin), **f32)
+                if beta:
+                    call("mvml_head_mean_bwd_f32", N, H, F, ptr(g_out), F, ptr(gX), Fin, st)
+            if amx is not None:
+                gemm(gY, Wcat, N, Fin, C, 0, 1, ldg, Fp, gX, Fin, amax=(None, slot(amx, 1)),
+                     arows=absmax_rows(gY, N, C, ldg), bil4=ctx.wil, beta=beta)
+            else:
+                gemm(gY, Wcat, N, Fin, C, 0, 1, ldg, Fp, gX, Fin, beta=beta)
+        else:
+            gX = None
+        return (gX, g_ws, g_wd, g_wr, g_bs, g_bd, g_br, g_av.view(ctx.attn_shape),
+                None, None, None, None, None, None)

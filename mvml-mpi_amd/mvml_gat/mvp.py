@@ -39,14 +39,14 @@ class MVP(MVFusion):
     def __init__(self, num_classes, in_feats=64, hidden_feats=None, num_step_set2set=6,
                  num_layer_set2set=3, rnn_embed_dim=64, blstm_dim=128, blstm_layers=2, fp_2_dim=128,
                  num_heads=4, dropout=0.2, device='cpu', proj_dtype=None,
-                 graph_readout="set2set"):
+                 graph_readout="set2set", graph_conv="gat"):
         if hidden_feats is None:
             hidden_feats = [64, 64]
         super().__init__(hidden_feats[-1], num_heads, num_classes, dropout)
         self.device = device
         self.vocab = tokens_struct()
         self.gnn = GNNModule(in_feats, hidden_feats, dropout, num_step_set2set, num_layer_set2set,
-                             proj_dtype=proj_dtype, readout=graph_readout)
+                             proj_dtype=proj_dtype, readout=graph_readout, conv=graph_conv)
         self.rnn = RNNModule(self.vocab, rnn_embed_dim, blstm_dim, blstm_layers,
                              self.final_hidden_feats, dropout, bidirectional=True, device=device)
         self.fp_mlp = FPNModule(fp_2_dim, self.final_hidden_feats)

@@ -189,6 +189,151 @@ class GAT(nn.Module):
         return feats
 
 
+class GATv2Conv(nn.Module):
+    """dgl.nn.pytorch.GATv2Conv (0.9.1) parameters, with feat/attn dropout 0 (restated; parity with
+    dgl is unpinned).  fc_src = Linear(in, H F, bias=bias); fc_dst is the same module with
+    share_weights, else a second such Linear; attn (1, H, F); res_fc a Linear(in, H F, bias=bias)
+    when residual and in_feats != H F, nn.Identity() when they are equal, a None buffer with
+    residual=False.  There is no separate bias parameter.  forward() returns rst (N, H, F), and
+    with get_attention=True also the attention (E, H, 1) in edge-id order, detached."""
+
+    def __init__(self, in_feats, out_feats, num_heads, feat_drop=0.0, attn_drop=0.0,
+                 negative_slope=0.2, residual=False, activation=None, allow_zero_in_degree=False,
+                 bias=True, share_weights=False):
+        super().__init__()
+        if feat_drop or attn_drop:
+            raise NotImplementedError("GATv2Conv: feat_drop/attn_drop > 0 are not on the fused path")
+        # the aggregation kernels' range (csrc/gatv2_agg.hip check_shapes): refuse here, not in forward
+        if num_heads not in (1, 2, 4, 8) or out_feats <= 0 or out_feats % 4 or num_heads * out_feats > 2048:
+            raise ValueError(
+                f"GATv2Conv: num_heads must be 1, 2, 4 or 8 and out_feats a positive multiple of 4 with "
+                f"num_heads * out_feats <= 2048 (got num_heads={num_heads}, out_feats={out_feats})")
+        self._num_heads = num_heads
+        self._in_feats = in_feats
+        self._out_feats = out_feats
+        self._allow_zero_in_degree = allow_zero_in_degree
+        self.negative_slope = negative_slope
+        self.activation = activation
+        self.share_weights = share_weights
+        self.bias = bias
+        self.fc_src = nn.Linear(in_feats, out_feats * num_heads, bias=bias)
+        self.fc_dst = self.fc_src if share_weights else nn.Linear(in_feats, out_feats * num_heads, bias=bias)
+        self.attn = nn.Parameter(torch.empty(1, num_heads, out_feats))
+        if not residual:
+            self.res_kind = Fn.RES_NONE
+            self.register_buffer("res_fc", None)
+        elif in_feats == num_heads * out_feats:
+            self.res_kind = Fn.RES_IDENTITY
+            self.res_fc = nn.Identity()
+        else:
+            self.res_kind = Fn.RES_PROJ
+            self.res_fc = nn.Linear(in_feats, num_heads * out_feats, bias=bias)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        gain = nn.init.calculate_gain("relu")
+        linears = [self.fc_src] + ([] if self.share_weights else [self.fc_dst])
+        if isinstance(self.res_fc, nn.Linear):
+            linears.append(self.res_fc)
+        for lin in linears:
+            nn.init.xavier_normal_(lin.weight, gain=gain)
+            if lin.bias is not None:
+                nn.init.constant_(lin.bias, 0)
+        nn.init.xavier_normal_(self.attn, gain=gain)
+
+    _check_graph = GATConv._check_graph
+
+    def fused(self, graph, feat, mode):
+        """(out, attention in in-CSR slot order) of the fused layer kernel for `mode`."""
+        self._check_graph(graph)
+        res = self.res_fc if self.res_kind == Fn.RES_PROJ else None
+        dst = None if self.share_weights else self.fc_dst
+        return Fn.GATv2LayerFunction.apply(
+            feat, self.fc_src.weight, dst.weight if dst is not None else None,
+            res.weight if res is not None else None, self.fc_src.bias,
+            dst.bias if dst is not None else None, res.bias if res is not None else None, self.attn,
+            graph, self._num_heads, self._out_feats, self.negative_slope, mode, self.res_kind)
+
+    def forward(self, graph, feat, get_attention=False):
+        rst, a = self.fused(graph, feat, Fn.MODE_FLATTEN)
+        rst = rst.view(-1, self._num_heads, self._out_feats)
+        if self.activation is not None:
+            rst = self.activation(rst)
+        if not get_attention:
+            return rst
+        # slot order -> edge-id order: slot k of the in-CSR holds edge in_eid[k]
+        att = torch.empty_like(a)
+        att[graph.in_eid.long()] = a.detach()
+        return rst, att.unsqueeze(-1)
+
+
+class GATv2Layer(nn.Module):
+    """dgllife.model.gnn.gatv2.GATv2Layer (0.3.0): gatv2_conv (its activation applied per head)
+    -> flatten(1) | mean(1); (flatten, ELU), (flatten, None) and (mean, None) are one kernel, any
+    other activation runs the flatten kernel followed by torch ops."""
+
+    def __init__(self, in_feats, out_feats, num_heads, feat_drop=0.0, attn_drop=0.0, negative_slope=0.2,
+                 residual=True, activation=None, allow_zero_in_degree=False, bias=True,
+                 share_weights=False, agg_mode="flatten"):
+        super().__init__()
+        self.gatv2_conv = GATv2Conv(in_feats, out_feats, num_heads, feat_drop, attn_drop, negative_slope,
+                                    residual, activation, allow_zero_in_degree, bias, share_weights)
+        assert agg_mode in ["flatten", "mean"]
+        self.agg_mode = agg_mode
+
+    def forward(self, bg, feats):
+        conv = self.gatv2_conv
+        act = conv.activation
+        if act is None:
+            return conv.fused(bg, feats, Fn.MODE_MEAN if self.agg_mode == "mean" else Fn.MODE_FLATTEN)[0]
+        if act is F.elu and self.agg_mode == "flatten":
+            return conv.fused(bg, feats, Fn.MODE_FLATTEN_ELU)[0]
+        rst = act(conv.fused(bg, feats, Fn.MODE_FLATTEN)[0].view(-1, conv._num_heads, conv._out_feats))
+        return rst.flatten(1) if self.agg_mode == "flatten" else rst.mean(1)
+
+
+class GATv2(nn.Module):
+    """dgllife.model.gnn.gatv2.GATv2 (0.3.0) with GAT's defaults: 4 heads per layer, slope 0.2,
+    residual, bias, 'flatten' + ELU for all but the last layer, 'mean' + no activation last;
+    share_weights defaults to False per layer."""
+
+    def __init__(self, in_feats, hidden_feats=None, num_heads=None, feat_drops=None, attn_drops=None,
+                 alphas=None, residuals=None, activations=None, allow_zero_in_degree=False, biases=None,
+                 share_weights=None, agg_modes=None):
+        super().__init__()
+        hidden_feats = list(hidden_feats) if hidden_feats is not None else [32, 32]
+        n = len(hidden_feats)
+        num_heads = num_heads or [4] * n
+        feat_drops = feat_drops or [0.0] * n
+        attn_drops = attn_drops or [0.0] * n
+        alphas = alphas or [0.2] * n
+        residuals = residuals or [True] * n
+        if activations is None:
+            activations = [F.elu] * (n - 1) + [None]
+        biases = biases or [True] * n
+        share_weights = share_weights or [False] * n
+        if agg_modes is None:
+            agg_modes = ["flatten"] * (n - 1) + ["mean"]
+        self.hidden_feats = hidden_feats
+        self.num_heads = num_heads
+        self.agg_modes = agg_modes
+        self.gnn_layers = nn.ModuleList()
+        for i in range(n):
+            self.gnn_layers.append(GATv2Layer(in_feats, hidden_feats[i], num_heads[i], feat_drops[i],
+                                              attn_drops[i], alphas[i], residuals[i], activations[i],
+                                              allow_zero_in_degree, biases[i], share_weights[i], agg_modes[i]))
+            in_feats = hidden_feats[i] * num_heads[i] if agg_modes[i] == "flatten" else hidden_feats[i]
+
+    def reset_parameters(self):
+        for layer in self.gnn_layers:
+            layer.gatv2_conv.reset_parameters()
+
+    def forward(self, g, feats):
+        for gnn in self.gnn_layers:
+            feats = gnn(g, feats)
+        return feats
+
+
 class Set2Set(nn.Module):
     """dgl.nn.pytorch.glob.Set2Set (0.9.1): lstm = nn.LSTM(2*input_dim, input_dim, n_layers)
     (the module is a parameter container; the recurrence runs on the HIP kernels)."""
@@ -295,19 +440,26 @@ class GNNModule(nn.Module):
     WeightedSumAndMax, the same 2 * hidden_feats[-1] output width; num_step_set2set and
     num_layer_set2set are then unused and the state_dict has readout.weight_and_sum.* instead of
     readout.lstm.*).
+
+    ``conv``: "gat" (the reference's dgllife GAT, the default: the modules, keys and launches are
+    unchanged) or "gatv2" (dgllife's GATv2 with its defaults; keys conv.gnn_layers.{i}.gatv2_conv.*;
+    fp32-accurate projection only).
     """
 
     READOUTS = ("set2set", "weighted_sum_max")
+    CONVS = ("gat", "gatv2")
 
     def __init__(self, in_feats=64, hidden_feats=None, dropout=0.2, num_step_set2set=6,
-                 num_layer_set2set=3, proj_dtype=None, readout="set2set"):
+                 num_layer_set2set=3, proj_dtype=None, readout="set2set", conv="gat"):
         super().__init__()
         if hidden_feats is None:
             raise TypeError("GNNModule needs hidden_feats (the reference indexes hidden_feats[-1])")
         if readout not in self.READOUTS:
             raise ValueError(f"GNNModule: readout must be one of {self.READOUTS} (got {readout!r})")
+        if conv not in self.CONVS:
+            raise ValueError(f"GNNModule: conv must be one of {self.CONVS} (got {conv!r})")
         hidden_feats = list(hidden_feats)
-        self.conv = GAT(in_feats, hidden_feats)
+        self.conv = GAT(in_feats, hidden_feats) if conv == "gat" else GATv2(in_feats, hidden_feats)
         if readout == "set2set":
             self.readout = Set2Set(input_dim=hidden_feats[-1], n_iters=num_step_set2set,
                                    n_layers=num_layer_set2set)
@@ -323,6 +475,10 @@ class GNNModule(nn.Module):
         (bf16 operands on MFMA, fp32 accumulate — BASELINE config 4)."""
         if dtype not in (None, torch.float32, torch.bfloat16):
             raise ValueError("proj_dtype must be None, torch.float32 or torch.bfloat16")
+        if isinstance(self.conv, GATv2):
+            if dtype == torch.bfloat16:
+                raise NotImplementedError("GNNModule: the bf16 projection is not implemented for conv='gatv2'")
+            return
         if dtype == torch.bfloat16 and any(layer.gat_conv.res_kind != Fn.RES_PROJ
                                            for layer in self.conv.gnn_layers):
             raise NotImplementedError(

@@ -185,6 +185,8 @@ class _Args(argparse.Namespace):
     """parse()'s namespace: defaults of the options that are not in config.py."""
     READOUTS = ("set2set", "weighted_sum_max")
     graph_readout = "set2set"
+    CONVS = ("gat", "gatv2")
+    graph_conv = "gat"
 
 
 def parse(argv=None):
@@ -218,6 +220,9 @@ def parse(argv=None):
     p.add_argument("--graph_readout", type=str, default=argparse.SUPPRESS, choices=list(_Args.READOUTS),
                    help="the graph view's readout: set2set (the reference's, the default) or "
                         "weighted_sum_max (dgllife's WeightedSumAndMax: one pass over the atom rows, no LSTM)")
+    p.add_argument("--graph_conv", type=str, default=argparse.SUPPRESS, choices=list(_Args.CONVS),
+                   help="the graph view's convolution: gat (the reference's, the default) or gatv2 "
+                        "(dgllife's GATv2: dynamic attention, scored from the whole source row per edge)")
     return p.parse_args(argv, namespace=_Args())
 
 
@@ -254,7 +259,8 @@ def main(args, log=print):
         model = MVP(num_classes=args.class_num, in_feats=dataset.feat_size, hidden_feats=args.hidden_feats,
                     rnn_embed_dim=args.rnn_embed_dim, blstm_dim=args.rnn_hidden_dim,
                     blstm_layers=args.rnn_layers, fp_2_dim=args.fp_dim, dropout=args.p,
-                    num_heads=args.head, device=device, graph_readout=args.graph_readout).to(device)
+                    num_heads=args.head, device=device, graph_readout=args.graph_readout,
+                    graph_conv=args.graph_conv).to(device)
         optimizer = FlatAdam(model.parameters(), lr=args.lr, weight_decay=args.weight_decay)
         scheduler = torch.optim.lr_scheduler.ExponentialLR(optimizer, gamma=0.95)
         stopper = EarlyStopping(mode='higher', filename=os.path.join(args.output, f'net_{iteration}.pkl'),
