@@ -15,6 +15,7 @@
 // counts (order-independent), so the output is deterministic and bit-exact with the oracle
 // (oracle/graph_ref.py: csr_ref).
 #include "common.h"
+#include "wave_ops.h"
 
 namespace mvml {
 namespace {
@@ -204,11 +205,6 @@ __device__ void rows_from_counts(int* cnt, int n, int64_t noff, int64_t eoff,
 //    <= kBigMolEdges edges (config 5's 150-400-atom hub molecules), walking that list; the rest
 //    to a second list for build_csr_kernel (one workgroup per graph, any size).
 // A stable counting sort has one result, so every path gives the same output.
-__device__ __forceinline__ void wave_lds_sync_b() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // exclusive wave scan of cnt[0..n) in place (+ the row starts), returns the zero-count rows
 __device__ __forceinline__ int wave_rows_from_counts(int* cnt, int n, int64_t noff, int64_t eoff,
@@ -272,7 +268,7 @@ __device__ __forceinline__ void wave_place_edges(int ne, int n, int64_t eoff, in
     }
     const int rank = __popcll(same & below);
     const int slot = k >= 0 ? cursor[k] + rank : 0;
-    wave_lds_sync_b();  // every lane read its cursor before any advances
+    wave_sync_wavefront_scope();  // every lane read its cursor before any advances
     if (k >= 0) {
       atomicAdd(&cursor[k], 1);
       const int64_t gs = eoff + slot;
@@ -284,7 +280,7 @@ __device__ __forceinline__ void wave_place_edges(int ne, int n, int64_t eoff, in
         out_aux[gs] = s_inslot[i];          // out_inslot
       }
     }
-    wave_lds_sync_b();
+    wave_sync_wavefront_scope();
   }
 }
 
@@ -316,7 +312,7 @@ __device__ __forceinline__ void wave_place_edges_reg(int ne, int n, int64_t eoff
     }
     const int rank = __popcll(same & below);
     const int slot = k >= 0 ? cursor[k] + rank : 0;
-    wave_lds_sync_b();
+    wave_sync_wavefront_scope();
     if (k >= 0) {
       atomicAdd(&cursor[k], 1);
       const int64_t gs = eoff + slot;
@@ -328,7 +324,7 @@ __device__ __forceinline__ void wave_place_edges_reg(int ne, int n, int64_t eoff
         out_aux[gs] = s_inslot[i];
       }
     }
-    wave_lds_sync_b();
+    wave_sync_wavefront_scope();
   }
 }
 
@@ -372,7 +368,7 @@ __device__ __forceinline__ void wave_build_molecule(const CsrArgs& a, int64_t g,
     cout[j] = 0;
     a.node_graph[noff + j] = (int32_t)g;
   }
-  wave_lds_sync_b();
+  wave_sync_wavefront_scope();
   int bad = 0;
   auto count_edge = [&](int i, int s, int d) {
     a.src[eoff + i] = s + (int32_t)noff;
@@ -395,7 +391,7 @@ __device__ __forceinline__ void wave_build_molecule(const CsrArgs& a, int64_t g,
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o, 64);
   if (lane == 0 && bad) atomicAdd(&a.flags[1], bad);
-  wave_lds_sync_b();
+  wave_sync_wavefront_scope();
   int zeros = wave_rows_from_counts(cin, n, noff, eoff, a.in_rowptr);
   wave_rows_from_counts(cout, n, noff, eoff, a.out_rowptr);
 #pragma unroll
@@ -405,7 +401,7 @@ __device__ __forceinline__ void wave_build_molecule(const CsrArgs& a, int64_t g,
     a.in_rowptr[noff + n] = (int32_t)(eoff + ne);  // == the next molecule's first row start
     a.out_rowptr[noff + n] = (int32_t)(eoff + ne);
   }
-  wave_lds_sync_b();
+  wave_sync_wavefront_scope();
   if constexpr (NCH > 0) {
     wave_place_edges_reg<true>(ne, n, eoff, noff, sv, dv, cin, slot, a.in_src, a.in_eid);
     wave_place_edges_reg<false>(ne, n, eoff, noff, sv, dv, cout, slot, a.out_dst, a.out_inslot);
@@ -451,7 +447,7 @@ build_csr_bigwave_kernel(CsrArgs a, const int32_t* __restrict__ list, const int*
       continue;
     }
     wave_build_molecule(a, g, n, ne, a.node_off[g], a.edge_off[g], s_cin, s_cout, s_slot);
-    wave_lds_sync_b();  // this molecule's LDS reads are done before the next one's zeroing
+    wave_sync_wavefront_scope();  // this molecule's LDS reads are done before the next one's zeroing
   }
 }
 

@@ -5,6 +5,7 @@
 #include <stddef.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "../../include/mvml_gat.h"
 
@@ -64,6 +65,23 @@ struct Carver {
 };
 inline size_t carve_size(size_t bytes) { return (bytes + 255) & ~size_t(255); }
 
+// Argument checks of the float4 kernels: a 16-byte aligned pointer; rows of `width` floats at a
+// row stride ld that float4 accesses and 32-bit offsets can walk.
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+inline bool row_ok(const void* p, int64_t ld, int64_t width) {
+  return p != nullptr && aligned16(p) && ld % 4 == 0 && ld >= width && ld < (int64_t(1) << 28);
+}
+
+// Run-time value -> template argument: fn(std::integral_constant<int, V>{}) for the V among Vs
+// that equals v, and its result; kNoCase when none does (no launch code returns that).
+constexpr int kNoCase = -(1 << 30);
+template <int... Vs, typename Fn>
+int switch_const(int v, Fn&& fn) {
+  int rc = kNoCase;
+  (void)((v == Vs && (rc = fn(std::integral_constant<int, Vs>{}), true)) || ...);
+  return rc;
+}
+
 // ---- device helpers -------------------------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -122,3 +140,14 @@ inline int proj_logw(int F) {
       return MVML_ERR_INVALID;           \
     }                                    \
   } while (0)
+
+namespace mvml {
+// Head count and width of the graph-attention aggregations (gat_agg.hip, gatv2_agg.hip); each
+// file checks `mode` itself, in its own words.
+inline int check_heads(int H, int F, const char* who) {
+  MVML_REQUIRE(H == 1 || H == 2 || H == 4 || H == 8, "%s: num_heads must be 1, 2, 4 or 8 (got %d)", who, H);
+  MVML_REQUIRE(F > 0 && F % 4 == 0, "%s: out_feats must be a positive multiple of 4 (got %d)", who, F);
+  MVML_REQUIRE((int64_t)H * F <= 2048, "%s: H*F must be <= 2048 (got %d)", who, H * F);
+  return MVML_OK;
+}
+}  // namespace mvml

@@ -1452,7 +1452,6 @@ extern "C" int mvml_layernorm_bwd(int64_t rows, int D, const float* x, int64_t l
                                                                          : KERN<true, 1>)
 static bool fuse_dk_ok(int dk) { return dk >= 16 && dk <= 64 * kDkVpl && dk % 4 == 0; }
 #define MVML_DK_SET "dk must be a multiple of 4 in [16, 384]"
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 extern "C" int mvml_token_attn_fwd(int64_t B, int H, int dk, const float* qkv, int64_t ld,
                                    float scale, float* att, float* P, void* stream) {

@@ -39,6 +39,7 @@
 // Workgroup -> atom mapping is XCD-aware (xcd_block): each XCD walks one contiguous range of
 // atoms, so a molecule's neighbour rows are gathered from ONE XCD's L2.
 #include "common.h"
+#include "wave_ops.h"
 
 namespace mvml {
 namespace {
@@ -48,34 +49,6 @@ constexpr int kWavesPerBlock = 4;
 #define MVML_FWD_UNR 2  // neighbour rows in flight per gather step (forward)
 #endif
 
-__device__ __forceinline__ float rl(float x, int j) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), j));
-}
-__device__ __forceinline__ int rl(int x, int j) { return __builtin_amdgcn_readlane(x, j); }
-
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ float leaky(float x, float slope) { return x > 0.f ? x : x * slope; }
-__device__ __forceinline__ float elu(float x) { return x > 0.f ? x : expm1f(x); }
-
-__device__ __forceinline__ float4 f4(float a) { return make_float4(a, a, a, a); }
-__device__ __forceinline__ float4 fma4(float a, float4 z, float4 c) {
-  return make_float4(fmaf(a, z.x, c.x), fmaf(a, z.y, c.y), fmaf(a, z.z, c.z), fmaf(a, z.w, c.w));
-}
-__device__ __forceinline__ float4 add4(float4 a, float4 b) {
-  return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
-}
-// explicit roundings: with the device default -ffp-contract=fast the compiler would pick the
-// contraction per call site, so kernels that promise the same dots bitwise could differ
-__device__ __forceinline__ float dot4(float4 a, float4 b) {
-  return __fmaf_rn(a.w, b.w, __fmaf_rn(a.z, b.z, __fmaf_rn(a.y, b.y, __fmul_rn(a.x, b.x))));
-}
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 // streaming (non-temporal) 16-B load / store: rows read or written exactly once pass through
 // without displacing the rows an XCD's waves share in L2
 typedef float mvml_f4v __attribute__((ext_vector_type(4)));
@@ -88,18 +61,6 @@ __device__ __forceinline__ void st4nt(float* p, float4 v) {
   __builtin_nontemporal_store(w, reinterpret_cast<mvml_f4v*>(p));
 }
 
-template <int H>
-__device__ __forceinline__ float pick(const float (&a)[H], int h) {
-  float r = a[0];
-#pragma unroll
-  for (int k = 1; k < H; ++k) r = (h == k) ? a[k] : r;
-  return r;
-}
-template <int H>
-__device__ __forceinline__ void add_at(float (&a)[H], int h, float v) {
-#pragma unroll
-  for (int k = 0; k < H; ++k) a[k] += (h == k) ? v : 0.f;
-}
 // wave-uniform per-head values -> p[0..H): lane h stores a[h]
 template <int H>
 __device__ __forceinline__ void store_heads(float* p, const float (&a)[H], int lane) {
@@ -124,60 +85,6 @@ __device__ __forceinline__ void block_amax_commit(float m, uint32_t* out) {
     for (int i = 1; i < NT / 64; ++i) r = fmaxf(r, red[i]);
     atomicMax(out, __float_as_uint(r));
   }
-}
-
-// All-reduce of H per-lane values over the 64 lanes in (H - 1) + (6 - log2 H) shuffles instead
-// of 6 H: a butterfly that halves the value count per step (lanes with the mask bit set keep
-// the upper half) and then finishes the single remaining value inside 64/H-lane groups.  After
-// it, lane l holds the total of head ((l >> (6 - log2 H)) & (H - 1)); readlane broadcasts them.
-template <int H>
-struct HeadReduce {
-  static constexpr int LOG = H == 1 ? 0 : H == 2 ? 1 : H == 4 ? 2 : 3;
-  template <bool MAX>
-  __device__ static __forceinline__ float op(float a, float b) { return MAX ? fmaxf(a, b) : a + b; }
-  template <bool MAX>
-  __device__ static __forceinline__ void all(float (&v)[H], int lane) {
-    float w[H];
-#pragma unroll
-    for (int h = 0; h < H; ++h) w[h] = v[h];
-    if constexpr (H >= 8) step<MAX, 8>(w, lane, 32);
-    if constexpr (H >= 4) step<MAX, 4>(w, lane, 32 >> (LOG - 2));
-    if constexpr (H >= 2) step<MAX, 2>(w, lane, 32 >> (LOG - 1));
-#pragma unroll
-    for (int m = 32 >> LOG; m >= 1; m >>= 1) w[0] = op<MAX>(w[0], __shfl_xor(w[0], m, 64));
-#pragma unroll
-    for (int h = 0; h < H; ++h)
-      v[h] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(w[0]), h << (6 - LOG)));
-  }
-  template <bool MAX, int N>
-  __device__ static __forceinline__ void step(float (&w)[H], int lane, int mask) {
-    const bool hi = (lane & mask) != 0;
-#pragma unroll
-    for (int i = 0; i < N / 2; ++i) {
-      const float keep = hi ? w[i + N / 2] : w[i];
-      const float send = hi ? w[i] : w[i + N / 2];
-      w[i] = op<MAX>(keep, __shfl_xor(send, mask, 64));
-    }
-  }
-};
-
-// g_rst[v, col..col+3] (per-head gradient of rst) from the layer-output gradient.
-__device__ __forceinline__ float4 grst_of(const float* __restrict__ g_out, const float* __restrict__ out,
-                                          int64_t v, int col, int HF, int F, int H, int mode) {
-  if (mode == 1) {  // mean over heads: torch mean backward = grad / H
-    const float4 g = ld4(g_out + v * F + (col % F));
-    const float inv = (float)H;
-    return make_float4(g.x / inv, g.y / inv, g.z / inv, g.w / inv);
-  }
-  float4 g = ld4(g_out + v * HF + col);
-  if (mode == 0) {  // ELU'(x) = 1 (x > 0) else exp(x) = out + 1 (torch elu_backward, is_result)
-    const float4 o = ld4(out + v * HF + col);
-    g.x *= o.x > 0.f ? 1.f : o.x + 1.f;
-    g.y *= o.y > 0.f ? 1.f : o.y + 1.f;
-    g.z *= o.z > 0.f ? 1.f : o.z + 1.f;
-    g.w *= o.w > 0.f ? 1.f : o.w + 1.f;
-  }
-  return g;
 }
 
 // ---------------------------------------------------------------------------------- forward
@@ -2223,6 +2130,31 @@ gat_flat_bwd_src1_kernel(int64_t N, const int32_t* __restrict__ out_rowptr,
   if (gy_amax) block_amax_commit<256>(gmx, gy_amax);
 }
 
+struct FlatSrc1Args {
+  int64_t N;
+  const int32_t *orp, *odst, *oslot;
+  const float* Y;
+  int64_t ldy;
+  const float *attn, *out, *g_out;
+  int F;
+  float *gpre, *gY;
+  int64_t ldgy;
+  uint32_t *blk_amax, *gy_rows;
+  float* gR;
+  int64_t ldgr;
+  int ramax;
+  hipStream_t st;
+};
+// the instance <H, NJ, MODE = mode, U = 1 (u1) or 2>
+template <int H, int NJ>
+void launch_flat_src1_kernel(int mode, bool u1, const FlatSrc1Args& a) {
+  const auto kernel = mode == 0 ? (u1 ? gat_flat_bwd_src1_kernel<H, NJ, 0, 1> : gat_flat_bwd_src1_kernel<H, NJ, 0>)
+                                : (u1 ? gat_flat_bwd_src1_kernel<H, NJ, 2, 1> : gat_flat_bwd_src1_kernel<H, NJ, 2>);
+  kernel<<<(unsigned)ceil_div(a.N, 4), 256, 0, a.st>>>(a.N, a.orp, a.odst, a.oslot, a.Y, a.ldy, a.attn, a.out,
+                                                       a.g_out, a.F, a.gpre, a.gY, a.ldgy, a.blk_amax, a.gy_rows,
+                                                       a.gR, a.ldgr, a.ramax);
+}
+
 template <int H>
 int launch_flat_src1(int64_t N, const int32_t* rp, const int32_t* src, const int32_t* orp,
                      const int32_t* odst, const int32_t* oslot, const float* Y, int64_t ldy,
@@ -2231,36 +2163,22 @@ int launch_flat_src1(int64_t N, const int32_t* rp, const int32_t* src, const int
                      uint32_t* gy_rows, hipStream_t st, float* gR, int64_t ldgr, int ramax) {
   const int HF = H * F;
   const int nj = (int)ceil_div(HF / 4, 64);
-  const unsigned b4 = (unsigned)ceil_div(N, 4), b256 = (unsigned)ceil_div(N, 256);
+  const unsigned b256 = (unsigned)ceil_div(N, 256);
   uint32_t* const blk_amax = gy_rows ? nullptr : gy_amax;  // (see launch_mean_src)
   const bool u1 = option(MVML_OPT_DST_UNR) != 2;  // one out-neighbour row per trip (2: two)
-#define MVML_FLAT_SRC1(NJ)                                                                                   \
-  do {                                                                                                       \
-    if (mode == 0 && u1)                                                                                     \
-      gat_flat_bwd_src1_kernel<H, NJ, 0, 1><<<b4, 256, 0, st>>>(                                              \
-          N, orp, odst, oslot, Y, ldy, attn, out, g_out, F, gpre, gY, ldgy, blk_amax, gy_rows, gR, ldgr, ramax); \
-    else if (mode == 0)                                                                                      \
-      gat_flat_bwd_src1_kernel<H, NJ, 0><<<b4, 256, 0, st>>>(                                                 \
-          N, orp, odst, oslot, Y, ldy, attn, out, g_out, F, gpre, gY, ldgy, blk_amax, gy_rows, gR, ldgr, ramax); \
-    else if (u1)                                                                                             \
-      gat_flat_bwd_src1_kernel<H, NJ, 2, 1><<<b4, 256, 0, st>>>(                                              \
-          N, orp, odst, oslot, Y, ldy, attn, out, g_out, F, gpre, gY, ldgy, blk_amax, gy_rows, gR, ldgr, ramax); \
-    else                                                                                                     \
-      gat_flat_bwd_src1_kernel<H, NJ, 2><<<b4, 256, 0, st>>>(                                                 \
-          N, orp, odst, oslot, Y, ldy, attn, out, g_out, F, gpre, gY, ldgy, blk_amax, gy_rows, gR, ldgr, ramax); \
-  } while (0)
+  const FlatSrc1Args a{N, orp, odst, oslot, Y, ldy, attn, out, g_out, F, gpre, gY, ldgy, blk_amax, gy_rows,
+                       gR, ldgr, ramax, st};
   switch (nj) {
-    case 1: MVML_FLAT_SRC1(1); break;
-    case 2: MVML_FLAT_SRC1(2); break;
-    case 3: MVML_FLAT_SRC1(3); break;
-    case 4: MVML_FLAT_SRC1(4); break;
-    case 5: MVML_FLAT_SRC1(5); break;
-    case 6: MVML_FLAT_SRC1(6); break;
-    case 7: MVML_FLAT_SRC1(7); break;
-    case 8: MVML_FLAT_SRC1(8); break;
+    case 1: launch_flat_src1_kernel<H, 1>(mode, u1, a); break;
+    case 2: launch_flat_src1_kernel<H, 2>(mode, u1, a); break;
+    case 3: launch_flat_src1_kernel<H, 3>(mode, u1, a); break;
+    case 4: launch_flat_src1_kernel<H, 4>(mode, u1, a); break;
+    case 5: launch_flat_src1_kernel<H, 5>(mode, u1, a); break;
+    case 6: launch_flat_src1_kernel<H, 6>(mode, u1, a); break;
+    case 7: launch_flat_src1_kernel<H, 7>(mode, u1, a); break;
+    case 8: launch_flat_src1_kernel<H, 8>(mode, u1, a); break;
     default: set_error("gat_agg_bwd: flat-src path needs H F <= 2048"); return MVML_ERR_INVALID;
   }
-#undef MVML_FLAT_SRC1
   int rc = check_launch("gat_flat_bwd_src1_kernel");
   if (rc) return rc;
   gat_mean_bwd_softmax_kernel<H><<<b256, 256, 0, st>>>(N, rp, src, elr, attn, slope, gpre, gY, ldgy, C);
@@ -2309,52 +2227,70 @@ int launch_mean_src(int64_t N, const int32_t* rp, const int32_t* src, const int3
   return launch_rows_amax(N, gy_rows, gy_amax, st);
 }
 
+// One launch of the destination-wave forward: the instance <H, M, NJ, U, SM = sm, LR, SEP>.
+struct DstFwdArgs {
+  int64_t N;
+  const int32_t *rp, *src;
+  const float* Y;
+  int64_t ldy;
+  int F;
+  const float *bias, *elr;
+  float slope;
+  float *attn, *out;
+  uint32_t *blk_amax, *out_rows;
+  const float* R;  // SEP instances only (the others ignore R / ldr: NULL, 0)
+  int64_t ldr;
+  hipStream_t st;
+};
+template <int H, int M, int NJ, int U, bool LR, bool SEP>
+int launch_dst_fwd(bool sm, const DstFwdArgs& a) {
+  const auto kernel = sm ? gat_agg_fwd_dst_kernel<H, M, NJ, U, true, LR, SEP>
+                         : gat_agg_fwd_dst_kernel<H, M, NJ, U, false, LR, SEP>;
+  kernel<<<(unsigned)ceil_div(a.N, 4), 256, 0, a.st>>>(a.N, a.rp, a.src, a.Y, a.ldy, a.F, a.bias, a.elr, a.slope,
+                                                       a.attn, a.out, a.blk_amax, a.out_rows, a.R, a.ldr);
+  return check_launch("gat_agg_fwd_dst_kernel");
+}
+// the flatten modes: M = 0 (ELU) or 2 (no activation)
+template <int H, int NJ, int U, bool LR, bool SEP>
+int launch_dst_fwd_flat(int mode, bool sm, const DstFwdArgs& a) {
+  return mode == 0 ? launch_dst_fwd<H, 0, NJ, U, LR, SEP>(sm, a) : launch_dst_fwd<H, 2, NJ, U, LR, SEP>(sm, a);
+}
+
 template <int H>
 int launch_fwd(int64_t N, const int32_t* groups, int64_t G, const int32_t* rp, const int32_t* src,
                const float* Y, int64_t ldy, int F, const float* bias, float slope, int mode,
                float* out, float* attn, const float* elr, uint32_t* out_amax, uint32_t* out_rows,
                hipStream_t st, bool sep = false, const float* R = nullptr, int64_t ldr = 0) {
+  // with per-row maxima requested, max |out| comes from them afterwards (no per-block atomics)
+  const DstFwdArgs a{N, rp, src, Y, ldy, F, bias, elr, slope, attn, out, out_rows ? nullptr : out_amax, out_rows,
+                     sep ? R : nullptr, sep ? ldr : 0, st};
   // A residual apart from Y's rows, no residual or no bias (mvml_gat_agg_fwd_res): the
   // destination-wave kernel's SEP instances are the one native path, at every shape (head-mean
   // rows past 4 slots, H <= 2 only, take an 8-slot instance); every option value is redirected
   // to them here, before anything is launched (dst_fwd 0 runs as 1: the softmax in the wave).
   if (sep) {
-    const unsigned b4 = (unsigned)ceil_div(N, 4);
     const bool sm = option(MVML_OPT_DST_FWD) != 2;
-    uint32_t* const blk_amax = out_rows ? nullptr : out_amax;
     if (!sm) {
       gat_softmax_dst_kernel<H><<<(unsigned)ceil_div(N * H, 256), 256, 0, st>>>(N, rp, src, elr, slope, attn);
       int rc = check_launch("gat_softmax_dst_kernel");
       if (rc) return rc;
     }
-#define MVML_DST_FWD_SEP(M, NJ, U)                                                                \
-  do {                                                                                            \
-    if (sm)                                                                                       \
-      gat_agg_fwd_dst_kernel<H, M, NJ, U, true, false, true><<<b4, 256, 0, st>>>(                 \
-          N, rp, src, Y, ldy, F, bias, elr, slope, attn, out, blk_amax, out_rows, R, ldr);        \
-    else                                                                                          \
-      gat_agg_fwd_dst_kernel<H, M, NJ, U, false, false, true><<<b4, 256, 0, st>>>(                \
-          N, rp, src, Y, ldy, F, bias, elr, slope, attn, out, blk_amax, out_rows, R, ldr);        \
-  } while (0)
+    int rc = MVML_OK;
     if (mode == 1) {
       const int nj = (int)ceil_div(F / 4, H >= 2 ? 32 : 64);
-      if (nj == 1) MVML_DST_FWD_SEP(1, 1, 4);
-      else if (nj == 2) MVML_DST_FWD_SEP(1, 2, 2);
-      else if (nj == 3) MVML_DST_FWD_SEP(1, 3, 1);
-      else if (nj == 4) MVML_DST_FWD_SEP(1, 4, 2);
-      else if constexpr (H <= 2) MVML_DST_FWD_SEP(1, 8, 1);  // F > 512 (H = 2) / 1024 (H = 1)
+      if (nj == 1) rc = launch_dst_fwd<H, 1, 1, 4, false, true>(sm, a);
+      else if (nj == 2) rc = launch_dst_fwd<H, 1, 2, 2, false, true>(sm, a);
+      else if (nj == 3) rc = launch_dst_fwd<H, 1, 3, 1, false, true>(sm, a);
+      else if (nj == 4) rc = launch_dst_fwd<H, 1, 4, 2, false, true>(sm, a);
+      else if constexpr (H <= 2) rc = launch_dst_fwd<H, 1, 8, 1, false, true>(sm, a);  // F > 512 (H = 2) / 1024 (H = 1)
     } else {
       const int nj = (int)ceil_div(H * F / 4, 64);
-#define MVML_DST_FWD_SEP_F(NJ, U) do { if (mode == 0) MVML_DST_FWD_SEP(0, NJ, U); else MVML_DST_FWD_SEP(2, NJ, U); } while (0)
-      if (nj == 1) MVML_DST_FWD_SEP_F(1, 4);
-      else if (nj == 2) MVML_DST_FWD_SEP_F(2, 4);
-      else if (nj == 3) MVML_DST_FWD_SEP_F(3, 1);
-      else if (nj == 4) MVML_DST_FWD_SEP_F(4, 2);
-      else MVML_DST_FWD_SEP_F(8, 2);
-#undef MVML_DST_FWD_SEP_F
+      if (nj == 1) rc = launch_dst_fwd_flat<H, 1, 4, false, true>(mode, sm, a);
+      else if (nj == 2) rc = launch_dst_fwd_flat<H, 2, 4, false, true>(mode, sm, a);
+      else if (nj == 3) rc = launch_dst_fwd_flat<H, 3, 1, false, true>(mode, sm, a);
+      else if (nj == 4) rc = launch_dst_fwd_flat<H, 4, 2, false, true>(mode, sm, a);
+      else rc = launch_dst_fwd_flat<H, 8, 2, false, true>(mode, sm, a);
     }
-#undef MVML_DST_FWD_SEP
-    int rc = check_launch("gat_agg_fwd_dst_kernel");
     if (rc) return rc;
     return launch_rows_amax(N, out_rows, out_amax, st);
   }
@@ -2364,11 +2300,7 @@ int launch_fwd(int64_t N, const int32_t* groups, int64_t G, const int32_t* rp, c
   // option says: decided here, before anything is launched.
   const bool dst_fits = H * F <= 2048 && (mode != 1 || ceil_div(F / 4, H >= 2 ? 32 : 64) <= 4);
   if (option(MVML_OPT_DST_FWD) && dst_fits) {  // one wave per destination atom, every atom
-    const unsigned b4 = (unsigned)ceil_div(N, 4);
-    const int HF = H * F;
     const bool sm = option(MVML_OPT_DST_FWD) == 1;  // 2: the softmax as its own launch first
-    // with per-row maxima requested, max |out| comes from them afterwards (no per-block atomics)
-    uint32_t* const blk_amax = out_rows ? nullptr : out_amax;
     if (!sm && H == 4) {
       gat_softmax_dst4_kernel<<<(unsigned)ceil_div(N, 256), 256, 0, st>>>(N, rp, src, elr, slope, attn);
       int rc = check_launch("gat_softmax_dst4_kernel");
@@ -2378,69 +2310,37 @@ int launch_fwd(int64_t N, const int32_t* groups, int64_t G, const int32_t* rp, c
       int rc = check_launch("gat_softmax_dst_kernel");
       if (rc) return rc;
     }
-#define MVML_DST_FWD(M, NJ, U)                                                                    \
-  do {                                                                                            \
-    if (sm)                                                                                       \
-      gat_agg_fwd_dst_kernel<H, M, NJ, U, true>                                                   \
-          <<<b4, 256, 0, st>>>(   \
-              N, rp, src, Y, ldy, F, bias, elr, slope, attn, out, blk_amax, out_rows);             \
-    else                                                                                          \
-      gat_agg_fwd_dst_kernel<H, M, NJ, U, false>                                                  \
-          <<<b4, 256, 0, st>>>(  \
-              N, rp, src, Y, ldy, F, bias, elr, slope, attn, out, blk_amax, out_rows);             \
-  } while (0)
     // rows in flight per wave (MVML_OPT_DST_UNR, H = 4 at the GAT widths: tuning A/B)
     const int unr = option(MVML_OPT_DST_UNR);
+    int rc;
     if (mode == 1) {  // mean: half-waves over the heads, lanes over F / 4
       const int nj = (int)ceil_div(F / 4, H >= 2 ? 32 : 64);
-      if (nj == 1) MVML_DST_FWD(1, 1, 4);
-      else if (nj == 2) MVML_DST_FWD(1, 2, 2);
-      else if (nj == 3 && H == 4 && unr == 2) MVML_DST_FWD(1, 3, 2);
-      else if (nj == 3 && H == 4 && unr == 3) MVML_DST_FWD(1, 3, 3);
-      else if (nj == 3 && unr == 6) MVML_DST_FWD(1, 3, 1);  // (6: the residual loaded first)
-      else if (nj == 3 && H == 4) {
-        // one row in flight, the residual loaded after the gather: 90 VGPRs, five waves per SIMD
-        // (residual first: 104, four) — config 5 layer 2 6.35 -> 6.08 ms, config 3 3.66 -> 3.60
-        // (profiles/r05_agg_late_residual_config*.txt)
-        if (sm)
-          gat_agg_fwd_dst_kernel<H, 1, 3, 1, true, true><<<b4, 256, 0, st>>>(
-              N, rp, src, Y, ldy, F, bias, elr, slope, attn, out, blk_amax, out_rows);
-        else
-          gat_agg_fwd_dst_kernel<H, 1, 3, 1, false, true><<<b4, 256, 0, st>>>(
-              N, rp, src, Y, ldy, F, bias, elr, slope, attn, out, blk_amax, out_rows);
-      }
-      else if (nj == 3) MVML_DST_FWD(1, 3, 1);  // one row in flight: fewest registers, most waves
-      else MVML_DST_FWD(1, 4, 2);  // nj == 4 (dst_fits)
+      if (nj == 1) rc = launch_dst_fwd<H, 1, 1, 4, false, false>(sm, a);
+      else if (nj == 2) rc = launch_dst_fwd<H, 1, 2, 2, false, false>(sm, a);
+      else if (nj == 3 && H == 4 && unr == 2) rc = launch_dst_fwd<H, 1, 3, 2, false, false>(sm, a);
+      else if (nj == 3 && H == 4 && unr == 3) rc = launch_dst_fwd<H, 1, 3, 3, false, false>(sm, a);
+      else if (nj == 3 && unr == 6) rc = launch_dst_fwd<H, 1, 3, 1, false, false>(sm, a);  // (6: the residual loaded first)
+      // one row in flight, the residual loaded after the gather: 90 VGPRs, five waves per SIMD
+      // (residual first: 104, four) — config 5 layer 2 6.35 -> 6.08 ms, config 3 3.66 -> 3.60
+      // (profiles/r05_agg_late_residual_config*.txt)
+      else if (nj == 3 && H == 4) rc = launch_dst_fwd<H, 1, 3, 1, true, false>(sm, a);
+      else if (nj == 3) rc = launch_dst_fwd<H, 1, 3, 1, false, false>(sm, a);  // one row in flight: fewest registers, most waves
+      else rc = launch_dst_fwd<H, 1, 4, 2, false, false>(sm, a);  // nj == 4 (dst_fits)
     } else {
-      const int nj = (int)ceil_div(HF / 4, 64);
-#define MVML_DST_FWD_F(NJ, U) do { if (mode == 0) MVML_DST_FWD(0, NJ, U); else MVML_DST_FWD(2, NJ, U); } while (0)
-      if (nj == 1) MVML_DST_FWD_F(1, 4);
-      else if (nj == 2) MVML_DST_FWD_F(2, 4);
-      else if (nj == 3 && H == 4 && unr == 2) MVML_DST_FWD_F(3, 2);
-      else if (nj == 3 && H == 4 && unr == 4) MVML_DST_FWD_F(3, 4);
-      else if (nj == 3 && H == 4 && (unr == 5 || (unr == 0 && sm))) {
-        // late residual (60 VGPRs, eight waves per SIMD instead of six): with the fused softmax
-        // (large molecules) config-5 layer 1 4.90 -> 4.41 ms; the split-softmax form (small
-        // molecules) measured even (profiles/r05_agg_late_residual_flatten_config*.txt)
-#define MVML_DST_FWD_LR(M)                                                                        \
-  do {                                                                                            \
-    if (sm)                                                                                       \
-      gat_agg_fwd_dst_kernel<H, M, 3, 1, true, true><<<b4, 256, 0, st>>>(                         \
-          N, rp, src, Y, ldy, F, bias, elr, slope, attn, out, blk_amax, out_rows);                 \
-    else                                                                                          \
-      gat_agg_fwd_dst_kernel<H, M, 3, 1, false, true><<<b4, 256, 0, st>>>(                        \
-          N, rp, src, Y, ldy, F, bias, elr, slope, attn, out, blk_amax, out_rows);                 \
-  } while (0)
-        if (mode == 0) MVML_DST_FWD_LR(0); else MVML_DST_FWD_LR(2);
-#undef MVML_DST_FWD_LR
-      }
-      else if (nj == 3) MVML_DST_FWD_F(3, 1);  // fewer rows in flight, more waves: faster
-      else if (nj == 4) MVML_DST_FWD_F(4, 2);
-      else MVML_DST_FWD_F(8, 2);
-#undef MVML_DST_FWD_F
+      const int nj = (int)ceil_div(H * F / 4, 64);
+      if (nj == 1) rc = launch_dst_fwd_flat<H, 1, 4, false, false>(mode, sm, a);
+      else if (nj == 2) rc = launch_dst_fwd_flat<H, 2, 4, false, false>(mode, sm, a);
+      else if (nj == 3 && H == 4 && unr == 2) rc = launch_dst_fwd_flat<H, 3, 2, false, false>(mode, sm, a);
+      else if (nj == 3 && H == 4 && unr == 4) rc = launch_dst_fwd_flat<H, 3, 4, false, false>(mode, sm, a);
+      // late residual (60 VGPRs, eight waves per SIMD instead of six): with the fused softmax
+      // (large molecules) config-5 layer 1 4.90 -> 4.41 ms; the split-softmax form (small
+      // molecules) measured even (profiles/r05_agg_late_residual_flatten_config*.txt)
+      else if (nj == 3 && H == 4 && (unr == 5 || (unr == 0 && sm)))
+        rc = launch_dst_fwd_flat<H, 3, 1, true, false>(mode, sm, a);
+      else if (nj == 3) rc = launch_dst_fwd_flat<H, 3, 1, false, false>(mode, sm, a);  // fewer rows in flight, more waves: faster
+      else if (nj == 4) rc = launch_dst_fwd_flat<H, 4, 2, false, false>(mode, sm, a);
+      else rc = launch_dst_fwd_flat<H, 8, 2, false, false>(mode, sm, a);
     }
-#undef MVML_DST_FWD
-    int rc = check_launch("gat_agg_fwd_dst_kernel");
     if (rc) return rc;
     return launch_rows_amax(N, out_rows, out_amax, st);
   }
@@ -2568,30 +2468,15 @@ int launch_bwd(int64_t N, const int32_t* groups, int64_t G, const int32_t* rp, c
   return check_launch("gat_agg_bwd_src_kernel");
 }
 
-#define MVML_VPL_CASES(FN, H, ...)                 \
-  switch (vpl) {                                   \
-    case 1: return FN<H, 1>(__VA_ARGS__);          \
-    case 2: return FN<H, 2>(__VA_ARGS__);          \
-    case 3: return FN<H, 3>(__VA_ARGS__);          \
-    case 4: return FN<H, 4>(__VA_ARGS__);          \
-    case 5: return FN<H, 5>(__VA_ARGS__);          \
-    case 6: return FN<H, 6>(__VA_ARGS__);          \
-    case 7: return FN<H, 7>(__VA_ARGS__);          \
-    case 8: return FN<H, 8>(__VA_ARGS__);          \
-    default: break;                                \
-  }
-
 // need_cols: the columns a Y row must hold (default: the projection-row layout's [Z | R])
 int check_shapes(int H, int F, int mode, int64_t ldy, const void* Y, const char* who, int64_t need_cols = -1) {
-  MVML_REQUIRE(H == 1 || H == 2 || H == 4 || H == 8, "%s: num_heads must be 1, 2, 4 or 8 (got %d)", who, H);
-  MVML_REQUIRE(F > 0 && F % 4 == 0, "%s: out_feats must be a positive multiple of 4 (got %d)", who, F);
-  MVML_REQUIRE(H * F <= 2048, "%s: H*F must be <= 2048 (got %d)", who, H * F);
+  if (int rc = check_heads(H, F, who)) return rc;
   MVML_REQUIRE(ldy < (1 << 20), "%s: leading dimension too large", who);
   MVML_REQUIRE(mode >= 0 && mode <= 2, "%s: bad mode %d", who, mode);
   const int64_t need = need_cols >= 0 ? need_cols : (int64_t)mvml_gat_proj_cols(H, F, mode == 1);
   MVML_REQUIRE(ldy >= need && ldy % 4 == 0, "%s: leading dimension %lld < %lld or not a multiple of 4",
                who, (long long)ldy, (long long)need);
-  MVML_REQUIRE(((uintptr_t)Y & 15) == 0, "%s: tensors must be 16-byte aligned", who);
+  MVML_REQUIRE(aligned16(Y), "%s: tensors must be 16-byte aligned", who);
   return MVML_OK;
 }
 
@@ -2738,8 +2623,7 @@ head_mean_bwd_kernel(int64_t N, int H, int F, const float* __restrict__ gR, int6
 int check_head_mean(int64_t N, int H, int F, const void* a, int64_t lda, int64_t wa, const void* b,
                     int64_t ldb, int64_t wb, const char* who) {
   MVML_REQUIRE(N >= 0 && H > 0 && F > 0 && F % 4 == 0, "%s: H > 0 and F a positive multiple of 4", who);
-  MVML_REQUIRE(lda >= wa && ldb >= wb && lda % 4 == 0 && ldb % 4 == 0 && ((uintptr_t)a & 15) == 0 &&
-                   ((uintptr_t)b & 15) == 0,
+  MVML_REQUIRE(lda >= wa && ldb >= wb && lda % 4 == 0 && ldb % 4 == 0 && aligned16(a) && aligned16(b),
                "%s: rows must be 16-byte aligned (pointers and row strides)", who);
   return MVML_OK;
 }
@@ -2844,9 +2728,9 @@ extern "C" int mvml_gat_agg_fwd_res(int64_t num_nodes, const int32_t* node_group
   int rc = check_shapes(H, F, mode, ldy, Y, "gat_agg_fwd", (int64_t)H * F);
   if (rc) return rc;
   const int RW = mode == 1 ? F : H * F;
-  MVML_REQUIRE(((uintptr_t)out & 15) == 0 && ((uintptr_t)bias & 15) == 0,
+  MVML_REQUIRE(aligned16(out) && aligned16(bias),
                "gat_agg_fwd: out / bias must be 16-byte aligned");
-  MVML_REQUIRE(R == nullptr || (((uintptr_t)R & 15) == 0 && ldr % 4 == 0 && ldr >= RW && ldr < (1 << 20)),
+  MVML_REQUIRE(R == nullptr || (aligned16(R) && ldr % 4 == 0 && ldr >= RW && ldr < (1 << 20)),
                "gat_agg_fwd: R must be 16-byte aligned with a row stride ldr >= %d that is a multiple of 4", RW);
   // the projection-row layout with a bias runs the instances compiled for it; a residual apart
   // from Y, no residual or no bias the SEP ones (launch_fwd)
@@ -2907,10 +2791,10 @@ extern "C" int mvml_gat_agg_bwd_res(int64_t num_nodes, const int32_t* node_group
   // counts in the maxima; apart from them or not formed: the SEP forms (launch_bwd)
   const bool sep = !(gR == gY + H * F && ldgr == ldgy);
   MVML_REQUIRE(elr_col >= (sep ? H * F : H * F + RW) && ldgy >= elr_col + 2 * H && ldgy % 4 == 0 &&
-                   ldgy < (1 << 20) && ((uintptr_t)gY & 15) == 0,
+                   ldgy < (1 << 20) && aligned16(gY),
                "gat_agg_bwd: gY must be 16-byte aligned, its [d el | d er] column %lld past dZ (and dR) and "
                "ldgy >= that + 2H, a multiple of 4", (long long)elr_col);
-  MVML_REQUIRE(gR == nullptr || (((uintptr_t)gR & 15) == 0 && ldgr % 4 == 0 && ldgr >= RW && ldgr < (1 << 20)),
+  MVML_REQUIRE(gR == nullptr || (aligned16(gR) && ldgr % 4 == 0 && ldgr >= RW && ldgr < (1 << 20)),
                "gat_agg_bwd: gR must be 16-byte aligned with a row stride ldgr >= %d that is a multiple of 4", RW);
   const int C = (int)elr_col;
   MVML_REQUIRE(attn != nullptr && elr != nullptr, "gat_agg_bwd: attn / elr from the forward are required");
@@ -2925,12 +2809,14 @@ extern "C" int mvml_gat_agg_bwd_res(int64_t num_nodes, const int32_t* node_group
   hipStream_t st = as_stream(stream);
   float* gpre = static_cast<float*>(workspace);
   const int vpl = (int)ceil_div(H * F, 256);
-  switch (H) {
-    case 1: { MVML_VPL_CASES(launch_bwd, 1, num_nodes, node_groups, num_groups, in_rowptr, in_src, out_rowptr, out_dst, out_inslot, Y, ldy, elr, attn, out, g_out, F, slope, mode, gpre, gY, ldgy, C, gy_amax, gy_row_amax, st, sep, gR, ldgr) break; }
-    case 2: { MVML_VPL_CASES(launch_bwd, 2, num_nodes, node_groups, num_groups, in_rowptr, in_src, out_rowptr, out_dst, out_inslot, Y, ldy, elr, attn, out, g_out, F, slope, mode, gpre, gY, ldgy, C, gy_amax, gy_row_amax, st, sep, gR, ldgr) break; }
-    case 4: { MVML_VPL_CASES(launch_bwd, 4, num_nodes, node_groups, num_groups, in_rowptr, in_src, out_rowptr, out_dst, out_inslot, Y, ldy, elr, attn, out, g_out, F, slope, mode, gpre, gY, ldgy, C, gy_amax, gy_row_amax, st, sep, gR, ldgr) break; }
-    case 8: { MVML_VPL_CASES(launch_bwd, 8, num_nodes, node_groups, num_groups, in_rowptr, in_src, out_rowptr, out_dst, out_inslot, Y, ldy, elr, attn, out, g_out, F, slope, mode, gpre, gY, ldgy, C, gy_amax, gy_row_amax, st, sep, gR, ldgr) break; }
-  }
+  rc = switch_const<1, 2, 4, 8>(H, [&](auto h) {
+    return switch_const<1, 2, 3, 4, 5, 6, 7, 8>(vpl, [&](auto v) {
+      return launch_bwd<decltype(h)::value, decltype(v)::value>(
+          num_nodes, node_groups, num_groups, in_rowptr, in_src, out_rowptr, out_dst, out_inslot, Y, ldy, elr, attn,
+          out, g_out, F, slope, mode, gpre, gY, ldgy, C, gy_amax, gy_row_amax, st, sep, gR, ldgr);
+    });
+  });
+  if (rc != kNoCase) return rc;
   set_error("gat_agg_bwd: unsupported shape");
   return MVML_ERR_INVALID;
 }

@@ -8,7 +8,7 @@
 // 8} is the instance's slot count (the smallest with H F <= 256 NJ); slots past the row are masked
 // (no load, no store).
 // Per-head sums over a row are H per-lane partials finished with the H-value butterfly all-reduce
-// (HeadReduce, as in gat_agg.hip): a fixed shuffle tree, so every result is bitwise repeatable.
+// (HeadReduce, wave_ops.h): a fixed shuffle tree, so every result is bitwise repeatable.
 //
 // Forward, one wave per destination v (xcd_block: an XCD walks one contiguous atom range):
 //   sweep 1  gathers ZL[src_e] for each in-edge (2 rows in flight) and reduces s_e[h]; lane e % 64
@@ -29,34 +29,12 @@
 //   gZL[u] = sum_out(u) (a_e g_rst[w] + d_e) once.
 // No float atomics anywhere; LeakyReLU' at exactly 0 is `slope` (p > 0 ? 1 : slope).
 #include "common.h"
+#include "wave_ops.h"
 
 namespace mvml {
 namespace {
 
-// (the device helpers below restate gat_agg.hip's: that file's instances stay compiled from
-// their own text, bitwise as before)
-__device__ __forceinline__ float rl(float x, int j) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), j));
-}
-__device__ __forceinline__ int rl(int x, int j) { return __builtin_amdgcn_readlane(x, j); }
-
-// a wave re-reads what its own lanes stored (LDS row, spilled scores): order the accesses
-__device__ __forceinline__ void wave_mem_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
-__device__ __forceinline__ float leaky(float x, float slope) { return x > 0.f ? x : x * slope; }
 __device__ __forceinline__ float dleaky(float x, float slope) { return x > 0.f ? 1.f : slope; }
-__device__ __forceinline__ float elu(float x) { return x > 0.f ? x : expm1f(x); }
-__device__ __forceinline__ float4 f4(float a) { return make_float4(a, a, a, a); }
-__device__ __forceinline__ float4 fma4(float a, float4 z, float4 c) {
-  return make_float4(fmaf(a, z.x, c.x), fmaf(a, z.y, c.y), fmaf(a, z.z, c.z), fmaf(a, z.w, c.w));
-}
-__device__ __forceinline__ float4 add4(float4 a, float4 b) {
-  return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
-}
 __device__ __forceinline__ float4 mul4(float4 a, float4 b) {
   return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w);
 }
@@ -65,84 +43,6 @@ __device__ __forceinline__ float4 leaky4(float4 p, float s) {
 }
 __device__ __forceinline__ float4 dleaky4(float4 p, float s) {
   return make_float4(dleaky(p.x, s), dleaky(p.y, s), dleaky(p.z, s), dleaky(p.w, s));
-}
-__device__ __forceinline__ float dot4(float4 a, float4 b) {
-  return __fmaf_rn(a.w, b.w, __fmaf_rn(a.z, b.z, __fmaf_rn(a.y, b.y, __fmul_rn(a.x, b.x))));
-}
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-
-// H wave-uniform per-head values, passed BY VALUE to pick(): through a reference the compiler
-// turns the select chain into one load from a selected address, which keeps the array in memory
-// (LDS, or scratch where the head-mean instances' LDS rows leave no room)
-template <int H>
-struct HeadVals {
-  float v[H];
-};
-template <int H>
-__device__ __forceinline__ float pick(HeadVals<H> a, int h) {
-  float r = a.v[0];
-#pragma unroll
-  for (int k = 1; k < H; ++k) r = (h == k) ? a.v[k] : r;
-  return r;
-}
-template <int H>
-__device__ __forceinline__ void add_at(float (&a)[H], int h, float v) {
-#pragma unroll
-  for (int k = 0; k < H; ++k) a[k] += (h == k) ? v : 0.f;
-}
-
-// All-reduce of H per-lane values over the 64 lanes: a butterfly that halves the value count per
-// step, then finishes the remaining value inside 64/H-lane groups; readlane broadcasts the totals.
-template <int H>
-struct HeadReduce {
-  static constexpr int LOG = H == 1 ? 0 : H == 2 ? 1 : H == 4 ? 2 : 3;
-  template <bool MAX>
-  __device__ static __forceinline__ float op(float a, float b) { return MAX ? fmaxf(a, b) : a + b; }
-  template <bool MAX>
-  __device__ static __forceinline__ void all(float (&v)[H], int lane) {
-    float w[H];
-#pragma unroll
-    for (int h = 0; h < H; ++h) w[h] = v[h];
-    if constexpr (H >= 8) step<MAX, 8>(w, lane, 32);
-    if constexpr (H >= 4) step<MAX, 4>(w, lane, 32 >> (LOG - 2));
-    if constexpr (H >= 2) step<MAX, 2>(w, lane, 32 >> (LOG - 1));
-#pragma unroll
-    for (int m = 32 >> LOG; m >= 1; m >>= 1) w[0] = op<MAX>(w[0], __shfl_xor(w[0], m, 64));
-#pragma unroll
-    for (int h = 0; h < H; ++h)
-      v[h] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(w[0]), h << (6 - LOG)));
-  }
-  template <bool MAX, int N>
-  __device__ static __forceinline__ void step(float (&w)[H], int lane, int mask) {
-    const bool hi = (lane & mask) != 0;
-#pragma unroll
-    for (int i = 0; i < N / 2; ++i) {
-      const float keep = hi ? w[i + N / 2] : w[i];
-      const float send = hi ? w[i] : w[i + N / 2];
-      w[i] = op<MAX>(keep, __shfl_xor(send, mask, 64));
-    }
-  }
-};
-
-// g_rst[v, col .. col+3] from the layer-output gradient (mode 0: ELU'(x) = out + 1 for x <= 0;
-// mode 1: the head mean's grad / H for every head).
-__device__ __forceinline__ float4 grst_of(const float* __restrict__ g_out, const float* __restrict__ out,
-                                          int64_t v, int col, int HF, int F, int H, int mode) {
-  if (mode == 1) {
-    const float4 g = ld4(g_out + v * F + (col % F));
-    const float inv = (float)H;
-    return make_float4(g.x / inv, g.y / inv, g.z / inv, g.w / inv);
-  }
-  float4 g = ld4(g_out + v * HF + col);
-  if (mode == 0) {
-    const float4 o = ld4(out + v * HF + col);
-    g.x *= o.x > 0.f ? 1.f : o.x + 1.f;
-    g.y *= o.y > 0.f ? 1.f : o.y + 1.f;
-    g.z *= o.z > 0.f ? 1.f : o.z + 1.f;
-    g.w *= o.w > 0.f ? 1.f : o.w + 1.f;
-  }
-  return g;
 }
 
 // The column slots of one lane.
@@ -262,7 +162,7 @@ gatv2_fwd_kernel(int64_t N, const int32_t* __restrict__ rowptr, const int32_t* _
     }
     if (spill && lane < cnt) st_heads<H>(attn + (int64_t)(eb + base + lane) * H, s_l);
   }
-  if (spill) wave_mem_sync();
+  if (spill) wave_sync_workgroup_scope();
   // the scores of chunk `base` on the lanes (-inf past the row)
   auto scores = [&](int base, float (&s)[H]) __attribute__((always_inline)) {
     float t[H];
@@ -315,7 +215,7 @@ gatv2_fwd_kernel(int64_t N, const int32_t* __restrict__ rowptr, const int32_t* _
   if constexpr (MEAN) {
     float* row = s_rows + wv * (NJ * 256);
     sl.store(row, acc);
-    wave_mem_sync();
+    wave_sync_workgroup_scope();
     const float* rv = R ? R + v * ldr : nullptr;
     const float invh = (float)H;
     for (int q = 4 * lane; q < F; q += 256) {
@@ -400,7 +300,7 @@ gatv2_bwd_dst_kernel(int64_t N, int64_t apw, const int32_t* __restrict__ rowptr,
       ordered_sum<H>(t, cnt, dot);
       if (spill && lane < cnt) st_heads<H>(gs + (int64_t)(eb + base + lane) * H, ga_l);
     }
-    if (spill) wave_mem_sync();
+    if (spill) wave_sync_workgroup_scope();
     // sweep 2: g_s, gZR[v] and the g_attn partial
     float4 zr[NJ], gzr[NJ];
     sl.load(zr, ZR + v * ldzr);
@@ -510,11 +410,6 @@ add_cols_kernel(int64_t rows, int c4, const float* __restrict__ src, int64_t lds
   st4(dst + r * ldd + c, add4(ld4(dst + r * ldd + c), ld4(src + r * lds + c)));
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-bool row_ok(const void* p, int64_t ld, int64_t width) {
-  return p != nullptr && aligned16(p) && ld % 4 == 0 && ld >= width && ld < (int64_t(1) << 28);
-}
-
 // Two [N, HF] column blocks (row strides lda, ldb) that share no element: apart as whole ranges,
 // or at one pitch with column ranges that do not meet.
 bool blocks_disjoint(const float* a, int64_t lda, const float* b, int64_t ldb, int64_t N, int64_t HF) {
@@ -528,9 +423,7 @@ bool blocks_disjoint(const float* a, int64_t lda, const float* b, int64_t ldb, i
 }
 
 int check_shapes(int H, int F, int mode, const char* who) {
-  MVML_REQUIRE(H == 1 || H == 2 || H == 4 || H == 8, "%s: num_heads must be 1, 2, 4 or 8 (got %d)", who, H);
-  MVML_REQUIRE(F > 0 && F % 4 == 0, "%s: out_feats must be a positive multiple of 4 (got %d)", who, F);
-  MVML_REQUIRE((int64_t)H * F <= 2048, "%s: H*F must be <= 2048 (got %d)", who, H * F);
+  if (int rc = check_heads(H, F, who)) return rc;
   MVML_REQUIRE(mode >= 0 && mode <= 2, "%s: mode must be 0, 1 or 2 (got %d)", who, mode);
   return MVML_OK;
 }
@@ -592,43 +485,23 @@ int launch_bwd(const BwdArgs& a, hipStream_t st) {
   return check_launch("gatv2_bwd_src_kernel");
 }
 
-#define GATV2_DISPATCH(FN, ARGS, ST)                                          \
-  switch (H * 16 + slots_of(H * F)) {                                         \
-    case 1 * 16 + 1: return FN<1, 1>(ARGS, ST);                               \
-    case 1 * 16 + 2: return FN<1, 2>(ARGS, ST);                               \
-    case 1 * 16 + 3: return FN<1, 3>(ARGS, ST);                               \
-    case 1 * 16 + 4: return FN<1, 4>(ARGS, ST);                               \
-    case 1 * 16 + 6: return FN<1, 6>(ARGS, ST);                               \
-    case 1 * 16 + 8: return FN<1, 8>(ARGS, ST);                               \
-    case 2 * 16 + 1: return FN<2, 1>(ARGS, ST);                               \
-    case 2 * 16 + 2: return FN<2, 2>(ARGS, ST);                               \
-    case 2 * 16 + 3: return FN<2, 3>(ARGS, ST);                               \
-    case 2 * 16 + 4: return FN<2, 4>(ARGS, ST);                               \
-    case 2 * 16 + 6: return FN<2, 6>(ARGS, ST);                               \
-    case 2 * 16 + 8: return FN<2, 8>(ARGS, ST);                               \
-    case 4 * 16 + 1: return FN<4, 1>(ARGS, ST);                               \
-    case 4 * 16 + 2: return FN<4, 2>(ARGS, ST);                               \
-    case 4 * 16 + 3: return FN<4, 3>(ARGS, ST);                               \
-    case 4 * 16 + 4: return FN<4, 4>(ARGS, ST);                               \
-    case 4 * 16 + 6: return FN<4, 6>(ARGS, ST);                               \
-    case 4 * 16 + 8: return FN<4, 8>(ARGS, ST);                               \
-    case 8 * 16 + 1: return FN<8, 1>(ARGS, ST);                               \
-    case 8 * 16 + 2: return FN<8, 2>(ARGS, ST);                               \
-    case 8 * 16 + 3: return FN<8, 3>(ARGS, ST);                               \
-    case 8 * 16 + 4: return FN<8, 4>(ARGS, ST);                               \
-    case 8 * 16 + 6: return FN<8, 6>(ARGS, ST);                               \
-    case 8 * 16 + 8: return FN<8, 8>(ARGS, ST);                               \
-  }
-
-int dispatch_fwd(int H, int F, const FwdArgs& a, hipStream_t st) {
-  GATV2_DISPATCH(launch_fwd, a, st)
-  set_error("gatv2_agg_fwd: unsupported shape");
+// launch(h, nj), as std::integral_constant values, for the instance of this shape
+template <typename Fn>
+int dispatch(int H, int F, const char* who, Fn&& launch) {
+  const int rc = switch_const<1, 2, 4, 8>(H, [&](auto h) {
+    return switch_const<1, 2, 3, 4, 6, 8>(slots_of(H * F), [&](auto nj) { return launch(h, nj); });
+  });
+  if (rc != kNoCase) return rc;
+  set_error("%s: unsupported shape", who);
   return MVML_ERR_INVALID;
 }
+int dispatch_fwd(int H, int F, const FwdArgs& a, hipStream_t st) {
+  return dispatch(H, F, "gatv2_agg_fwd",
+                  [&](auto h, auto nj) { return launch_fwd<decltype(h)::value, decltype(nj)::value>(a, st); });
+}
 int dispatch_bwd(int H, int F, const BwdArgs& a, hipStream_t st) {
-  GATV2_DISPATCH(launch_bwd, a, st)
-  set_error("gatv2_agg_bwd: unsupported shape");
-  return MVML_ERR_INVALID;
+  return dispatch(H, F, "gatv2_agg_bwd",
+                  [&](auto h, auto nj) { return launch_bwd<decltype(h)::value, decltype(nj)::value>(a, st); });
 }
 
 }  // namespace

@@ -9,6 +9,7 @@
 // Atoms are accumulated in index order and nothing is added atomically: the outputs are a fixed
 // function of the inputs, bitwise equal run to run.
 #include "common.h"
+#include "wave_ops.h"
 
 namespace mvml {
 namespace {
@@ -18,11 +19,6 @@ namespace {
 // instructions of expf and an IEEE division, in a loop whose time followed its vector
 // instruction count where it followed nothing else ("Weighted-sum-and-max")
 __device__ __forceinline__ float sigm(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ float dot4(float4 a, float4 b) {
-  return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w;
-}
 
 // Rows in flight per wave (the row buffer is 4 NV VGPRs per row).  The backward holds five
 // vectors per column slot where the forward holds four, and takes fewer rows for the occupancy.
@@ -90,7 +86,7 @@ wsum_max_fwd_kernel(int64_t B, int D, const int64_t* __restrict__ node_off, cons
     for (int u = 0; u < U; ++u) {
       float part = 0.f;
 #pragma unroll
-      for (int c = 0; c < NV; ++c) part += dot4(x[u][c], w[c]);
+      for (int c = 0; c < NV; ++c) part += dot4_contract(x[u][c], w[c]);
       sg[u] = sigm(wave_sum(part) + b);
     }
     // one gate store per batch: lane u writes row u's
@@ -184,7 +180,7 @@ wsum_max_bwd_kernel(int64_t B, int D, const int64_t* __restrict__ node_off, cons
     for (int u = 0; u < U; ++u) {
       float part_t = 0.f;
 #pragma unroll
-      for (int c = 0; c < NV; ++c) part_t += dot4(x[u][c], gs[c]);
+      for (int c = 0; c < NV; ++c) part_t += dot4_contract(x[u][c], gs[c]);
       t[u] = wave_sum(part_t);
     }
 #pragma unroll

@@ -9,16 +9,12 @@
 #include <numeric>
 
 #include "common.h"
+#include "wave_ops.h"
 
 namespace mvml {
 namespace {
 
 __device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ float dot4(float4 a, float4 b) {
-  return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w;
-}
 
 __global__ void lstm_cell_fwd_kernel(int64_t B, int D, const float* __restrict__ gp,
                                      const float* __restrict__ b_ih, const float* __restrict__ b_hh,
@@ -137,7 +133,7 @@ seg_fwd_kernel(int64_t B, int D, const int64_t* __restrict__ node_off, const flo
 #pragma unroll
     for (int c = 0; c < NV; ++c) {
       x[c] = ok[c] ? ld4(X + n * D + 4 * (lane + 64 * c)) : make_float4(0, 0, 0, 0);
-      part += dot4(x[c], q[c]);
+      part += dot4_contract(x[c], q[c]);
     }
     const float e = wave_sum(part);
     const float mn = fmaxf(m, e);
@@ -182,7 +178,7 @@ seg_bwd_kernel(int64_t B, int D, const int64_t* __restrict__ node_off, const flo
     q[c] = ok[c] ? ld4(qstar + g * ldq + col) : make_float4(0, 0, 0, 0);
     gr[c] = ok[c] ? ld4(g_qstar + g * ldgq + D + col) : make_float4(0, 0, 0, 0);
     const float4 rr = ok[c] ? ld4(qstar + g * ldq + D + col) : make_float4(0, 0, 0, 0);
-    cpart += dot4(rr, gr[c]);
+    cpart += dot4_contract(rr, gr[c]);
     gq[c] = make_float4(0, 0, 0, 0);
   }
   const float cdot = wave_sum(cpart);  // sum_n alpha_n <x_n, g_r> = <r, g_r>
@@ -193,8 +189,8 @@ seg_bwd_kernel(int64_t B, int D, const int64_t* __restrict__ node_off, const flo
 #pragma unroll
     for (int c = 0; c < NV; ++c) {
       x[c] = ok[c] ? ld4(X + n * D + 4 * (lane + 64 * c)) : make_float4(0, 0, 0, 0);
-      pe += dot4(x[c], q[c]);
-      pa += dot4(x[c], gr[c]);
+      pe += dot4_contract(x[c], q[c]);
+      pa += dot4_contract(x[c], gr[c]);
     }
     const float e = wave_sum(pe);
     const float ga = wave_sum(pa);

@@ -19,6 +19,7 @@
 // C ABI (no Python per step) rather than in a persistent grid; W_hh (2.4 MB per direction)
 // stays L2-resident across the step launches.
 #include "common.h"
+#include "wave_ops.h"
 
 namespace mvml {
 namespace {
@@ -91,7 +92,6 @@ constexpr int kFwdUnits = 4, kFwdWaves = 4;
 constexpr int kBwdUnits = 16, kBwdWaves = 8;
 
 __device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 
 // acc += A (16 x 16 k) B (16 k x 16) for one float4 of each operand per lane: lane l holds
 // A[l % 16][k0 + 4 (l / 16) + s] and B[k0 + 4 (l / 16) + s][l % 16], s = 0..3 (the four MFMA
@@ -457,7 +457,7 @@ extern "C" int mvml_bilstm_pack_rows(int64_t nrows, int64_t t_count, int64_t B, 
   clear_error();
   MVML_REQUIRE(nrows >= 0 && t_count > 0 && B > 0 && cols > 0 && cols % 4 == 0 && ld_tm % 4 == 0 &&
                    ld_pk % 4 == 0 && ld_tm >= cols && ld_pk >= cols && (dir == 0 || dir == 1) &&
-                   ((uintptr_t)tm & 15) == 0 && ((uintptr_t)packed & 15) == 0,
+                   aligned16(tm) && aligned16(packed),
                "bilstm_pack_rows: bad shape / alignment");
   if (nrows == 0) return MVML_OK;
   MVML_REQUIRE(t_count <= 65535, "bilstm_pack_rows: t_count must be <= 65535");
