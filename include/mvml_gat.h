@@ -680,6 +680,50 @@ int mvml_graphnorm_bwd(int64_t G, int D, const int64_t* group_offsets, const flo
                        float* g_mean_scale, void* workspace, size_t workspace_bytes,
                        void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * BatchNorm1d (torch.nn.BatchNorm1d(C) on a 2-D input [M, C], affine, track_running_stats, a
+ * numeric momentum): the normalisation of dgllife 0.3.0's MLPPredictor (GATPredictor /
+ * GATv2Predictor), sized for tall inputs ([65536, 128] molecule rows, [1.75 M, 768] atom rows).
+ *   training != 0:  mean[c] = sum_m x / M;  var_b[c] = sum_m (x - mean)^2 / M (biased);
+ *                   invstd = 1 / sqrt(var_b + eps);  y = (x - mean) invstd weight + bias;
+ *                   running_mean = (1 - momentum) running_mean + momentum mean
+ *                   running_var  = (1 - momentum) running_var + momentum var_b M / (M - 1)
+ *                   num_batches_tracked[0] += 1 (an int64 device scalar; may be NULL)
+ *                   — all inside the kernels: nothing is read back, no other launch is needed.
+ *                   running_mean / running_var may be NULL (not tracked).
+ *   training == 0:  y = (x - running_mean) / sqrt(running_var + eps) weight + bias; nothing is
+ *                   updated, and a row's output depends on that row only (bitwise the same alone
+ *                   and inside a batch).
+ *   save_mean, save_invstd: fp64 [C] outputs of the forward (eval: the running statistics'), the
+ *                   backward's inputs.  weight / bias NULL: 1 / 0.
+ *   backward:       training: g_x = weight invstd / M (M g_y - sum(g_y) - xhat sum(g_y xhat));
+ *                   eval: g_x = g_y weight invstd;  both: g_weight = sum(g_y xhat), g_bias =
+ *                   sum(g_y), xhat = (x - save_mean) save_invstd.  g_x, g_weight, g_bias may each
+ *                   be NULL (not formed).
+ * Statistics, partial sums and the per-element arithmetic run in fp64 (x - mean cancels; as
+ * GraphNorm); inputs and outputs are fp32.  Rows are cut into mvml_batchnorm1d_part_rows(M)
+ * stripes (a function of M alone, non-decreasing, 1 at M = 1, at most 1024) whose fp64 partial
+ * sums go into `workspace` and are added in a fixed order: no float atomics, bitwise repeatable,
+ * and a column's results do not depend on its position.
+ * Any C >= 1 and M >= 1; row pitches ldx, ldy, ldgy, ldgx >= C (pad columns are never read as
+ * data and never written); float4 accesses when C, the pitches and the pointers allow them, a
+ * scalar path otherwise.  Refused with MVML_ERR_INVALID before any launch: M < 1, C < 1, a pitch
+ * < C, training with M == 1 (torch: "Expected more than 1 value per channel when training"),
+ * eps < 0, momentum outside [0, 1]; MVML_ERR_WORKSPACE: fewer than
+ * mvml_batchnorm1d_workspace_size(M, C) bytes (the eval forward uses none).
+ * ------------------------------------------------------------------------------------- */
+int64_t mvml_batchnorm1d_part_rows(int64_t M);
+size_t mvml_batchnorm1d_workspace_size(int64_t M, int C);
+int mvml_batchnorm1d_fwd(int64_t M, int C, const float* x, int64_t ldx, const float* weight,
+                         const float* bias, int training, double momentum, double eps,
+                         float* running_mean, float* running_var, int64_t* num_batches_tracked,
+                         float* y, int64_t ldy, double* save_mean, double* save_invstd,
+                         void* workspace, size_t workspace_bytes, void* stream);
+int mvml_batchnorm1d_bwd(int64_t M, int C, const float* x, int64_t ldx, const float* weight,
+                         int training, const double* save_mean, const double* save_invstd,
+                         const float* g_y, int64_t ldgy, float* g_x, int64_t ldgx, float* g_weight,
+                         float* g_bias, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Small elementwise helpers.  ReLU backward (threshold_backward on the output), times the
  * Dropout scale when a Dropout followed the ReLU (scale = 1 / (1 - p), 1 without one):
  * g_x = g_y * scale * (y > 0).  y is the DROPPED output: a dropped element reads 0, so its

@@ -1088,6 +1088,106 @@ def relu_dropout_(y, p):
     return float(np.float32(1.0 / (1.0 - p)))  # the float the kernel multiplied by
 
 
+class DropoutFunction(torch.autograd.Function):
+    """nn.Dropout(p) anywhere (not only on a ReLU output, where a dropped element reads 0):
+    mvml_dropout_fwd out of place with a seed from dropout_seed(); the backward is the same kernel
+    on g_y with the saved (p, seed) — the mask is a function of (seed, element index) alone, so it
+    is regenerated, not stored.  Use dropout() below: p == 0 (or eval mode) is the identity with
+    no launch."""
+
+    @staticmethod
+    def forward(ctx, x, p, seed=None):
+        _check_cuda_f32(x, "x")
+        if p >= 1.0:
+            raise ValueError("dropout probability must be < 1 on the HIP path")
+        ctx.p = max(float(p), 0.0)
+        if ctx.p == 0.0:  # the identity: nothing launched
+            return x
+        x = _c(x)
+        ctx.seed = dropout_seed() if seed is None else int(seed)
+        y = torch.empty_like(x)
+        call("mvml_dropout_fwd", x.numel(), ptr(x), ptr(y), ctx.p, ctx.seed, _stream(x.device))
+        return y
+
+    @staticmethod
+    def backward(ctx, g_y):
+        if ctx.p == 0.0:
+            return g_y, None, None
+        g_y = _c(g_y)
+        g_x = torch.empty_like(g_y)
+        call("mvml_dropout_fwd", g_y.numel(), ptr(g_y), ptr(g_x), ctx.p, ctx.seed, _stream(g_y.device))
+        return g_x, None, None
+
+
+def dropout(x, p, seed=None):
+    """nn.Dropout(p) in training mode on any float32 GPU tensor (DropoutFunction); p <= 0 returns
+    x itself with nothing launched, p >= 1 is refused as in relu_dropout_."""
+    if p >= 1.0:
+        raise ValueError("dropout probability must be < 1 on the HIP path")
+    if p <= 0.0:
+        return x
+    return DropoutFunction.apply(x, float(p), seed)
+
+
+class BatchNorm1dFunction(torch.autograd.Function):
+    """torch.nn.BatchNorm1d on (M, C) rows (csrc/batchnorm.hip).  Training mode normalises with
+    the batch statistics and updates running_mean, running_var and num_batches_tracked inside
+    the kernel; eval mode normalises with the running statistics.  fp64 statistics save_mean /
+    save_invstd pass from the forward to the backward.  Under data parallelism the batch
+    statistics are per rank, as torch's BatchNorm1d without SyncBatchNorm."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, num_batches_tracked, training, momentum, eps):
+        _check_cuda_f32(x, "x")
+        if x.dim() != 2:
+            raise ValueError("BatchNorm1d: 2-D (M, C) inputs only on the HIP path")
+        if momentum is None:
+            raise ValueError("BatchNorm1d: momentum=None (cumulative average) is not implemented on the HIP path")
+        if not training and (running_mean is None or running_var is None):
+            raise ValueError("BatchNorm1d: eval mode needs running statistics")
+        x = _rows_f32(x)
+        M, C = x.shape
+        dev = x.device
+        if training and M == 1:
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(x.shape)}")
+        y = torch.empty((M, C), dtype=torch.float32, device=dev)
+        save = torch.empty((2, C), dtype=torch.float64, device=dev)
+        wp, wn = (None, 0)
+        if training:
+            wp, wn = _lib.ws_ptr_size(_lib.lib().mvml_batchnorm1d_workspace_size(M, C), dev)
+        weight = None if weight is None else _c(weight)
+        call("mvml_batchnorm1d_fwd", M, C, ptr(x), x.stride(0), ptr(weight), ptr(None if bias is None else _c(bias)),
+             int(bool(training)), float(momentum), float(eps), ptr(running_mean), ptr(running_var),
+             ptr(num_batches_tracked), ptr(y), C, ptr(save[0]), ptr(save[1]), wp, wn, _stream(dev))
+        ctx.save_for_backward(x, weight, save)
+        ctx.training = bool(training)
+        return y
+
+    @staticmethod
+    def backward(ctx, g_y):
+        x, weight, save = ctx.saved_tensors
+        g_y = _rows_f32(g_y)
+        M, C = x.shape
+        dev = x.device
+        g_x = torch.empty((M, C), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
+        g_w = torch.empty(C, dtype=torch.float32, device=dev) if weight is not None else None
+        g_b = torch.empty(C, dtype=torch.float32, device=dev) if ctx.needs_input_grad[2] else None
+        wp, wn = _lib.ws_ptr_size(_lib.lib().mvml_batchnorm1d_workspace_size(M, C), dev)
+        call("mvml_batchnorm1d_bwd", M, C, ptr(x), x.stride(0), ptr(weight), int(ctx.training), ptr(save[0]),
+             ptr(save[1]), ptr(g_y), g_y.stride(0), ptr(g_x), C, ptr(g_w), ptr(g_b), wp, wn, _stream(dev))
+        return g_x, g_w, g_b, None, None, None, None, None, None
+
+
+def batch_norm1d(x, bn):
+    """x through the torch.nn.BatchNorm1d module `bn` (a parameter container: its weight, bias,
+    buffers, eps, momentum and training flag are read; the arithmetic runs in the HIP kernels)."""
+    if bn.momentum is None:
+        raise ValueError("BatchNorm1d: momentum=None (cumulative average) is not implemented on the HIP path")
+    training = bn.training or bn.running_mean is None
+    return BatchNorm1dFunction.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var,
+                                     bn.num_batches_tracked if training else None, training, bn.momentum, bn.eps)
+
+
 class LinearReLUFunction(torch.autograd.Function):
     """nn.Linear + nn.ReLU of GNNModule.fc (model.py:86-87) as one MFMA GEMM with a bias+ReLU
     epilogue, and the nn.Dropout(p) that follows it (model.py:87; p = 0: none) applied in place

@@ -5,7 +5,9 @@ Drop-in replacements, on the MI355X HIP path, for
   * dgl 0.9.1 ``Set2Set`` (model.py:7, 82-84, 92),
   * dgllife 0.3.0 ``WeightAndSum`` / ``WeightedSumAndMax`` (a second readout; not in model.py),
   * torch_geometric 2.2.0 ``GraphNorm`` (model.py:10, 85, 93),
-  * ``GNNModule`` itself (model.py:77-95).
+  * ``GNNModule`` itself (model.py:77-95),
+  * dgllife 0.3.0 ``MLPPredictor`` / ``GATPredictor`` / ``GATv2Predictor`` (the single-view graph
+    classifiers; not in model.py).
 Parameter names/shapes/registration order follow the reference so a ``net_i.pkl``
 ``model_state_dict`` (keys under ``gnn.``) loads unchanged.
 """
@@ -493,3 +495,90 @@ class GNNModule(nn.Module):
         out = self.norm(graph_x, group_offsets=graphs.group_offsets_rows())
         # fc = Linear -> ReLU -> Dropout (model.py:86-87): the Dropout in place on the ReLU output
         return Fn.LinearReLUFunction.apply(out, self.fc[0].weight, self.fc[0].bias, Fn.dropout_p(self.fc[2]))
+
+
+class MLPPredictor(nn.Module):
+    """dgllife.model.model_zoo.mlp_predictor.MLPPredictor (0.3.0; restated, parity with dgllife is
+    unpinned): predict = Sequential(Dropout(dropout), Linear(in_feats, hidden_feats), ReLU(),
+    BatchNorm1d(hidden_feats), Linear(hidden_feats, n_tasks)).  The torch modules are parameter
+    containers only (keys predict.1.*, predict.3.* with BatchNorm1d's three buffers, predict.4.*);
+    forward runs Dropout anywhere -> Linear + ReLU -> BatchNorm1d (csrc/batchnorm.hip; its
+    parameters, buffers, eps, momentum and training flag read from predict[3]) -> Linear on the
+    HIP kernels.  momentum=None (cumulative average) is refused.  Under data parallelism the batch
+    statistics are per rank, as torch's BatchNorm1d without SyncBatchNorm."""
+
+    def __init__(self, in_feats, hidden_feats, n_tasks, dropout=0.):
+        super().__init__()
+        if not 0.0 <= dropout < 1.0:
+            raise ValueError("MLPPredictor: dropout probability must be in [0, 1) on the HIP path")
+        self.predict = nn.Sequential(nn.Dropout(dropout), nn.Linear(in_feats, hidden_feats), nn.ReLU(),
+                                     nn.BatchNorm1d(hidden_feats), nn.Linear(hidden_feats, n_tasks))
+
+    def forward(self, feats):
+        from .fusion import LinearFunction
+        drop, lin1, _, bn, lin2 = self.predict
+        if bn.momentum is None:
+            raise ValueError("MLPPredictor: BatchNorm1d momentum=None (cumulative average) is not implemented")
+        h = Fn.dropout(feats, Fn.dropout_p(drop))
+        h = Fn.LinearReLUFunction.apply(h, lin1.weight, lin1.bias, 0.0)
+        h = Fn.batch_norm1d(h, bn)
+        return LinearFunction.apply(h, lin2.weight, lin2.bias)
+
+
+def _gnn_out_feats(gnn):
+    last = -1
+    return gnn.hidden_feats[last] * gnn.num_heads[last] if gnn.agg_modes[last] == "flatten" else gnn.hidden_feats[last]
+
+
+class GATPredictor(nn.Module):
+    """dgllife.model.model_zoo.gat_predictor.GATPredictor (0.3.0; restated, parity with dgllife is
+    unpinned): gnn = GAT(...) -> readout = WeightedSumAndMax(gnn_out_feats) -> predict =
+    MLPPredictor(2 * gnn_out_feats, predictor_hidden_feats, n_tasks, predictor_dropout);
+    gnn_out_feats = hidden_feats[-1] * num_heads[-1] when the last agg_mode is "flatten", else
+    hidden_feats[-1].  The deprecated classifier_hidden_feats / classifier_dropout override the
+    predictor_* pair when only they are non-default (dgllife's rule).  forward(bg, feats) returns
+    (B, n_tasks) logits.  feat_drops / attn_drops > 0 stay refused by the conv constructors, and a
+    readout width that is no multiple of 4 up to 1024 by WeightAndSum's."""
+
+    def __init__(self, in_feats, hidden_feats=None, num_heads=None, feat_drops=None, attn_drops=None,
+                 alphas=None, residuals=None, agg_modes=None, activations=None, biases=None,
+                 classifier_hidden_feats=128, classifier_dropout=0., n_tasks=1,
+                 predictor_hidden_feats=128, predictor_dropout=0.):
+        super().__init__()
+        if predictor_hidden_feats == 128 and classifier_hidden_feats != 128:
+            predictor_hidden_feats = classifier_hidden_feats
+        if predictor_dropout == 0. and classifier_dropout != 0.:
+            predictor_dropout = classifier_dropout
+        self.gnn = GAT(in_feats=in_feats, hidden_feats=hidden_feats, num_heads=num_heads, feat_drops=feat_drops,
+                       attn_drops=attn_drops, alphas=alphas, residuals=residuals, agg_modes=agg_modes,
+                       activations=activations, biases=biases)
+        self.gnn_out_feats = _gnn_out_feats(self.gnn)
+        self.readout = WeightedSumAndMax(self.gnn_out_feats)
+        self.predict = MLPPredictor(2 * self.gnn_out_feats, predictor_hidden_feats, n_tasks, predictor_dropout)
+
+    def forward(self, bg, feats):
+        node_feats = self.gnn(bg, feats)
+        return self.predict(self.readout(bg, node_feats))
+
+
+class GATv2Predictor(nn.Module):
+    """dgllife.model.model_zoo.gatv2_predictor.GATv2Predictor (0.3.0; restated, parity with
+    dgllife is unpinned): the GATPredictor stack over GATv2, with nn.GATv2's own argument order:
+    gnn = GATv2(...) -> WeightedSumAndMax(gnn_out_feats) -> MLPPredictor(2 * gnn_out_feats,
+    predictor_out_feats, n_tasks, predictor_dropout)."""
+
+    def __init__(self, in_feats, hidden_feats=None, num_heads=None, feat_drops=None, attn_drops=None,
+                 alphas=None, residuals=None, activations=None, allow_zero_in_degree=False, biases=None,
+                 share_weights=None, agg_modes=None, n_tasks=1, predictor_out_feats=128, predictor_dropout=0.):
+        super().__init__()
+        self.gnn = GATv2(in_feats=in_feats, hidden_feats=hidden_feats, num_heads=num_heads, feat_drops=feat_drops,
+                         attn_drops=attn_drops, alphas=alphas, residuals=residuals, activations=activations,
+                         allow_zero_in_degree=allow_zero_in_degree, biases=biases, share_weights=share_weights,
+                         agg_modes=agg_modes)
+        self.gnn_out_feats = _gnn_out_feats(self.gnn)
+        self.readout = WeightedSumAndMax(self.gnn_out_feats)
+        self.predict = MLPPredictor(2 * self.gnn_out_feats, predictor_out_feats, n_tasks, predictor_dropout)
+
+    def forward(self, bg, feats):
+        node_feats = self.gnn(bg, feats)
+        return self.predict(self.readout(bg, node_feats))
