@@ -2692,8 +2692,7 @@ extern "C" int mvml_gat_proj_fwd(int64_t num_nodes, const float* X, int64_t ldx,
       static_cast<uint8_t*>(workspace) +
       carve_size((size_t)num_nodes * 2 * (H * F / (1 << proj_logw(F))) * sizeof(float)));
   int rc = gemm_proj_epi(algo, num_nodes, C, K, X, ldx, Wcat, ldw, Y, ldy,
-                         attn_lr, H * F, proj_logw(F), part, amax_ws, amax_x, amax_w, w_planes,
-                         w_plane, st);
+                         attn_lr, H * F, proj_logw(F), part, amax_ws, amax_x, amax_w, w_planes, st);
   if (rc) return rc;
   const int W = 1 << proj_logw(F);
   const unsigned blocks = (unsigned)ceil_div(num_nodes * 2 * H, 256);

@@ -1,6 +1,8 @@
-// Shared pieces of the split-fp16 GEMM kernels (gemm_f32.hip, gemm_planes.hip): operand types,
-// the scaled split-fp16 split, operand / per-row maxima, and the LDS epilogue of a wave's 32x32
-// accumulator tiles (bias, beta, ReLU / ELU / ELU', LSTM cell, folded output maxima).
+// Shared pieces of the split-fp16 GEMM kernels (gemm_f32.hip: the tile kernels; gemm_smallk.hip:
+// the small-K memory kernel; gemm_prep.hip: maxima, pre-splits, column sums; gemm_planes.hip):
+// operand types, the scaled split-fp16 split, operand / per-row maxima, the LDS epilogue of a
+// wave's 32x32 accumulator tiles (bias, beta, ReLU / ELU / ELU', LSTM cell, folded output
+// maxima), and the host launchers the files call across.
 #pragma once
 #include <type_traits>
 #include <utility>
@@ -76,7 +78,7 @@ __device__ __forceinline__ float pow2f(int k) { return __uint_as_float((uint32_t
 struct AmaxPtrs {
   const uint32_t* a = nullptr;
   const uint32_t* b = nullptr;
-  int64_t b_plane = 0;  // BPS: elements from B's high fp16 plane to its low plane
+  int64_t reserved = 0;  // (the removed two-plane B image's plane offset: keeps the kernels' argument layout)
   const uint32_t* a_rows = nullptr;
   // gemm_f32_kernel<..., RS = true> (k-major A): fp32 sums over k of every op(A) row, as
   // [2 S][M] partials (split s, wave column half h -> row 2 s + h); mvml_gemm_f16x2_amax_colsum
@@ -425,4 +427,21 @@ typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 }  // namespace
+
+// gemm_prep.hip: |max| bits of a rows x cols matrix into *out (accumulate: folded into the stored
+// bits); the 128x128 kernel's interleaved pre-split of a K-contiguous operand (ld K, K % 8 == 0);
+// the fixed-order sum of S column-sum partials (colsum_final_kernel), checked as `what`.
+int absmax_launch(int64_t rows, int64_t cols, const float* P, int64_t ld, uint32_t* out,
+                  bool accumulate, hipStream_t st);
+int split_il_launch(int64_t rows, int64_t K, const float* P, const uint32_t* amax, float* out,
+                    hipStream_t st);
+int colsum_final_launch(int64_t N, int S, const float* part, int64_t ld, float alpha, float beta,
+                        float* out, hipStream_t st, const char* what);
+// gemm_smallk.hip: the shapes the small-K kernel takes, and its launch.
+bool smallk_fits(int b_kmajor, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda,
+                 const float* Bp, int64_t ldb, float beta, int act, const float* C, int64_t ldc);
+int smallk_launch(int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B,
+                  int64_t ldb, bool il4, const uint32_t* a_rows, const uint32_t* amax_b,
+                  const float* bias, int act, float* C, int64_t ldc, hipStream_t st);
+
 }  // namespace mvml

@@ -241,18 +241,6 @@ struct Stager {
           : "memory");
     }
   }
-
-  // Fragment of k-group g (8 k values): element s of the result is the operand value at
-  // row `row`, k = 8g + 4h + s, where h = lane >> 5 — the k order both operands share.
-  __device__ static __forceinline__ float4 frag(const float* lds_tile, int row, int g, int h) {
-    if (!KMAJ) {
-      const int slot = (2 * g + h) ^ swz(row);
-      return *reinterpret_cast<const float4*>(lds_tile + row * BKT + slot * 4);
-    } else {
-      const float* p = lds_tile + (8 * g + 4 * h) * 128 + row;
-      return make_float4(p[0], p[128], p[256], p[384]);
-    }
-  }
 };
 
 __device__ __forceinline__ float comp(const float4& v, int s) {
@@ -594,66 +582,65 @@ gemm_f32_kernel(int64_t M, int64_t N, int64_t K, const float* __restrict__ A, in
       // there (VALU beside the matrix pipe); 4 sub-tiles x 6 bf16 MFMAs per step
       float4 f[2][4][2];  // [step][a0, a1, b0, b1][lo, hi]
       bf16x8 pa[2][3], pb[2][3];
-#define MVML_FRAGS8(T)                                                          \
-      SA::frag8_asm(sa_b, ra0, 2 * (T) + lk, f[T][0][0], f[T][0][1]);           \
-      SA::frag8_asm(sa_b, ra1, 2 * (T) + lk, f[T][1][0], f[T][1][1]);           \
-      SB::frag8_asm(sb_b, rb0, 2 * (T) + lk, f[T][2][0], f[T][2][1]);           \
-      SB::frag8_asm(sb_b, rb1, 2 * (T) + lk, f[T][3][0], f[T][3][1]);
-#define MVML_SPLIT(T)                                                           \
-      split3(f[T][0][0], f[T][0][1], pa[0][0], pa[0][1], pa[0][2]);             \
-      split3(f[T][1][0], f[T][1][1], pa[1][0], pa[1][1], pa[1][2]);             \
-      split3(f[T][2][0], f[T][2][1], pb[0][0], pb[0][1], pb[0][2]);             \
-      split3(f[T][3][0], f[T][3][1], pb[1][0], pb[1][1], pb[1][2]);
-#define MVML_MFMAS3()                                                           \
-      acc[0][0] = mfma_x3(pa[0], pb[0], acc[0][0]);                             \
-      acc[0][1] = mfma_x3(pa[0], pb[1], acc[0][1]);                             \
-      acc[1][0] = mfma_x3(pa[1], pb[0], acc[1][0]);                             \
-      acc[1][1] = mfma_x3(pa[1], pb[1], acc[1][1]);
-      MVML_FRAGS8(0)
-      MVML_FRAGS8(1)
+      auto frags8 = [&](int T) __attribute__((always_inline)) {
+        SA::frag8_asm(sa_b, ra0, 2 * T + lk, f[T][0][0], f[T][0][1]);
+        SA::frag8_asm(sa_b, ra1, 2 * T + lk, f[T][1][0], f[T][1][1]);
+        SB::frag8_asm(sb_b, rb0, 2 * T + lk, f[T][2][0], f[T][2][1]);
+        SB::frag8_asm(sb_b, rb1, 2 * T + lk, f[T][3][0], f[T][3][1]);
+      };
+      auto split_mfmas = [&](int T) __attribute__((always_inline)) {
+        split3(f[T][0][0], f[T][0][1], pa[0][0], pa[0][1], pa[0][2]);
+        split3(f[T][1][0], f[T][1][1], pa[1][0], pa[1][1], pa[1][2]);
+        split3(f[T][2][0], f[T][2][1], pb[0][0], pb[0][1], pb[0][2]);
+        split3(f[T][3][0], f[T][3][1], pb[1][0], pb[1][1], pb[1][2]);
+        acc[0][0] = mfma_x3(pa[0], pb[0], acc[0][0]);
+        acc[0][1] = mfma_x3(pa[0], pb[1], acc[0][1]);
+        acc[1][0] = mfma_x3(pa[1], pb[0], acc[1][0]);
+        acc[1][1] = mfma_x3(pa[1], pb[1], acc[1][1]);
+      };
+      frags8(0);
+      frags8(1);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);
-      MVML_SPLIT(0)
-      MVML_MFMAS3()
-      MVML_SPLIT(1)
-      MVML_MFMAS3()
+      split_mfmas(0);
+      split_mfmas(1);
       __builtin_amdgcn_sched_barrier(0);
-#undef MVML_FRAGS8
-#undef MVML_SPLIT
-#undef MVML_MFMAS3
     } else {
-    float4 fa0[2], fa1[2], fb0[2], fb1[2];  // [register set] x (sub-tile 0 / 1)
-#define MVML_FRAGS(G, SET)                                  \
-    SA::template frag_asm<G>(sa_b, ra0, lk, fa0[SET]);      \
-    SA::template frag_asm<G>(sa_b, ra1, lk, fa1[SET]);      \
-    SB::template frag_asm<G>(sb_b, rb0, lk, fb0[SET]);      \
-    SB::template frag_asm<G>(sb_b, rb1, lk, fb1[SET]);
-#define MVML_MFMAS(SET)                                                                                      \
-    _Pragma("unroll") for (int s = 0; s < 4; ++s) {                                                          \
-      acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(comp(fa0[SET], s), comp(fb0[SET], s), acc[0][0], 0, 0, 0); \
-      acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(comp(fa0[SET], s), comp(fb1[SET], s), acc[0][1], 0, 0, 0); \
-      acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(comp(fa1[SET], s), comp(fb0[SET], s), acc[1][0], 0, 0, 0); \
-      acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(comp(fa1[SET], s), comp(fb1[SET], s), acc[1][1], 0, 0, 0); \
-    }
-#define MVML_WAIT_LDS()                                  \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   \
-    __builtin_amdgcn_sched_barrier(0);
-    MVML_FRAGS(0, 0)
-    MVML_WAIT_LDS()
-    MVML_FRAGS(1, 1)
-    MVML_MFMAS(0)
-    MVML_WAIT_LDS()
-    MVML_FRAGS(2, 0)
-    MVML_MFMAS(1)
-    MVML_WAIT_LDS()
-    MVML_FRAGS(3, 1)
-    MVML_MFMAS(0)
-    MVML_WAIT_LDS()
-    MVML_MFMAS(1)
-    __builtin_amdgcn_sched_barrier(0);
-#undef MVML_FRAGS
-#undef MVML_MFMAS
-#undef MVML_WAIT_LDS
+      float4 fa0[2], fa1[2], fb0[2], fb1[2];  // [register set] x (sub-tile 0 / 1)
+      auto frags = [&](auto G, int set) __attribute__((always_inline)) {
+        constexpr int g = decltype(G)::value;
+        SA::template frag_asm<g>(sa_b, ra0, lk, fa0[set]);
+        SA::template frag_asm<g>(sa_b, ra1, lk, fa1[set]);
+        SB::template frag_asm<g>(sb_b, rb0, lk, fb0[set]);
+        SB::template frag_asm<g>(sb_b, rb1, lk, fb1[set]);
+      };
+      auto mfmas = [&](int set) __attribute__((always_inline)) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+          acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(comp(fa0[set], s), comp(fb0[set], s), acc[0][0], 0, 0, 0);
+          acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(comp(fa0[set], s), comp(fb1[set], s), acc[0][1], 0, 0, 0);
+          acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(comp(fa1[set], s), comp(fb0[set], s), acc[1][0], 0, 0, 0);
+          acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(comp(fa1[set], s), comp(fb1[set], s), acc[1][1], 0, 0, 0);
+        }
+      };
+      auto wait_lds = []() __attribute__((always_inline)) {
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+      };
+      using std::integral_constant;
+      frags(integral_constant<int, 0>{}, 0);
+      wait_lds();
+      frags(integral_constant<int, 1>{}, 1);
+      mfmas(0);
+      wait_lds();
+      frags(integral_constant<int, 2>{}, 0);
+      mfmas(1);
+      wait_lds();
+      frags(integral_constant<int, 3>{}, 1);
+      mfmas(0);
+      wait_lds();
+      mfmas(1);
+      __builtin_amdgcn_sched_barrier(0);
     }
   }
 
@@ -812,13 +799,10 @@ struct SplitStager {
   }
 };
 
-#ifndef MVML_X3S_WAVES
-#define MVML_X3S_WAVES 2
-#endif
 // H2: scaled split-fp16 planes (two per operand, three fp16 MFMAs per fragment pair; scales from
 // amax) instead of split-bf16 (three planes, six MFMAs) — the skinny plan of the f16x2 algorithm.
 template <bool AK, bool BKM, int EPI_LOGW = -1, bool H2 = false>
-__global__ void __launch_bounds__(kThreads, MVML_X3S_WAVES)  // 2 workgroups per CU
+__global__ void __launch_bounds__(kThreads, 2)  // 2 workgroups per CU
 gemm_x3s_kernel(int64_t M, int64_t N, int64_t K, const float* __restrict__ A, int64_t lda,
                 const float* __restrict__ B, int64_t ldb, const float* __restrict__ bias,
                 float beta, int act, float* __restrict__ C, int64_t ldc, int64_t k_split,
@@ -1065,33 +1049,6 @@ struct XOp {
 };
 
 
-#ifndef MVML_X3W_WAVES
-#define MVML_X3W_WAVES 2
-#endif
-#ifndef MVML_X3W_LDSEPI
-#define MVML_X3W_LDSEPI 1
-#endif
-#ifndef MVML_X3W_SGB
-#define MVML_X3W_SGB 0
-#endif
-#ifndef MVML_X3W_PF2
-#define MVML_X3W_PF2 0
-#endif
-#ifndef MVML_X3W_STAGGER
-#define MVML_X3W_STAGGER 0
-#endif
-#ifndef MVML_X3W_SGB_V
-#define MVML_X3W_SGB_V 3
-#endif
-#ifndef MVML_H2_SGB
-#define MVML_H2_SGB 1
-#endif
-#ifndef MVML_H2_KS
-#define MVML_H2_KS (MVML_H2_SGB ? 1 : 2)
-#endif
-#ifndef MVML_X3W_SGB_V2
-#define MVML_X3W_SGB_V2 3
-#endif
 // FAST (host-checked: both operands 16-B aligned rows, K-major row counts % 4 == 0): whole
 // stages by unguarded loads from clamped rows, the K tail as one guarded stage; !FAST: every
 // stage guarded.
@@ -1106,7 +1063,7 @@ struct XOp {
 // spill reload inside the main loop costs a vmcnt drain per stage).
 template <bool AK, bool BKM, int EPI_LOGW = -1, bool FAST = true, int NP = 3, int BPS = 0,
           bool ROWS = false, bool EX = false>
-__global__ void __launch_bounds__(kXThreads, MVML_X3W_WAVES)  // one workgroup per CU
+__global__ void __launch_bounds__(kXThreads, 2)  // one workgroup per CU
 gemm_x3w_kernel(int64_t M, int64_t N, int64_t K, const float* __restrict__ A, int64_t lda,
                 const float* __restrict__ B, int64_t ldb, const float* __restrict__ bias,
                 float beta, int act, float* __restrict__ C, int64_t ldc, int64_t k_split,
@@ -1134,16 +1091,12 @@ gemm_x3w_kernel(int64_t M, int64_t N, int64_t K, const float* __restrict__ A, in
   using OA = XOp<AK, NP>;
   using OB = XOp<BKM, NP>;
   static_assert(!BPS || (NP == 2 && FAST), "pre-split B: split-fp16 fast path only");
-  // B piece at float-indexed address p: fp32 values, or
-  // (BPS 2) the interleaved image's 16-B piece [4 high | 4 low] (mvml_split_f16x2_il4: the same
-  // float indexing as the fp32 operand, one load per piece like fp32)
-  auto ldb4 = [&](const float* p) -> float4 {
-    if constexpr (BPS == 2) {
-      return *reinterpret_cast<const float4*>(p);
-    } else {
-      return *reinterpret_cast<const float4*>(p);
-    }
-  };
+  // A B piece is one float4 load either way: fp32 values, or (BPS 2) the interleaved image's
+  // 16-B piece [4 high | 4 low] (mvml_split_f16x2_il4: the fp32 operand's own float indexing).
+  // (A lambda, and below the never-used LOAD == 2 case and `KS == 1` in the interleaved body's
+  // condition: what the stage lambdas capture, in which order, moves the compiler's register
+  // allocation — without them the kernels' instructions differ; tools/codeobj_diff.py.)
+  auto ldb4 = [&](const float* p) -> float4 { return *reinterpret_cast<const float4*>(p); };
   // NP = 2: operand scales from the |max| bits of A and B (per-row A maxima: amax.a_rows, a
   // shift per A row of the tile in rsh — host: K-contiguous A)
   static_assert(!ROWS || (NP == 2 && !AK), "per-row A maxima: split-fp16, K-contiguous A");
@@ -1164,9 +1117,9 @@ gemm_x3w_kernel(int64_t M, int64_t N, int64_t K, const float* __restrict__ A, in
   // loop: the sched_group_barrier interleave, placed for the split of both operands, measured
   // slower there than two plain sub-stages per barrier (L2 forward 17.5 -> 16.8 ms, dX 15.7 ->
   // 15.5, LSTM gates 0.523 -> 0.514; profiles/r04_gemm_schedule_variants.txt), so it is kept
-  // for the in-loop split of both operands only
-  constexpr bool H2SGB = MVML_H2_SGB && BPS == 0;
-  constexpr int KS = (NP == 2) ? (H2SGB ? MVML_H2_KS : 2) : 1;
+  // for the in-loop split of both operands only (H2SGB: one sub-stage per barrier, body_h2)
+  constexpr bool H2SGB = NP == 2 && BPS == 0;
+  constexpr int KS = (NP == 2 && !H2SGB) ? 2 : 1;
   constexpr int kSub = OA::kBytes + OB::kBytes;
   constexpr int kStage = KS * kSub;
   // double-buffered stages; the LDS epilogue reuses the space (8 waves x 32 rows x kEpiLd)
@@ -1308,14 +1261,12 @@ gemm_x3w_kernel(int64_t M, int64_t N, int64_t K, const float* __restrict__ A, in
         OB::split_store(op + OA::kBytes, tid, vb[s], s_b);
     }
   };
-#ifndef MVML_X3W_PRIO
-#define MVML_X3W_PRIO 1
-#endif
   // One 16-deep stage: fragments of stage t from LDS buffer t & 1; with STAGE, split + store
-  // stage t+1 (in va / vb) into the other buffer; LOAD: 0 none, 1 fast, 2 guarded load of t+2.
-  // Each (STAGE, LOAD) is its own straight-line body: no control flow around the accumulators.
+  // stage t+1 (in va / vb) into the other buffer; LOAD of stage t+2: 0 none, 1 fast, 2 guarded
+  // (no caller), 3 masked (the stage that may hold the K tail).  Each (STAGE, LOAD) is its own
+  // straight-line body: no control flow around the accumulators.  Two schedules: the interleaved
+  // one for H2SGB stages that stage, the plain one (from stage_and_load on) for everything else.
   auto body = [&](int64_t t, auto STAGE, auto LOAD) {
-#if MVML_X3W_SGB || MVML_H2_SGB
     const uint8_t* sa = lds + (t & 1) * kStage;
     const uint8_t* sb = sa + OA::kBytes;
     bf16x8 fb[2][NP];
@@ -1323,13 +1274,18 @@ gemm_x3w_kernel(int64_t M, int64_t N, int64_t K, const float* __restrict__ A, in
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int p = 0; p < NP; ++p) fb[j][p] = OB::frag(sb, p, wn * 64 + 32 * j, lane);
-    if constexpr (MVML_X3W_SGB && decltype(STAGE)::value && NP == 3) {
-      // Interleaved schedule: every fragment of stage t is read from LDS FIRST (so the split's
-      // LDS writes into the other buffer, which the compiler cannot prove disjoint, do not pin
-      // the reads behind them), then the split of stage t+1 (VALU + LDS writes) and the global
-      // loads of stage t+2 ride in the MFMA stream of stage t (an MFMA leaves 24 of its 32 issue
-      // cycles to other instructions), instead of running as a VALU-only phase in front of it
-      // while the SIMD's matrix pipe idles (both waves of a SIMD reach that phase together).
+    if constexpr (H2SGB && decltype(STAGE)::value && KS == 1) {
+      // The interleaved body (split-fp16 with both operands split in the loop, the default
+      // there; a stage that also stages the next one): every fragment of stage t is read from LDS
+      // FIRST (so the split's LDS writes into the other buffer, which the compiler cannot prove
+      // disjoint, do not pin the reads behind them), then the split of stage t+1 (VALU + LDS
+      // writes) and the global loads of stage t+2 ride in the MFMA stream of stage t (an MFMA
+      // leaves 24 of its 32 issue cycles to other instructions), instead of running as a
+      // VALU-only phase in front of it while the SIMD's matrix pipe idles (both waves of a SIMD
+      // reach that phase together).  The 24 MFMAs carry the 32 split VALU (8 per float4: 2
+      // pk_mul, 2 cvt_pk, 4 fma_mix), 8 LDS plane writes and the 4 global loads — measured
+      // +3 / +7 / +3 % on the L2 forward / dX / dW shapes over two sub-stages per barrier without
+      // the interleave (tools/gemm_bench.py)
       bf16x8 fa[4][NP];
 #pragma unroll
       for (int i = 0; i < 4; ++i)
@@ -1344,46 +1300,11 @@ gemm_x3w_kernel(int64_t M, int64_t N, int64_t K, const float* __restrict__ A, in
 #pragma unroll
         for (int j = 0; j < 2; ++j) acc[i][j] = mfma_np<NP>(fa[i], fb[j], acc[i][j]);
       // 0x8 MFMA, 0x2 VALU, 0x100 DS read, 0x200 DS write, 0x20 VMEM read
-      __builtin_amdgcn_sched_group_barrier(0x100, 6 * NP, 0);  // fb + fa[0] + fa[1]
-#pragma unroll
-      for (int k = 0; k < 24; ++k) {
-        __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x2, MVML_X3W_SGB_V, 0);
-        if (k % 4 == 3) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-        if (k == 2) __builtin_amdgcn_sched_group_barrier(0x100, 2 * NP, 0);  // fa[2] + fa[3]
-      }
-      __builtin_amdgcn_sched_group_barrier(0x20, 4, 0);  // next stage's global loads
-#pragma unroll
-      for (int k = 0; k < 24; ++k) {
-        __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x2, 1, 0);
-      }
-      __syncthreads();
-      return;
-    }
-    if constexpr (H2SGB && decltype(STAGE)::value && NP == 2 && KS == 1) {
-      // the same interleave for split-fp16 (default): 24 MFMAs carry the 32 split VALU (8 per
-      // float4: 2 pk_mul, 2 cvt_pk, 4 fma_mix), 8 LDS plane writes and the 4 global loads —
-      // measured +3 / +7 / +3 % on the L2 forward / dX / dW shapes over two sub-stages per
-      // barrier without the interleave (tools/gemm_bench.py)
-      bf16x8 fa[4][NP];
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int p = 0; p < NP; ++p) fa[i][p] = OA::frag(sa, p, wm * 128 + 32 * i, lane);
-      stage((t + 1) & 1);
-      if constexpr (decltype(LOAD)::value == 1) load_fast();
-      if constexpr (decltype(LOAD)::value == 2) load_guarded(t + 2);
-      if constexpr (decltype(LOAD)::value == 3) load_masked(t + 2);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = mfma_np<NP>(fa[i], fb[j], acc[i][j]);
       __builtin_amdgcn_sched_group_barrier(0x100, 4 * NP, 0);  // fb + fa[0]
 #pragma unroll
       for (int k = 0; k < 24; ++k) {
         __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x2, MVML_X3W_SGB_V2, 0);
+        __builtin_amdgcn_sched_group_barrier(0x2, 3, 0);
         if (k % 3 == 2) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
         if (k == 1 || k == 4 || k == 7) __builtin_amdgcn_sched_group_barrier(0x100, NP, 0);  // fa[1..3]
         if (k == 12) __builtin_amdgcn_sched_group_barrier(0x20, 4, 0);
@@ -1391,25 +1312,16 @@ gemm_x3w_kernel(int64_t M, int64_t N, int64_t K, const float* __restrict__ A, in
       __syncthreads();
       return;
     }
-#endif
     auto stage_and_load = [&]() {
       if constexpr (decltype(STAGE)::value) stage((t + 1) & 1);
       if constexpr (decltype(LOAD)::value == 1) load_fast();
       if constexpr (decltype(LOAD)::value == 2) load_guarded(t + 2);
       if constexpr (decltype(LOAD)::value == 3) load_masked(t + 2);
     };
-#if MVML_X3W_STAGGER
-    // Stagger: waves 0-3 (one per SIMD) split stage t+1 BEFORE their MFMAs of stage t, waves
-    // 4-7 (the SIMD partners) AFTER theirs, so each SIMD's matrix pipe runs one wave's MFMAs
-    // while its partner does the VALU split, instead of both splitting together behind the
-    // barrier.  The branches are wave-uniform and leave the accumulators alone.
-    if (wid < 4) stage_and_load();
-#else
     stage_and_load();
-#endif
     // s_setprio around the MFMA block: measured +1-3 % slower for split-fp16 (NP = 2), kept for
     // the split-bf16 / bf16 instantiations
-    constexpr bool kPrio = MVML_X3W_PRIO && NP != 2;
+    constexpr bool kPrio = NP != 2;
     if (kPrio) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
@@ -1430,90 +1342,14 @@ gemm_x3w_kernel(int64_t M, int64_t N, int64_t K, const float* __restrict__ A, in
       }
     }
     if (kPrio) __builtin_amdgcn_s_setprio(0);
-#if MVML_X3W_STAGGER
-    if (wid >= 4) stage_and_load();
-#endif
     __syncthreads();
   };
   using T_ = std::true_type;
   using F_ = std::false_type;
   using L0 = std::integral_constant<int, 0>;
   using L1 = std::integral_constant<int, 1>;
-  using L2 = std::integral_constant<int, 2>;
-#if MVML_X3W_PF2
-  if constexpr (FAST && KS == 1 && BPS == 0) {
-    // Prefetch distance 2: tile k's fp32 values live in register set k % 2 from their load (in
-    // body k - 3) to their split (in body k - 1), so a global load has two whole stages to land
-    // instead of one (the loads of a stage are issued right after the split that frees the set).
-    using S0 = std::integral_constant<int, 0>;
-    using S1 = std::integral_constant<int, 1>;
-    using LM = std::integral_constant<int, 3>;
-    float4 ra[2][2], rb[2][2];
-    auto ldf = [&](auto SET) {
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        ra[decltype(SET)::value][i] = *reinterpret_cast<const float4*>(pa[i]);
-        rb[decltype(SET)::value][i] = *reinterpret_cast<const float4*>(pb[i]);
-        pa[i] += sa_step;
-        pb[i] += sb_step;
-      }
-    };
-    auto ldm = [&](auto SET, int64_t k) {  // tile k, the K tail: as load_masked
-      load_masked_into(k, ra[decltype(SET)::value], rb[decltype(SET)::value]);
-    };
-    auto stg = [&](auto SET, int buf) {
-      OA::split_store(lds + buf * kStage, tid, ra[decltype(SET)::value], sa_i);
-      OB::split_store(lds + buf * kStage + OA::kBytes, tid, rb[decltype(SET)::value], s_b);
-    };
-    auto body2 = [&](int64_t t, auto SET, auto STAGE, auto LOAD) {
-      const uint8_t* sa = lds + (t & 1) * kStage;
-      const uint8_t* sb = sa + OA::kBytes;
-      bf16x8 fb[2][NP];
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int p = 0; p < NP; ++p) fb[j][p] = OB::frag(sb, p, wn * 64 + 32 * j, lane);
-      if constexpr (decltype(STAGE)::value) stg(SET, (int)((t + 1) & 1));
-      if constexpr (decltype(LOAD)::value == 1) ldf(SET);
-      if constexpr (decltype(LOAD)::value == 3) ldm(SET, t + 3);
-      if (MVML_X3W_PRIO) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        bf16x8 fa[NP];
-#pragma unroll
-        for (int p = 0; p < NP; ++p) fa[p] = OA::frag(sa, p, wm * 128 + 32 * i, lane);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = mfma_np<NP>(fa, fb[j], acc[i][j]);
-      }
-      if (MVML_X3W_PRIO) __builtin_amdgcn_s_setprio(0);
-      __syncthreads();
-    };
-    if (ntiles >= 1) { if (ntiles == 1) ldm(S0{}, 0); else ldf(S0{}); }
-    if (ntiles >= 2) { if (ntiles == 2) ldm(S1{}, 1); else ldf(S1{}); }
-    if (ntiles >= 1) stg(S0{}, 0);
-    if (ntiles >= 3) { if (ntiles == 3) ldm(S0{}, 2); else ldf(S0{}); }
-    __syncthreads();
-    int64_t t = 0;
-    for (; t + 5 < ntiles; t += 2) {  // body t loads tile t + 3 (a whole stage: t + 4 < ntiles)
-      body2(t, S1{}, T_{}, L1{});
-      body2(t + 1, S0{}, T_{}, L1{});
-    }
-    for (; t < ntiles; ++t) {  // at most 5 bodies: runtime parity / stage / load kind
-      const bool st = t + 1 < ntiles;
-      const int lk = (t + 4 < ntiles) ? 1 : (t + 4 == ntiles ? 3 : 0);
-      auto tail = [&](auto SET) {
-        if (!st) body2(t, SET, F_{}, L0{});
-        else if (lk == 1) body2(t, SET, T_{}, L1{});
-        else if (lk == 3) body2(t, SET, T_{}, LM{});
-        else body2(t, SET, T_{}, L0{});
-      };
-      if ((t & 1) == 0) tail(S1{});
-      else tail(S0{});
-    }
-  } else
-#endif
+  using LM = std::integral_constant<int, 3>;
   if constexpr (FAST) {
-    using LM = std::integral_constant<int, 3>;
     if (ntiles >= 3) {
       load_fast();
       stage(0);
@@ -1569,7 +1405,6 @@ gemm_x3w_kernel(int64_t M, int64_t N, int64_t K, const float* __restrict__ A, in
           for (int r = 0; r < 16; ++r) acc[i][j][r] = acc[i][j][r] * ua * ub;
     }
   }
-#if MVML_X3W_LDSEPI
   // the projection's logit partials straight from the accumulators, then C through LDS (every
   // K loop ends with a workgroup barrier, so the staging buffers are free)
   if constexpr (EPI_LOGW >= 0)
@@ -1587,11 +1422,6 @@ gemm_x3w_kernel(int64_t M, int64_t N, int64_t K, const float* __restrict__ A, in
         atomicMax(ex.c_rows + blockIdx.z * ex.crows_z + slot * ex.rows_stride + m0 + tid, s_rmax[tid]);
     }
   }
-#else
-  static_assert(NP != 2, "per-row A maxima need the LDS epilogue");
-  tile_epilogue<EPI_LOGW, 4, 2>(acc, M, N, m0 + wm * 128, n0 + wn * 64, lane, bias, beta, act, C,
-                                ldc, slab, epi);
-#endif
   }  // tile loop
 }
 
@@ -1620,11 +1450,9 @@ __global__ void splitk_reduce_kernel(int64_t M, int64_t N, int S, const float* _
   }
 }
 
-// Split-K policy for small-output / long-K products (the weight gradients): pick the split
-// count that fills whole rounds of resident workgroups (256 CUs x 2) best, keeping >= 1024 K
-// per split so the slab reduction stays negligible.
-// Split-K count for `tiles` output tiles over `slots` concurrent workgroups: the count that
-// best fills whole waves of workgroups, keeping >= 1024 k per split.
+// Split-K policy for small-output / long-K products (the weight gradients): the split count for
+// `tiles` output tiles that best fills whole rounds of `slots` resident workgroups, keeping
+// >= 1024 k per split so the slab reduction stays negligible.
 int choose_splits_t(int64_t tiles, int64_t K, int64_t slots) {
   if (tiles >= 2 * slots || K < 2048) return 1;
   int best = 1;
@@ -1688,597 +1516,131 @@ unsigned x3w_grid_x(int64_t tiles, int S) {
   return (unsigned)persist;
 }
 
-// Column sums, stage 1: each thread owns one column of a row chunk; eight independent partial
-// sums keep eight loads in flight per lane (the loop is otherwise latency-bound).
-__global__ void colsum_partial_kernel(int64_t M, int64_t N, const float* __restrict__ X,
-                                      int64_t ldx, int64_t rows_per, float* __restrict__ part) {
-  const int64_t col = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (col >= N) return;
-  const int64_t r0 = (int64_t)blockIdx.y * rows_per, r1 = min(M, r0 + rows_per);
-  float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  int64_t r = r0;
-  for (; r + 8 <= r1; r += 8) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) s[j] += X[(r + j) * ldx + col];
-  }
-  for (; r < r1; ++r) s[0] += X[r * ldx + col];
-  part[(int64_t)blockIdx.y * N + col] = ((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7]));
+// ---- run-time flags -> instantiations ----------------------------------------------------
+// One launch of a tile kernel: the kernels' common argument list, then the grid, the stream and
+// the name the launch check reports.  Each kernel has ONE function below that lists its
+// instantiations; flags outside its list launch nothing and return kNoCase.
+struct TileArgs {
+  int64_t M, N, K;
+  const float* A;
+  int64_t lda;
+  const float* B;
+  int64_t ldb;
+  const float* bias;
+  float beta;
+  int act;
+  float* C;
+  int64_t ldc, k_split;
+  float* slab;
+  int a_vec, b_vec;
+  dim3 grid;
+  hipStream_t st;
+  const char* what;
+  ProjEpi epi = ProjEpi{};
+  BatchStrides bst;
+  AmaxPtrs amax;
+  CellEpi cep;
+  DualPtrs dual;
+  EpiX ex;
+};
+template <typename Fn>
+int switch_bool(bool v, Fn&& fn) {
+  return v ? fn(std::true_type{}) : fn(std::false_type{});
+}
+template <int V>
+using int_c = std::integral_constant<int, V>;
+
+template <bool AK, bool BK, int LW = -1, bool X3 = false, bool H2 = false, bool BPS = false, bool RS = false>
+int run_f32(const TileArgs& a) {
+  gemm_f32_kernel<AK, BK, LW, X3, H2, BPS, RS><<<a.grid, kThreads, 0, a.st>>>(
+      a.M, a.N, a.K, a.A, a.lda, a.B, a.ldb, a.bias, a.beta, a.act, a.C, a.ldc, a.k_split, a.slab, a.a_vec,
+      a.b_vec, a.epi, a.bst, a.amax, a.cep, a.dual);
+  return check_launch(a.what);
+}
+template <bool AK, bool BK, int LW = -1, bool H2 = false>
+int run_x3s(const TileArgs& a) {
+  gemm_x3s_kernel<AK, BK, LW, H2><<<a.grid, kThreads, 0, a.st>>>(
+      a.M, a.N, a.K, a.A, a.lda, a.B, a.ldb, a.bias, a.beta, a.act, a.C, a.ldc, a.k_split, a.slab, a.a_vec,
+      a.b_vec, a.epi, a.bst, a.amax);
+  return check_launch(a.what);
+}
+template <bool AK, bool BK, int LW, bool FAST, int NP, int BPS = 0, bool ROWS = false, bool EX = false>
+int run_x3w(const TileArgs& a) {
+  gemm_x3w_kernel<AK, BK, LW, FAST, NP, BPS, ROWS, EX><<<a.grid, kXThreads, 0, a.st>>>(
+      a.M, a.N, a.K, a.A, a.lda, a.B, a.ldb, a.bias, a.beta, a.act, a.C, a.ldc, a.k_split, a.slab, a.a_vec,
+      a.b_vec, a.epi, a.bst, a.cep, a.amax, a.dual, a.ex);
+  return check_launch(a.what);
 }
 
-// out[col] = beta out[col] + alpha sum_z part[z ld + col]: a workgroup per 16 columns, 16 stripes of
-// the S partials per column (four accumulators each, loads in flight), a fixed-order LDS tree —
-// deterministic.  (A thread per column walking all S ~ 1024 partials took 20-70 us.)
-__global__ void __launch_bounds__(256) colsum_final_kernel(int64_t N, int S, const float* __restrict__ part,
-                                                           int64_t ld, float alpha, float beta,
-                                                           float* __restrict__ out) {
-  const int c = threadIdx.x & 15, stripe = threadIdx.x >> 4;
-  const int64_t col = (int64_t)blockIdx.x * 16 + c;
-  float a[4] = {0.f, 0.f, 0.f, 0.f};
-  if (col < N) {
-    int z = stripe;
-    for (; z + 48 < S; z += 64) {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) a[u] += part[(int64_t)(z + 16 * u) * ld + col];
-    }
-    for (; z < S; z += 16) a[0] += part[(int64_t)z * ld + col];
+// gemm_f32_kernel (128x128, fragments split per wave): every operand layout as fp32, split-bf16
+// (x3) or split-fp16 (h2); split-fp16 also with A's row sums (rs: k-major A) or B pre-split (bps:
+// both operands K-contiguous); fp32 with the projection epilogue (logw 2 .. 5: both K-contiguous).
+int launch_f32(const TileArgs& a, bool ak, bool bk, int logw = -1, bool x3 = false, bool h2 = false,
+               bool bps = false, bool rs = false) {
+  if (logw >= 0) {
+    if (ak || bk || x3 || h2 || bps || rs) return kNoCase;
+    return switch_const<2, 3, 4, 5>(logw, [&](auto LW) { return run_f32<false, false, decltype(LW)::value>(a); });
   }
-  __shared__ float red[16][17];
-  red[stripe][c] = (a[0] + a[1]) + (a[2] + a[3]);
-  __syncthreads();
-  for (int h = 8; h > 0; h >>= 1) {
-    if (stripe < h) red[stripe][c] += red[stripe + h][c];
-    __syncthreads();
-  }
-  if (stripe == 0 && col < N) out[col] = (beta != 0.f ? beta * out[col] : 0.f) + alpha * red[0][c];
+  if (bps) return (ak || bk || !h2 || rs) ? kNoCase : run_f32<false, false, -1, true, true, true>(a);
+  if (rs && !(ak && h2)) return kNoCase;
+  return switch_bool(ak, [&](auto AK) {
+    return switch_bool(bk, [&](auto BK) {
+      constexpr bool akc = decltype(AK)::value, bkc = decltype(BK)::value;
+      if constexpr (akc)
+        if (rs) return run_f32<true, bkc, -1, true, true, false, true>(a);
+      if (h2) return run_f32<akc, bkc, -1, true, true>(a);
+      return x3 ? run_f32<akc, bkc, -1, true>(a) : run_f32<akc, bkc>(a);
+    });
+  });
 }
 
-// |max| of a stored rows x cols fp32 matrix (row pitch ld) folded into *out as float bits:
-// non-negative float bits order like the values, so an unsigned atomicMax per workgroup is
-// order-independent (deterministic).  Four independent rows in flight per thread.
-__global__ void __launch_bounds__(256) absmax_kernel(int64_t rows, int64_t cols,
-                                                     const float* __restrict__ P, int64_t ld,
-                                                     int vec, uint32_t* __restrict__ out) {
-  float m[4] = {0.f, 0.f, 0.f, 0.f};
-  const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t rs = gridDim.y;
-  if (vec) {  // cols % 4 == 0, ld % 4 == 0, 16-B aligned base: c indexes float4 columns
-    if (c < cols / 4) {
-      int64_t r = blockIdx.y;
-      for (; r + 3 * rs < rows; r += 4 * rs) {
-        float4 v[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const float4*>(P + (r + u * rs) * ld + 4 * c);
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-          m[u] = fmaxf(m[u], fmaxf(fmaxf(fabsf(v[u].x), fabsf(v[u].y)), fmaxf(fabsf(v[u].z), fabsf(v[u].w))));
-      }
-      for (; r < rows; r += rs) {
-        const float4 v = *reinterpret_cast<const float4*>(P + r * ld + 4 * c);
-        m[0] = fmaxf(m[0], fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
-      }
-    }
-  } else if (c < cols) {
-    for (int64_t r = blockIdx.y; r < rows; r += rs) m[0] = fmaxf(m[0], fabsf(P[r * ld + c]));
+// gemm_x3s_kernel (128x128, split once per workgroup): every operand layout as split-bf16 or
+// split-fp16 (h2); split-bf16 with the projection epilogue (both K-contiguous).
+int launch_x3s(const TileArgs& a, bool ak, bool bk, int logw = -1, bool h2 = false) {
+  if (logw >= 0) {
+    if (ak || bk || h2) return kNoCase;
+    return switch_const<2, 3, 4, 5>(logw, [&](auto LW) { return run_x3s<false, false, decltype(LW)::value>(a); });
   }
-  float v = wave_max(fmaxf(fmaxf(m[0], m[1]), fmaxf(m[2], m[3])));
-  __shared__ float red[4];
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    v = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    atomicMax(out, __float_as_uint(v));
-  }
+  return switch_bool(ak, [&](auto AK) {
+    return switch_bool(bk, [&](auto BK) {
+      constexpr bool akc = decltype(AK)::value, bkc = decltype(BK)::value;
+      return h2 ? run_x3s<akc, bkc, -1, true>(a) : run_x3s<akc, bkc>(a);
+    });
+  });
 }
 
-// |max| of a contiguous run of n floats (a matrix with ld == cols, or one row): grid-stride over
-// float4s (vec) or floats, 4 loads in flight per thread, one atomicMax per workgroup.  The
-// column-parallel absmax_kernel leaves all but `cols` lanes of a workgroup idle, which for the
-// GAT layers' max-of-row-maxima (N x 1) was 1 live lane in 256: ~0.4 ms per 1.75 M atoms.
-__global__ void __launch_bounds__(256) absmax_flat_kernel(int64_t n, const float* __restrict__ P,
-                                                          int vec, uint32_t* __restrict__ out) {
-  float m[4] = {0.f, 0.f, 0.f, 0.f};
-  const int64_t stride = (int64_t)gridDim.x * 256;
-  int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (vec) {
-    const int64_t n4 = n / 4;
-    const float4* P4 = reinterpret_cast<const float4*>(P);
-    for (; i + 3 * stride < n4; i += 4 * stride) {
-      float4 v[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) v[u] = P4[i + u * stride];
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        m[u] = fmaxf(m[u], fmaxf(fmaxf(fabsf(v[u].x), fabsf(v[u].y)), fmaxf(fabsf(v[u].z), fabsf(v[u].w))));
-    }
-    for (; i < n4; i += stride) {
-      const float4 v = P4[i];
-      m[0] = fmaxf(m[0], fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
-    }
-  } else {
-    for (; i < n; i += stride) m[0] = fmaxf(m[0], fabsf(P[i]));
+// gemm_x3w_kernel (256x256): np = 1 bf16, 2 split-fp16, 3 split-bf16; fast (x3w_fast) or guarded.
+//  * every operand layout, or the projection epilogue (logw 2 .. 5) on K-contiguous operands;
+//  * split-fp16 with a K-contiguous A: per-row A maxima (rows) and / or B read from its il4 image
+//    (bps 2) on the fast path, per-row A maxima alone on the guarded one;
+//  * ex (mvml_gemm_f16x2_ex): fast, per-row A maxima, B fp32 or its il4 image.
+int launch_x3w(const TileArgs& a, bool ak, bool bk, int logw, bool fast, int np, int bps = 0,
+               bool rows = false, bool ex = false) {
+  if (rows || bps || ex) {
+    if (ak || logw >= 0 || np != 2 || (!fast && (bps || !rows || ex)) || (ex && !rows)) return kNoCase;
+    return switch_bool(bk, [&](auto BK) {
+      constexpr bool bkc = decltype(BK)::value;
+      if (ex)
+        return bps ? run_x3w<false, bkc, -1, true, 2, 2, true, true>(a)
+                   : run_x3w<false, bkc, -1, true, 2, 0, true, true>(a);
+      if (!fast) return run_x3w<false, bkc, -1, false, 2, 0, true>(a);
+      if (!bps) return run_x3w<false, bkc, -1, true, 2, 0, true>(a);
+      return rows ? run_x3w<false, bkc, -1, true, 2, 2, true>(a) : run_x3w<false, bkc, -1, true, 2, 2, false>(a);
+    });
   }
-  float v = wave_max(fmaxf(fmaxf(m[0], m[1]), fmaxf(m[2], m[3])));
-  __shared__ float red[4];
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    v = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    atomicMax(out, __float_as_uint(v));
-  }
-}
-
-// Per-row |max| bits: a group of 2^lg lanes per row (float4 columns when vec), butterfly max;
-// one writer per row (accumulate: max with the stored bits), so no atomics.
-__global__ void __launch_bounds__(256) absmax_rows_kernel(int64_t rows, int64_t cols,
-                                                          const float* __restrict__ P, int64_t ld,
-                                                          int vec, int lg, int accumulate,
-                                                          uint32_t* __restrict__ out) {
-  const int L = 1 << lg;
-  const int64_t groups = (int64_t)gridDim.x * (256 >> lg);
-  const int sub = threadIdx.x & (L - 1);
-  for (int64_t row = (int64_t)blockIdx.x * (256 >> lg) + (threadIdx.x >> lg); row < rows; row += groups) {
-    const float* p = P + row * ld;
-    float m = 0.f;
-    if (vec) {
-      for (int64_t c = sub; c < cols / 4; c += L) {
-        const float4 v = *reinterpret_cast<const float4*>(p + 4 * c);
-        m = fmaxf(m, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
-      }
-    } else {
-      for (int64_t c = sub; c < cols; c += L) m = fmaxf(m, fabsf(p[c]));
-    }
-    for (int o = L / 2; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    if (sub == 0) {
-      uint32_t b = __float_as_uint(m);
-      if (accumulate) b = max(b, out[row]);
-      out[row] = b;
-    }
-  }
-}
-
-// Interleaved pre-split of a K-contiguous operand for the 128x128 kernel's BPS path: every
-// 8-value k group becomes its 8 scaled high fp16 halves then its 8 low halves (split2h8's h, l),
-// 32 B in place of the group's 32 B of fp32, so the LDS-DMA staging and the swizzle are unchanged
-// and a fragment read yields the two MFMA operands ready-made.  K % 8 == 0 (host).
-__global__ void __launch_bounds__(256) split_f16x2_il_kernel(int64_t rows, int64_t groups,
-                                                             const float* __restrict__ P, int64_t ld,
-                                                             const uint32_t* __restrict__ amax,
-                                                             float* __restrict__ out) {
-  const float sc = pow2f(amax_shift(*amax));
-  const int64_t total = rows * groups;
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-    const int64_t r = e / groups, c = 8 * (e - r * groups);
-    const float* src = P + r * ld + c;
-    bf16x8 h, l;
-    split2h8(*reinterpret_cast<const float4*>(src), *reinterpret_cast<const float4*>(src + 4), sc, h, l);
-    float* dst = out + r * ld + c;
-    *reinterpret_cast<float4*>(dst) = __builtin_bit_cast(float4, h);
-    *reinterpret_cast<float4*>(dst + 4) = __builtin_bit_cast(float4, l);
-  }
-}
-
-// Interleaved-by-4 pre-split for the 256x256 kernels (BPS 2): every 4-value group of a row
-// becomes [4 scaled high fp16 | 4 low fp16] = 16 B in place of its 16 B of fp32, so the image
-// has the operand's own float indexing (any layout, K-contiguous or K-major) and a staged piece
-// is one 16-B load, stored to the LDS planes as it is (split2h of the kernel's own staging).
-__global__ void __launch_bounds__(256) split_f16x2_il4_kernel(int64_t rows, int64_t cols4,
-                                                              const float* __restrict__ P, int64_t ld,
-                                                              const uint32_t* __restrict__ amax,
-                                                              float* __restrict__ out) {
-  const float sc = pow2f(amax_shift(*amax));
-  const int64_t total = rows * cols4;
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-    const int64_t r = e / cols4, c = 4 * (e - r * cols4);
-    uint2 h, l;
-    split2h(*reinterpret_cast<const float4*>(P + r * ld + c), sc, h, l);
-    *reinterpret_cast<float4*>(out + r * ld + c) =
-        make_float4(__uint_as_float(h.x), __uint_as_float(h.y), __uint_as_float(l.x), __uint_as_float(l.y));
-  }
-}
-
-int split_il_launch(int64_t rows, int64_t K, const float* P, const uint32_t* amax, float* out,
-                    hipStream_t st) {
-  const int64_t total = rows * (K / 8);
-  const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(total, 256), 4096));
-  split_f16x2_il_kernel<<<blocks, 256, 0, st>>>(rows, K / 8, P, K, amax, out);
-  return check_launch("split_f16x2_il_kernel");
-}
-
-int absmax_launch(int64_t rows, int64_t cols, const float* P, int64_t ld, uint32_t* out,
-                  bool accumulate, hipStream_t st) {
-  if (!accumulate && hipMemsetAsync(out, 0, sizeof(uint32_t), st) != hipSuccess) {
-    set_error("absmax: hipMemsetAsync failed");
-    return MVML_ERR_LAUNCH;
-  }
-  if (rows <= 0 || cols <= 0) return MVML_OK;
-  if (ld == cols || rows == 1) {  // contiguous: one flat pass (also bounds the atomics at ~1 K)
-    const int64_t n = rows * cols;
-    const int fvec = (n % 4 == 0) && ((uintptr_t)P % 16 == 0);
-    const unsigned blocks =
-        (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(fvec ? n / 4 : n, 256 * 4), 1024));
-    absmax_flat_kernel<<<blocks, 256, 0, st>>>(n, P, fvec, out);
-    return check_launch("absmax_flat_kernel");
-  }
-  const int vec = (cols % 4 == 0) && (ld % 4 == 0) && ((uintptr_t)P % 16 == 0);
-  const int64_t cx = ceil_div(vec ? cols / 4 : cols, 256);
-  // ~1 K workgroups (each ends with ONE atomicMax on the single output word: a word takes ~90
-  // atomics per us, so the round-4 8 K workgroups spent ~90 us of a 150 us pass on them); each
-  // thread walks its column down rows 4 at a time, enough loads in flight for HBM rate
-  const int64_t ry = std::max<int64_t>(1, std::min<int64_t>(ceil_div(rows, 4), ceil_div(1024, cx)));
-  absmax_kernel<<<dim3((unsigned)cx, (unsigned)ry), 256, 0, st>>>(rows, cols, P, ld, vec, out);
-  return check_launch("absmax_kernel");
-}
-
-int absmax_rows_launch(int64_t rows, int64_t cols, const float* P, int64_t ld, uint32_t* out,
-                       bool accumulate, hipStream_t st) {
-  if (rows <= 0) return MVML_OK;
-  if (cols <= 0) {
-    if (accumulate) return MVML_OK;
-    if (hipMemsetAsync(out, 0, rows * sizeof(uint32_t), st) != hipSuccess) {
-      set_error("absmax_rows: hipMemsetAsync failed");
-      return MVML_ERR_LAUNCH;
-    }
-    return MVML_OK;
-  }
-  const int vec = (cols % 4 == 0) && (ld % 4 == 0) && ((uintptr_t)P % 16 == 0);
-  const int64_t units = vec ? cols / 4 : cols;
-  int lg = 0;
-  while ((1 << lg) < units && lg < 6) ++lg;  // lanes per row: enough for one unit each, <= 64
-  const int64_t per_block = 256 >> lg;
-  const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(rows, per_block), 16384));
-  absmax_rows_kernel<<<blocks, 256, 0, st>>>(rows, cols, P, ld, vec, lg, accumulate ? 1 : 0, out);
-  return check_launch("absmax_rows_kernel");
-}
-
-int colsum_splits(int64_t M, int64_t N) {
-  const int64_t colblocks = ceil_div(N, 256);
-  int64_t s = ceil_div(2048, colblocks);
-  s = std::min<int64_t>(s, ceil_div(M, 64));
-  return (int)std::max<int64_t>(1, std::min<int64_t>(s, 4096));
-}
-
-// ---- small-K split-fp16 product: the layer-1 projection as the memory kernel it is ---------
-// C[M][N] = A[M][K] B[N][K]^T for K <= 96 (the atom features: K = 76 against the 1544 rows of
-// layer 1's Wcat) writes N / K ~ 20 output bytes per input byte: HBM-bound on the C stores, and
-// the 256x256 tile (five 16-deep stages, then an LDS epilogue that cannot overlap the next
-// tile's loads) reached 0.34 of HBM on it.  Here a WAVE owns 64 output columns: it loads the
-// split-fp16 planes of its 64 B rows into registers ONCE (B's il4 image, or fp32 split in place
-// -- bitwise the same planes), then walks chunk_blocks blocks of 16 A rows: A's fragments come
-// straight from global memory (the next block's in flight behind the current block's MFMAs),
-// are split with the row's own scale (split2h, as the tiles do) and multiplied as C^T = B A^T
-// on v_mfma_f32_16x16x32_f16 (K <= 16: 16x16x16) — transposed so that each lane's four
-// accumulators are FOUR CONSECUTIVE COLUMNS OF ONE ROW; a wave-private LDS slice turns the
-// 16 x 64 block into 4-row x 256-B float4 stores (measured: float4 stores straight from the
-// accumulators, 16 rows x 64 B per instruction, ran at the tile's 2.7 TB/s), no block barrier.  The
-// three products per k-step keep the tiles' order (l_b h_a, h_b l_a, h_b h_a); the scales are
-// undone as there (B's, then the row's).  Waves are numbered XCD-major (xcd_block), slab
-// fastest: the ~25 waves sharing a block of A rows run together on one XCD and read the rows
-// from its L2.  Same values as the tiles to fp32-GEMM accuracy (the MFMA shape changes the
-// summation order, so not bitwise).
-constexpr int kSkMaxK = 96;
-
-// KS16 = ceil(K / 16): KS16 / 2 steps of 16x16x32 and, for odd KS16, a 16-deep tail on
-// 16x16x16, each zero-padded past K.  The tail accumulates into its OWN registers, added once at
-// the end: behind 16x16x32 steps on the same accumulators it came out wrong in the first two of
-// each lane's four results (K = 76 / 80, a missing MFMA-to-MFMA wait between the two pass
-// counts).  Skipping the 16 padding k of a 96-deep plan saves 1/6 of the MFMA time at K = 76.
-// A rows with an all-zero low plane (fp16-exact values: layer 1's 0/1 atom features) skip the
-// h_b l_a products — per 16-row block, wave-uniform (a ballot); adding exact zeros is all they
-// would do.
-// ABL (timing ablations, option smallk 5 / 6; wrong results): 1 = no MFMAs, 2 = no C stores
-// WL (default): the workgroup's four waves share ONE 64-column slab (four consecutive row
-// chunks) and its B planes live in LDS (filled once, one group per wave), read per block as
-// fragments — no B registers (162 VGPRs instead of 230), so three waves fit per SIMD and the
-// store stream overlaps more matrix work: 3.26 -> 2.75 ms at config 3 on one box.  WL = false
-// (B fragments in registers, every wave its own slab) stays as option smallk 10.
-template <int KS16, bool IL4, bool NT, int ABL = 0, int NG = 4, bool WL = false>
-__global__ void __launch_bounds__(256, WL ? 3 : 2)  // two (three) waves per SIMD
-gemm_smallk_kernel(int64_t M, int64_t N, int K, const float* __restrict__ A, int64_t lda,
-                   const float* __restrict__ B, int64_t ldb, const uint32_t* __restrict__ a_rows,
-                   const uint32_t* __restrict__ amax_b, const float* __restrict__ bias, int act,
-                   float* __restrict__ C, int64_t ldc, int n_slabs, int chunk_blocks) {
-  constexpr int N32 = KS16 / 2, T16 = KS16 % 2, NW = N32 > 0 ? N32 : 1;
-  constexpr int NX = 2 * N32 + T16;  // A float4 per lane and row block
-  constexpr int SW = 16 * NG, PITCH = SW + 4;  // slab width (columns per wave); LDS row pitch
-  const int lane = threadIdx.x & 63, li = lane & 15, lq = lane >> 4;
-  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int64_t lb = xcd_block(blockIdx.x, gridDim.x);
-  const int64_t w = lb * 4 + wid;
-  const int slab = (int)(WL ? lb % n_slabs : w % n_slabs);
-  const int64_t nrb = (M + 15) >> 4;
-  const int64_t rb0 = (WL ? (lb / n_slabs) * 4 + wid : w / n_slabs) * chunk_blocks;
-  if (!WL && rb0 >= nrb) return;
-  const int64_t rb1 = min(nrb, rb0 + (int64_t)chunk_blocks);
-  const int kb = amax_shift(*amax_b);
-  const float s_b = pow2f(kb), u_b = pow2f(-kb);
-  // this lane's B rows (output columns c0 + 16 g + li) for the MFMA's A side: k = 32 s + 8 lq
-  // + 0..7 (x32 steps), 32 N32 + 4 lq + 0..3 (x16 tail); k >= K reads as zero
-  constexpr int RG = WL ? 1 : NG;  // register copies of the B fragments (WL: none)
-  f16x8 bh[RG][NW], bl[RG][NW];
-  f16x4 th[RG], tl[RG];
-  __shared__ u32x4 s_wh[WL ? NG : 1][WL ? NW : 1][WL ? 64 : 1], s_wl[WL ? NG : 1][WL ? NW : 1][WL ? 64 : 1];
-  __shared__ uint2 s_th[WL ? NG : 1][WL ? 64 : 1], s_tl[WL ? NG : 1][WL ? 64 : 1];
-  auto piece = [&](const float* row, int k, uint2& h, uint2& l) {  // B[row][k .. k + 3] as planes
-    const float4 v = *reinterpret_cast<const float4*>(row + min(k, K - 4));
-    if constexpr (IL4) {
-      h = make_uint2(__float_as_uint(v.x), __float_as_uint(v.y));
-      l = make_uint2(__float_as_uint(v.z), __float_as_uint(v.w));
-    } else {
-      split2h(v, s_b, h, l);
-    }
-    if (k >= K) h = l = make_uint2(0u, 0u);
+  auto rest = [&](auto AK, auto BK, auto LW) {
+    return switch_bool(fast, [&](auto FAST) {
+      return switch_const<1, 2, 3>(np, [&](auto NP) {
+        return run_x3w<decltype(AK)::value, decltype(BK)::value, decltype(LW)::value, decltype(FAST)::value,
+                       decltype(NP)::value>(a);
+      });
+    });
   };
-  if constexpr (WL) {  // wave wid fills group wid's planes (NG == 4 waves), then one barrier
-    static_assert(NG == 4, "one group per wave");
-    const int g = wid;
-    const int64_t col = (int64_t)slab * SW + 16 * g + li;
-    const float* row = B + min(col, N - 1) * ldb;
-#pragma unroll
-    for (int s = 0; s < N32; ++s) {
-      uint2 h0, l0, h1, l1;
-      piece(row, 32 * s + 8 * lq, h0, l0);
-      piece(row, 32 * s + 8 * lq + 4, h1, l1);
-      s_wh[g][s][lane] = u32x4{h0.x, h0.y, h1.x, h1.y};
-      s_wl[g][s][lane] = u32x4{l0.x, l0.y, l1.x, l1.y};
-    }
-    if constexpr (T16) {
-      uint2 h, l;
-      piece(row, 32 * N32 + 4 * lq, h, l);
-      s_th[g][lane] = h;
-      s_tl[g][lane] = l;
-    }
-    __syncthreads();
-    if (rb0 >= nrb) return;
-  } else {
-#pragma unroll
-  for (int g = 0; g < NG; ++g) {
-    const int64_t col = (int64_t)slab * SW + 16 * g + li;
-    const float* row = B + min(col, N - 1) * ldb;
-#pragma unroll
-    for (int s = 0; s < N32; ++s) {
-      uint2 h0, l0, h1, l1;
-      piece(row, 32 * s + 8 * lq, h0, l0);
-      piece(row, 32 * s + 8 * lq + 4, h1, l1);
-      const u32x4 hv = {h0.x, h0.y, h1.x, h1.y}, lv = {l0.x, l0.y, l1.x, l1.y};
-      bh[g][s] = __builtin_bit_cast(f16x8, hv);
-      bl[g][s] = __builtin_bit_cast(f16x8, lv);
-    }
-    if constexpr (T16) {
-      uint2 h, l;
-      piece(row, 32 * N32 + 4 * lq, h, l);
-      th[g] = __builtin_bit_cast(f16x4, h);
-      tl[g] = __builtin_bit_cast(f16x4, l);
-    }
+  if (logw >= 0) {
+    if (ak || bk) return kNoCase;
+    return switch_const<2, 3, 4, 5>(logw, [&](auto LW) { return rest(std::false_type{}, std::false_type{}, LW); });
   }
-  }
-  // the B fragments of group g (registers, or the LDS image)
-  auto fbh = [&](int g, int s) -> f16x8 {
-    if constexpr (WL) return __builtin_bit_cast(f16x8, s_wh[g][s][lane]); else return bh[g][s];
-  };
-  auto fbl = [&](int g, int s) -> f16x8 {
-    if constexpr (WL) return __builtin_bit_cast(f16x8, s_wl[g][s][lane]); else return bl[g][s];
-  };
-  auto fth = [&](int g) -> f16x4 {
-    if constexpr (WL) return __builtin_bit_cast(f16x4, s_th[g][lane]); else return th[g];
-  };
-  auto ftl = [&](int g) -> f16x4 {
-    if constexpr (WL) return __builtin_bit_cast(f16x4, s_tl[g][lane]); else return tl[g];
-  };
-  float bv[NG][4];
-#pragma unroll
-  for (int g = 0; g < NG; ++g)
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int64_t col = (int64_t)slab * SW + 16 * g + 4 * lq + u;
-      bv[g][u] = (bias && col < N) ? bias[col] : 0.f;
-    }
-  // A fragments of one 16-row block: row 16 rb + li, k as B's; KS16 float4 per lane
-  auto load_a = [&](int64_t rb, float4 (&x)[NX], uint32_t& rbits) {
-    const int64_t r = min(rb * 16 + li, M - 1);
-    const float* p = A + r * lda;
-#pragma unroll
-    for (int s = 0; s < N32; ++s) {
-      x[2 * s] = *reinterpret_cast<const float4*>(p + min(32 * s + 8 * lq, K - 4));
-      x[2 * s + 1] = *reinterpret_cast<const float4*>(p + min(32 * s + 8 * lq + 4, K - 4));
-    }
-    if constexpr (T16) x[NX - 1] = *reinterpret_cast<const float4*>(p + min(32 * N32 + 4 * lq, K - 4));
-    rbits = a_rows[r];
-  };
-  __shared__ __attribute__((aligned(16))) float s_c[4][16 * PITCH];
-  float* wl = s_c[threadIdx.x >> 6];
-  // two register sets, prefetch distance 2: a block's A rows are requested two blocks before
-  // they are split (the first of the ~25 waves reading a row block pays the HBM miss)
-  auto block = [&](int64_t rb, float4 (&xn)[NX], uint32_t& rn) {
-    float4 x[NX];
-#pragma unroll
-    for (int i = 0; i < NX; ++i) x[i] = xn[i];
-    const int ka = amax_shift(rn);
-    if (rb + 2 < rb1) load_a(rb + 2, xn, rn);
-    const float s_a = pow2f(ka);
-    f16x8 ah[NW], al[NW];
-    f16x4 ath, atl;
-#pragma unroll
-    for (int s = 0; s < N32; ++s) {
-      uint2 h0, l0, h1, l1;
-      split2h(x[2 * s], s_a, h0, l0);
-      split2h(x[2 * s + 1], s_a, h1, l1);
-      if (32 * s + 8 * lq >= K) h0 = l0 = make_uint2(0u, 0u);
-      if (32 * s + 8 * lq + 4 >= K) h1 = l1 = make_uint2(0u, 0u);
-      const u32x4 hv = {h0.x, h0.y, h1.x, h1.y}, lv = {l0.x, l0.y, l1.x, l1.y};
-      ah[s] = __builtin_bit_cast(f16x8, hv);
-      al[s] = __builtin_bit_cast(f16x8, lv);
-    }
-    if constexpr (T16) {
-      uint2 h, l;
-      split2h(x[NX - 1], s_a, h, l);
-      if (32 * N32 + 4 * lq >= K) h = l = make_uint2(0u, 0u);
-      ath = __builtin_bit_cast(f16x4, h);
-      atl = __builtin_bit_cast(f16x4, l);
-    }
-    // any non-zero word in the block's A low plane (wave-uniform)
-    uint32_t lo_bits = 0;
-#pragma unroll
-    for (int s = 0; s < N32; ++s) {
-      const u32x4 q = __builtin_bit_cast(u32x4, al[s]);
-      lo_bits |= q[0] | q[1] | q[2] | q[3];
-    }
-    if constexpr (T16) {
-      const uint2 q = __builtin_bit_cast(uint2, atl);
-      lo_bits |= q.x | q.y;
-    }
-    const bool a_lo = __ballot(lo_bits != 0) != 0;
-    f32x4 acc[NG];
-    auto products = [&](auto ALO) {
-      constexpr bool kLo = decltype(ALO)::value;
-#pragma unroll
-      for (int g = 0; g < NG; ++g) {
-        acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if constexpr (ABL == 1) {
-#pragma unroll
-          for (int s = 0; s < N32; ++s) {
-            acc[g][0] += (float)ah[s][g] * (float)fbh(g, s)[0];
-            acc[g][1] += (float)al[s][g] * (float)fbl(g, s)[1];
-          }
-          continue;
-        }
-#pragma unroll
-        for (int s = 0; s < N32; ++s) {
-          const f16x8 bhv = fbh(g, s), blv = fbl(g, s);
-          acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(blv, ah[s], acc[g], 0, 0, 0);
-          if constexpr (kLo) acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bhv, al[s], acc[g], 0, 0, 0);
-          acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bhv, ah[s], acc[g], 0, 0, 0);
-        }
-      }
-      if constexpr (T16 && ABL != 1) {
-        f32x4 tac[NG];
-#pragma unroll
-        for (int g = 0; g < NG; ++g) {
-          tac[g] = f32x4{0.f, 0.f, 0.f, 0.f};
-          const f16x4 thv = fth(g), tlv = ftl(g);
-          tac[g] = __builtin_amdgcn_mfma_f32_16x16x16f16(tlv, ath, tac[g], 0, 0, 0);
-          if constexpr (kLo) tac[g] = __builtin_amdgcn_mfma_f32_16x16x16f16(thv, atl, tac[g], 0, 0, 0);
-          tac[g] = __builtin_amdgcn_mfma_f32_16x16x16f16(thv, ath, tac[g], 0, 0, 0);
-        }
-#pragma unroll
-        for (int g = 0; g < NG; ++g) acc[g] = N32 > 0 ? acc[g] + tac[g] : tac[g];
-      }
-    };
-    if (a_lo)
-      products(std::true_type{});
-    else
-      products(std::false_type{});
-    // the 16 x 64 block leaves through the wave's LDS slice: each lane's 4 x float4 (row li,
-    // columns 16 g + 4 lq) in, then 4 rows x 256 contiguous bytes per store instruction out
-    // (straight from the accumulators a store instruction would write 16 rows x 64 B)
-    const float u_a = pow2f(-ka);
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      float4 o;
-      o.x = acc[g][0] * u_b * u_a + bv[g][0];
-      o.y = acc[g][1] * u_b * u_a + bv[g][1];
-      o.z = acc[g][2] * u_b * u_a + bv[g][2];
-      o.w = acc[g][3] * u_b * u_a + bv[g][3];
-      if (act == 1) {
-        o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f);
-      }
-      *reinterpret_cast<float4*>(wl + li * PITCH + 16 * g + 4 * lq) = o;
-    }
-    wave_sync_lds();
-#pragma unroll
-    for (int t = 0; t < NG; ++t) {  // 64 / (4 NG) rows of SW floats per store instruction
-      const int rr = (16 / NG) * t + lane / (4 * NG), c4 = 4 * (lane % (4 * NG));
-      const float4 o = *reinterpret_cast<const float4*>(wl + rr * PITCH + c4);
-      const int64_t row = rb * 16 + rr, col = (int64_t)slab * SW + c4;
-      if (row < M && col < N && (ABL != 2 || __float_as_uint(o.x) == 0x7fc00123u)) {
-        if constexpr (NT) {
-          const f32x4 ov = {o.x, o.y, o.z, o.w};
-          __builtin_nontemporal_store(ov, reinterpret_cast<f32x4*>(C + row * ldc + col));
-        } else {
-          *reinterpret_cast<float4*>(C + row * ldc + col) = o;
-        }
-      }
-    }
-    wave_sync_lds();  // the reads are done before the next block's writes
-  };
-  float4 xa[NX], xb[NX];
-  uint32_t ra = 0, rbits = 0;
-  load_a(rb0, xa, ra);
-  if (rb0 + 1 < rb1) load_a(rb0 + 1, xb, rbits);
-  // (measured: issuing block rb + 1's MFMAs before block rb's epilogue, two accumulator sets,
-  // was ~5 % slower relative to the tile on the same box)
-  for (int64_t rb = rb0; rb < rb1; rb += 2) {
-    block(rb, xa, ra);
-    if (rb + 1 < rb1) block(rb + 1, xb, rbits);
-  }
-}
-
-// Host: the shapes the small-K kernel takes (per-row A scales, K-contiguous B, K <= 96, every
-// row and pointer 16-B aligned, N % 4 == 0, no beta, act 0 / 1).
-bool smallk_fits(int b_kmajor, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda,
-                 const float* Bp, int64_t ldb, float beta, int act, const float* C, int64_t ldc) {
-  auto al = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-  return option(MVML_OPT_SMALLK) != 0 && !b_kmajor && M > 0 && K >= 4 && K <= kSkMaxK && K % 4 == 0 &&
-         N % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0 && ldc % 4 == 0 && al(A) && al(Bp) && al(C) &&
-         beta == 0.f && (act == 0 || act == 1);
-}
-
-int smallk_launch(int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B,
-                  int64_t ldb, bool il4, const uint32_t* a_rows, const uint32_t* amax_b,
-                  const float* bias, int act, float* C, int64_t ldc, hipStream_t st) {
-  // 64 columns per wave (NG = 4).  Measured: 32-column slabs (NG = 2, 152 VGPRs, three waves
-  // per SIMD) 3.38 vs 2.87 ms at config 3 — twice the A reads cost more than the occupancy buys
-  const int n_slabs = (int)ceil_div(N, 64);
-  const int64_t nrb = ceil_div(M, 16);
-  // ~32 row blocks (512 rows) per wave: the B slab's one load is 1/30 of what the wave stores;
-  // fewer on small launches so that >= 4096 waves fill the chip
-  const int sko = option(MVML_OPT_SMALLK);
-  const int64_t cap = sko == 3 ? 8 : (sko == 4 ? 128 : 32);  // (3 / 4: chunk-size variants)
-  const int64_t cb = std::max<int64_t>(1, std::min<int64_t>(cap, nrb * n_slabs / 4096));
-  const int64_t waves = ceil_div(nrb, cb) * n_slabs;
-  const int64_t blocks = ceil_div(waves, 4);
-  if (blocks >= (int64_t(1) << 31)) {
-    set_error("gemm small-K: too many blocks");
-    return MVML_ERR_INVALID;
-  }
-  const bool nt = option(MVML_OPT_SMALLK) != 2;  // (3 .. 6: timing variants)
-  const int ks = (int)ceil_div(K, 16);  // 1 .. 6: the k-step plans above
-  // WL: a workgroup = four row chunks of one slab
-  const int64_t wl_blocks = ceil_div(ceil_div(nrb, cb), 4) * n_slabs;
-#define MVML_SK(KS, IL, NTV)                                                                      \
-  gemm_smallk_kernel<KS, IL, NTV, 0, 4, true><<<(unsigned)wl_blocks, 256, 0, st>>>(              \
-      M, N, (int)K, A, lda, B, ldb, a_rows, amax_b, bias, act, C, ldc, n_slabs, (int)cb)
-#define MVML_SK_KS(IL, NTV)                 \
-  switch (ks) {                             \
-    case 1: MVML_SK(1, IL, NTV); break;     \
-    case 2: MVML_SK(2, IL, NTV); break;     \
-    case 3: MVML_SK(3, IL, NTV); break;     \
-    case 4: MVML_SK(4, IL, NTV); break;     \
-    case 5: MVML_SK(5, IL, NTV); break;     \
-    default: MVML_SK(6, IL, NTV); break;    \
-  }
-  const int opt = option(MVML_OPT_SMALLK);
-  if (opt == 10 && ks == 5 && il4) {  // (10: B fragments in registers — the round-5 first build)
-    gemm_smallk_kernel<5, true, true, 0, 4, false><<<(unsigned)blocks, 256, 0, st>>>(
-        M, N, (int)K, A, lda, B, ldb, a_rows, amax_b, bias, act, C, ldc, n_slabs, (int)cb);
-    return check_launch("gemm_smallk_kernel(B in registers)");
-  }
-  if ((opt == 5 || opt == 6) && ks == 5 && il4) {
-    if (opt == 5)
-      gemm_smallk_kernel<5, true, true, 1, 4, true><<<(unsigned)wl_blocks, 256, 0, st>>>(
-          M, N, (int)K, A, lda, B, ldb, a_rows, amax_b, bias, act, C, ldc, n_slabs, (int)cb);
-    else
-      gemm_smallk_kernel<5, true, true, 2, 4, true><<<(unsigned)wl_blocks, 256, 0, st>>>(
-          M, N, (int)K, A, lda, B, ldb, a_rows, amax_b, bias, act, C, ldc, n_slabs, (int)cb);
-    return check_launch("gemm_smallk_kernel(ablation)");
-  }
-  if (il4) {
-    if (nt) { MVML_SK_KS(true, true) } else { MVML_SK_KS(true, false) }
-  } else {
-    if (nt) { MVML_SK_KS(false, true) } else { MVML_SK_KS(false, false) }
-  }
-#undef MVML_SK_KS
-#undef MVML_SK
-  return check_launch("gemm_smallk_kernel");
+  return switch_bool(ak, [&](auto AK) { return switch_bool(bk, [&](auto BK) { return rest(AK, BK, int_c<-1>{}); }); });
 }
 
 }  // namespace
@@ -2299,8 +1661,97 @@ int gemm_launch(int prec, int a_kmajor, int b_kmajor, int64_t M, int64_t N, int6
                 float beta, int act, float* C, int64_t ldc, void* workspace,
                 size_t workspace_bytes, void* stream, int64_t batch = 1,
                 BatchStrides bst = BatchStrides{}, AmaxPtrs amax = AmaxPtrs{},
-                const uint16_t* bps = nullptr);
+                const uint16_t* bps = nullptr) {
+  MVML_REQUIRE(M >= 0 && N >= 0 && K >= 0, "gemm: negative size");
+  if (M == 0 || N == 0) return MVML_OK;
+  MVML_REQUIRE(ldc >= N, "gemm: ldc < N");
+  MVML_REQUIRE(a_kmajor ? lda >= M : lda >= K, "gemm: bad lda");
+  MVML_REQUIRE(b_kmajor ? ldb >= N : ldb >= K, "gemm: bad ldb");
+  MVML_REQUIRE(act == 0 || act == 1, "gemm: bad act");
+  hipStream_t st = as_stream(stream);
+  const bool hf = prec == kPrecF16x2;
+  const bool x3 = prec == kPrecX3 || hf, bf = prec == kPrecBf16;
+  GemmPlan plan = plan_gemm(prec, M, N, K);
+  MVML_REQUIRE(!amax.a_rows || (hf && !a_kmajor && batch == 1 && amax.b),
+               "gemm: per-row A maxima need split-fp16, a K-contiguous A, no batch and max |B|");
+  if (hf && !amax.a && !amax.a_rows) {  // operand maxima into the workspace head, once per product
+    if (!workspace || workspace_bytes < kAmaxBytes) {
+      set_error("gemm: workspace too small (need %zu)", mvml_gemm_workspace_size(M, N, K));
+      return MVML_ERR_WORKSPACE;
+    }
+    uint32_t* mx = static_cast<uint32_t*>(workspace);
+    int rc = absmax_launch(a_kmajor ? K : M, a_kmajor ? M : K, A, lda, mx, false, st);
+    if (!rc) rc = absmax_launch(b_kmajor ? K : N, b_kmajor ? N : K, B, ldb, mx + 1, false, st);
+    if (rc) return rc;
+    amax = AmaxPtrs{mx, mx + 1};
+  }
+  // N = 256 q + r with 0 < r <= 128 (384-column products: the fusion head's data / weight
+  // gradients, the LSTM hh weight gradients): a last 256-wide tile column would be at least half
+  // padding (so such products fell back to the 128x128 kernel entirely); instead the first
+  // 256 q columns run on the 256x256 kernel and the last r on their own (narrow) plan — two
+  // launches on the stream, one workspace reused in stream order.
+  const bool nsplit_on = option(MVML_OPT_GEMM_NSPLIT) != 0;
+  if (nsplit_on && x3 && batch == 1 && N > XBN && N % XBN != 0 && N % XBN <= XBN / 2 &&
+      plan_gemm(prec, M, N / XBN * XBN, K).wide) {
+    const int64_t N1 = N / XBN * XBN, N2 = N - N1;
+    if (mvml_gemm_workspace_size(M, N1, K) <= workspace_bytes &&
+        mvml_gemm_workspace_size(M, N2, K) <= workspace_bytes) {
+      int rc = gemm_launch(prec, a_kmajor, b_kmajor, M, N1, K, A, lda, B, ldb, bias, beta, act, C,
+                           ldc, workspace, workspace_bytes, stream, 1, BatchStrides{}, amax, bps);
+      if (rc) return rc;
+      const int64_t boff = b_kmajor ? N1 : N1 * ldb;
+      return gemm_launch(prec, a_kmajor, b_kmajor, M, N2, K, A, lda, B + boff, ldb,
+                         bias ? bias + N1 : nullptr, beta, act, C + N1, ldc, workspace,
+                         workspace_bytes, stream, 1, BatchStrides{}, amax, bps ? bps + boff : nullptr);
+    }
+  }
+  if (batch > 1) plan.S = 1;  // batched products are small: no split-K slab
+  const int S = plan.S;
+  float* slab = nullptr;
+  if (S > 1) {
+    if (workspace_bytes < mvml_gemm_workspace_size(M, N, K) || !workspace) {
+      set_error("gemm: workspace too small (need %zu)", mvml_gemm_workspace_size(M, N, K));
+      return MVML_ERR_WORKSPACE;
+    }
+    slab = reinterpret_cast<float*>(static_cast<uint8_t*>(workspace) + kAmaxBytes);
+  }
+  const int64_t kc = S > 1 ? k_chunk(K, S) : (K > 0 ? K : 1);
+  const int64_t tiles = plan.wide ? ceil_div(M, XBM) * ceil_div(N, XBN) : ceil_div(M, BM) * ceil_div(N, BN);
+  MVML_REQUIRE(tiles < (int64_t(1) << 31), "gemm: too many tiles");
+  const int av = (lda % 4 == 0) && ((uintptr_t)A % 16 == 0) && bst.a % 4 == 0;
+  const int bv = (ldb % 4 == 0) && ((uintptr_t)B % 16 == 0) && bst.b % 4 == 0;
+  dim3 grid(plan.wide || bf ? x3w_grid_x(tiles, S) : (unsigned)tiles, (unsigned)S, (unsigned)batch);
+  TileArgs a{M, N, K, A, lda, B, ldb, bias, beta, act, C, ldc, kc, slab, av, bv, grid, st, "gemm_f32_kernel"};
+  a.bst = bst;
+  a.amax = amax;
+  const bool ak = a_kmajor != 0, bk = b_kmajor != 0;
+  const bool fast = x3w_fast(ak, bk, M, N, K, av, bv);
+  // B read from its interleaved-by-4 image (bps, mvml_split_f16x2_il4): the 256x256 tile's fast
+  // path with a K-contiguous A only; every other plan splits the fp32 B itself
+  const bool il4 = bps && plan.wide && !ak && batch == 1 && fast;
+  if (il4) a.B = reinterpret_cast<const float*>(bps);
+  int rc;
+  if (plan.wide && (amax.a_rows || il4))  // per-row A maxima (host: !a_kmajor) and / or the il4 image
+    rc = launch_x3w(a, false, bk, -1, fast, 2, il4 ? 2 : 0, amax.a_rows != nullptr);
+  else if (hf && plan.wide) rc = launch_x3w(a, ak, bk, -1, fast, 2);
+  else if (bf) rc = launch_x3w(a, ak, bk, -1, fast, 1);
+  else if (plan.wide) rc = launch_x3w(a, ak, bk, -1, fast, 3);
+  else if (hf && ak && bk)  // skinny, both k-major: split-fp16 fragment split (+ A's row sums)
+    rc = launch_f32(a, true, true, -1, true, true, false, amax.a_rowsum != nullptr);
+  else if (x3 && ak && bk) rc = launch_f32(a, true, true, -1, true);  // fragment split measured faster at 128x128
+  else if (hf) rc = launch_x3s(a, ak, bk, -1, true);  // skinny: split-fp16 planes staged once per workgroup
+  else if (x3) rc = launch_x3s(a, ak, bk);
+  else rc = launch_f32(a, ak, bk);
+  if (rc) return rc;
+  if (S > 1) {
+    const int64_t total = M * N;
+    const unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(total, 256), 4096);
+    splitk_reduce_kernel<<<blocks, 256, 0, st>>>(M, N, S, slab, bias, beta, act, C, ldc);
+    rc = check_launch("splitk_reduce_kernel");
+  }
+  return rc;
 }
+}  // namespace
 
 extern "C" int mvml_gemm_f32(int a_kmajor, int b_kmajor, int64_t M, int64_t N, int64_t K,
                              const float* A, int64_t lda, const float* B, int64_t ldb,
@@ -2403,29 +1854,16 @@ extern "C" int mvml_gemm_f16x2_ex(int64_t M, int64_t N, int64_t K, int64_t batch
   const int64_t tiles = ceil_div(M, XBM) * ceil_div(N, XBN);
   MVML_REQUIRE(tiles < (int64_t(1) << 31), "gemm_f16x2_ex: too many tiles");
   const dim3 grid(x3w_grid_x(tiles, 1), 1, (unsigned)batch);
-  const BatchStrides bst{stride_a, stride_b, stride_c};
-  AmaxPtrs am;
-  am.b = amax_b;
-  am.a_rows = amax_a_rows;
-  EpiX ex;
+  TileArgs a{M, N, K, A, lda, Bp, ldb, bias, 0.f, act, C, ldc, K > 0 ? K : 1, nullptr, av, bv, grid,
+             as_stream(stream), "gemm_x3w_kernel(ex)"};
+  a.bst = BatchStrides{stride_a, stride_b, stride_c};
+  a.amax.b = amax_b;
+  a.amax.a_rows = amax_a_rows;
+  EpiX& ex = a.ex;
   ex.aux = aux; ex.ld_aux = ld_aux; ex.c_amax = c_amax; ex.c_rows = c_rows;
   ex.rows_stride = c_rows_stride; ex.rows_cols = c_rows_cols;
   ex.bias_z = stride_bias; ex.rows_z = stride_rows; ex.crows_z = stride_c_rows;
-  hipStream_t st = as_stream(stream);
-  const int64_t kc = K > 0 ? K : 1;
-#define MVML_X3W_EX(BKV, BPSV)                                                                    \
-  gemm_x3w_kernel<false, BKV, -1, true, 2, BPSV, true, true><<<grid, kXThreads, 0, st>>>(         \
-      M, N, K, A, lda, Bp, ldb, bias, 0.f, act, C, ldc, kc, nullptr, av, bv, ProjEpi{}, bst,       \
-      CellEpi{}, am, DualPtrs{}, ex)
-  if (b_kmajor) {
-    if (b_il4) MVML_X3W_EX(true, 2);
-    else MVML_X3W_EX(true, 0);
-  } else {
-    if (b_il4) MVML_X3W_EX(false, 2);
-    else MVML_X3W_EX(false, 0);
-  }
-#undef MVML_X3W_EX
-  return check_launch("gemm_x3w_kernel(ex)");
+  return launch_x3w(a, false, b_kmajor != 0, -1, true, 2, b_il4 ? 2 : 0, true, true);
 }
 
 extern "C" int mvml_gemm_f16x2_batched(int a_kmajor, int b_kmajor, int64_t M, int64_t N, int64_t K,
@@ -2442,26 +1880,6 @@ extern "C" int mvml_gemm_f16x2_batched(int a_kmajor, int b_kmajor, int64_t M, in
                      AmaxPtrs{amax_a, amax_b});
 }
 
-extern "C" int mvml_split_f16x2_il4(int64_t rows, int64_t cols, const float* P, int64_t ld,
-                                    const uint32_t* amax, float* out, void* stream) {
-  clear_error();
-  MVML_REQUIRE(rows >= 0 && cols >= 0 && cols % 4 == 0 && ld % 4 == 0 && ld >= cols && amax &&
-                   out && ((uintptr_t)P % 16) == 0 && ((uintptr_t)out % 16) == 0,
-               "split_f16x2_il4: bad shape / alignment");
-  if (rows == 0 || cols == 0) return MVML_OK;
-  const int64_t total = rows * (cols / 4);
-  const unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(total, 256), 8192);
-  split_f16x2_il4_kernel<<<blocks, 256, 0, as_stream(stream)>>>(rows, cols / 4, P, ld, amax, out);
-  return check_launch("split_f16x2_il4_kernel");
-}
-
-extern "C" int mvml_absmax_rows_f32(int64_t rows, int64_t cols, const float* P, int64_t ld,
-                                    uint32_t* out, int accumulate, void* stream) {
-  clear_error();
-  MVML_REQUIRE(rows >= 0 && cols >= 0 && (rows == 0 || ld >= cols) && out, "absmax_rows: bad shape");
-  return absmax_rows_launch(rows, cols, P, ld, out, accumulate != 0, as_stream(stream));
-}
-
 extern "C" int mvml_gemm_f16x2_bsplit(int a_kmajor, int b_kmajor, int64_t M, int64_t N, int64_t K,
                                       const float* A, int64_t lda, const float* B, int64_t ldb,
                                       const uint16_t* b_planes, int64_t b_plane,
@@ -2472,16 +1890,9 @@ extern "C" int mvml_gemm_f16x2_bsplit(int a_kmajor, int b_kmajor, int64_t M, int
   clear_error();
   MVML_REQUIRE(amax_a && amax_b && b_planes && b_plane == 0 && ((uintptr_t)b_planes % 16) == 0,
                "gemm_f16x2_bsplit: maxima and B's planes are required");
-  AmaxPtrs am{amax_a, amax_b, b_plane};
+  AmaxPtrs am{amax_a, amax_b};
   return gemm_launch(kPrecF16x2, a_kmajor, b_kmajor, M, N, K, A, lda, B, ldb, bias, beta, act, C,
                      ldc, workspace, workspace_bytes, stream, 1, BatchStrides{}, am, b_planes);
-}
-
-extern "C" int mvml_absmax_f32(int64_t rows, int64_t cols, const float* P, int64_t ld,
-                               uint32_t* out, int accumulate, void* stream) {
-  clear_error();
-  MVML_REQUIRE(rows >= 0 && cols >= 0 && (rows == 0 || ld >= cols) && out, "absmax: bad shape");
-  return absmax_launch(rows, cols, P, ld, out, accumulate != 0, as_stream(stream));
 }
 
 extern "C" int mvml_gemm_f32x3_batched(int a_kmajor, int b_kmajor, int64_t M, int64_t N,
@@ -2507,7 +1918,7 @@ extern "C" int mvml_lstm_gates_cell_fwd(int64_t M, int D, int64_t K, const float
                                         void* stream) {
   clear_error();
   MVML_REQUIRE(M >= 0 && D > 0 && K > 0 && lda >= K && ldw >= K && ldh >= D &&
-                   (!h_out2 || ldh2 >= D) && MVML_X3W_LDSEPI,
+                   (!h_out2 || ldh2 >= D),
                "lstm_gates_cell_fwd: bad shape");
   MVML_REQUIRE(!amax_a_rows || amax_b, "lstm_gates_cell_fwd: per-row A maxima need max |w_perm|");
   if (amax_a_rows && !amax_a) amax_a = amax_a_rows;  // (unused: the rows' maxima replace it)
@@ -2520,37 +1931,26 @@ extern "C" int mvml_lstm_gates_cell_fwd(int64_t M, int D, int64_t K, const float
                "lstm_gates_cell_fwd: needs the 256x256 plan without split-K and aligned rows "
                "(use mvml_gemm_f32x3 + mvml_lstm_cell_fwd)");
   const int64_t tiles = ceil_div(M, XBM) * ceil_div(N, XBN);
-  CellEpi cep;
+  TileArgs a{M, N, K, A, lda, w_perm, ldw, nullptr, 0.f, 0, nullptr, N, K, nullptr, av, bv,
+             dim3(x3w_grid_x(tiles, 1), 1, 1), as_stream(stream), "gemm_x3w_kernel(lstm cell)"};
+  CellEpi& cep = a.cep;
   cep.b_ih = b_ih; cep.b_hh = b_hh; cep.c_prev = c_prev; cep.c_out = c_out; cep.h_out = h_out;
   cep.h_out2 = h_out2; cep.act = act; cep.ldh = ldh; cep.ldh2 = ldh2; cep.D = D;
-  const dim3 grid(x3w_grid_x(tiles, 1), 1, 1);
   MVML_REQUIRE(!amax_a == !amax_b, "lstm_gates_cell_fwd: give both maxima or neither");
+  a.amax = AmaxPtrs{amax_a, amax_b, 0, amax_a_rows};
   if (amax_a && option(MVML_OPT_LSTM_TILE) == 128 && K % BKT == 0) {
     // the 128x128 split-fp16 kernel with the same cell epilogue (the wide BiLSTM steps' plan)
-    const int64_t t128 = ceil_div(M, BM) * ceil_div(N, BN);
-    gemm_f32_kernel<false, false, -1, true, true><<<dim3((unsigned)t128, 1, 1), kThreads, 0, as_stream(stream)>>>(
-        M, N, K, A, lda, w_perm, ldw, nullptr, 0.f, 0, nullptr, N, K, nullptr, av, bv, ProjEpi{},
-        BatchStrides{}, AmaxPtrs{amax_a, amax_b, 0, amax_a_rows}, cep);
-    return check_launch("gemm_f32_kernel(lstm cell)");
+    a.grid = dim3((unsigned)(ceil_div(M, BM) * ceil_div(N, BN)), 1, 1);
+    a.what = "gemm_f32_kernel(lstm cell)";
+    return launch_f32(a, false, false, -1, true, true);
   }
   MVML_REQUIRE(!w_planes || w_plane == 0, "lstm_gates_cell_fwd: w_planes must be the il4 image (w_plane 0)");
-  if (amax_a_rows && w_planes)  // per-row A, w_perm from its il4 image
-    gemm_x3w_kernel<false, false, -1, true, 2, 2, true><<<grid, kXThreads, 0, as_stream(stream)>>>(
-        M, N, K, A, lda, reinterpret_cast<const float*>(w_planes), ldw, nullptr, 0.f, 0, nullptr,
-        N, K, nullptr, av, bv, ProjEpi{}, BatchStrides{}, cep, AmaxPtrs{amax_a, amax_b, 0, amax_a_rows});
-  else if (amax_a_rows)  // a scale per A row (Set2Set: per molecule)
-    gemm_x3w_kernel<false, false, -1, true, 2, 0, true><<<grid, kXThreads, 0, as_stream(stream)>>>(
-        M, N, K, A, lda, w_perm, ldw, nullptr, 0.f, 0, nullptr, N, K, nullptr, av, bv, ProjEpi{},
-        BatchStrides{}, cep, AmaxPtrs{amax_a, amax_b, 0, amax_a_rows});
-  else if (amax_a)
-    gemm_x3w_kernel<false, false, -1, true, 2><<<grid, kXThreads, 0, as_stream(stream)>>>(
-        M, N, K, A, lda, w_perm, ldw, nullptr, 0.f, 0, nullptr, N, K, nullptr, av, bv, ProjEpi{},
-        BatchStrides{}, cep, AmaxPtrs{amax_a, amax_b});
-  else
-    gemm_x3w_kernel<false, false, -1, true><<<grid, kXThreads, 0, as_stream(stream)>>>(
-        M, N, K, A, lda, w_perm, ldw, nullptr, 0.f, 0, nullptr, N, K, nullptr, av, bv, ProjEpi{},
-        BatchStrides{}, cep);
-  return check_launch("gemm_x3w_kernel(lstm cell)");
+  if (amax_a_rows && w_planes) {  // per-row A, w_perm from its il4 image
+    a.B = reinterpret_cast<const float*>(w_planes);
+    return launch_x3w(a, false, false, -1, true, 2, 2, true);
+  }
+  // a scale per A row (Set2Set: per molecule), operand-wide scales, or split-bf16
+  return launch_x3w(a, false, false, -1, true, amax_a ? 2 : 3, 0, amax_a_rows != nullptr);
 }
 
 extern "C" int mvml_lstm_gates_cell_plan_ok(int64_t M, int D, int64_t K) {
@@ -2567,180 +1967,17 @@ extern "C" int mvml_gemm_bf16(int a_kmajor, int b_kmajor, int64_t M, int64_t N, 
                      ldc, workspace, workspace_bytes, stream);
 }
 
-namespace {
-int gemm_launch(int prec, int a_kmajor, int b_kmajor, int64_t M, int64_t N, int64_t K,
-                const float* A, int64_t lda, const float* B, int64_t ldb, const float* bias,
-                float beta, int act, float* C, int64_t ldc, void* workspace,
-                size_t workspace_bytes, void* stream, int64_t batch, BatchStrides bst,
-                AmaxPtrs amax, const uint16_t* bps) {
-  MVML_REQUIRE(M >= 0 && N >= 0 && K >= 0, "gemm: negative size");
-  if (M == 0 || N == 0) return MVML_OK;
-  MVML_REQUIRE(ldc >= N, "gemm: ldc < N");
-  MVML_REQUIRE(a_kmajor ? lda >= M : lda >= K, "gemm: bad lda");
-  MVML_REQUIRE(b_kmajor ? ldb >= N : ldb >= K, "gemm: bad ldb");
-  MVML_REQUIRE(act == 0 || act == 1, "gemm: bad act");
-  hipStream_t st = as_stream(stream);
-  const bool hf = prec == kPrecF16x2;
-  const bool x3 = prec == kPrecX3 || hf, bf = prec == kPrecBf16;
-  GemmPlan plan = plan_gemm(prec, M, N, K);
-  MVML_REQUIRE(!amax.a_rows || (hf && !a_kmajor && batch == 1 && amax.b),
-               "gemm: per-row A maxima need split-fp16, a K-contiguous A, no batch and max |B|");
-  if (hf && !amax.a && !amax.a_rows) {  // operand maxima into the workspace head, once per product
-    if (!workspace || workspace_bytes < kAmaxBytes) {
-      set_error("gemm: workspace too small (need %zu)", mvml_gemm_workspace_size(M, N, K));
-      return MVML_ERR_WORKSPACE;
-    }
-    uint32_t* mx = static_cast<uint32_t*>(workspace);
-    int rc = absmax_launch(a_kmajor ? K : M, a_kmajor ? M : K, A, lda, mx, false, st);
-    if (!rc) rc = absmax_launch(b_kmajor ? K : N, b_kmajor ? N : K, B, ldb, mx + 1, false, st);
-    if (rc) return rc;
-    amax = AmaxPtrs{mx, mx + 1};
-  }
-  // N = 256 q + r with 0 < r <= 128 (384-column products: the fusion head's data / weight
-  // gradients, the LSTM hh weight gradients): a last 256-wide tile column would be at least half
-  // padding (so such products fell back to the 128x128 kernel entirely); instead the first
-  // 256 q columns run on the 256x256 kernel and the last r on their own (narrow) plan — two
-  // launches on the stream, one workspace reused in stream order.
-  const bool nsplit_on = option(MVML_OPT_GEMM_NSPLIT) != 0;
-  if (nsplit_on && x3 && batch == 1 && N > XBN && N % XBN != 0 && N % XBN <= XBN / 2 &&
-      plan_gemm(prec, M, N / XBN * XBN, K).wide) {
-    const int64_t N1 = N / XBN * XBN, N2 = N - N1;
-    if (mvml_gemm_workspace_size(M, N1, K) <= workspace_bytes &&
-        mvml_gemm_workspace_size(M, N2, K) <= workspace_bytes) {
-      int rc = gemm_launch(prec, a_kmajor, b_kmajor, M, N1, K, A, lda, B, ldb, bias, beta, act, C,
-                           ldc, workspace, workspace_bytes, stream, 1, BatchStrides{}, amax, bps);
-      if (rc) return rc;
-      const int64_t boff = b_kmajor ? N1 : N1 * ldb;
-      return gemm_launch(prec, a_kmajor, b_kmajor, M, N2, K, A, lda, B + boff, ldb,
-                         bias ? bias + N1 : nullptr, beta, act, C + N1, ldc, workspace,
-                         workspace_bytes, stream, 1, BatchStrides{}, amax, bps ? bps + boff : nullptr);
-    }
-  }
-  if (batch > 1) plan.S = 1;  // batched products are small: no split-K slab
-  const int S = plan.S;
-  float* slab = nullptr;
-  if (S > 1) {
-    if (workspace_bytes < mvml_gemm_workspace_size(M, N, K) || !workspace) {
-      set_error("gemm: workspace too small (need %zu)", mvml_gemm_workspace_size(M, N, K));
-      return MVML_ERR_WORKSPACE;
-    }
-    slab = reinterpret_cast<float*>(static_cast<uint8_t*>(workspace) + kAmaxBytes);
-  }
-  const int64_t kc = S > 1 ? k_chunk(K, S) : (K > 0 ? K : 1);
-  const int64_t tiles = plan.wide ? ceil_div(M, XBM) * ceil_div(N, XBN) : ceil_div(M, BM) * ceil_div(N, BN);
-  MVML_REQUIRE(tiles < (int64_t(1) << 31), "gemm: too many tiles");
-  const int av = (lda % 4 == 0) && ((uintptr_t)A % 16 == 0) && bst.a % 4 == 0;
-  const int bv = (ldb % 4 == 0) && ((uintptr_t)B % 16 == 0) && bst.b % 4 == 0;
-  dim3 grid(plan.wide || bf ? x3w_grid_x(tiles, S) : (unsigned)tiles, (unsigned)S, (unsigned)batch);
-  // B pre-split as an interleaved-by-4 image (bps with b_plane == 0, mvml_split_f16x2_il4) and /
-  // or per-row A maxima, on the 256x256 tile (host: K-contiguous A)
-  const bool il4 = bps && amax.b_plane == 0;
-  const float* Bil = il4 ? reinterpret_cast<const float*>(bps) : B;
-#define MVML_X3W_RB(BKV, BPSV, ROWSV)                                                            \
-  gemm_x3w_kernel<false, BKV, -1, true, 2, BPSV, ROWSV><<<grid, kXThreads, 0, st>>>(             \
-      M, N, K, A, lda, Bil, ldb, bias, beta, act, C, ldc, kc, slab, av, bv, ProjEpi{}, bst,       \
-      CellEpi{}, amax)
-  if ((amax.a_rows || il4) && plan.wide && !a_kmajor && batch == 1 &&
-      x3w_fast(false, b_kmajor, M, N, K, av, bv)) {
-    if (b_kmajor) {
-      if (il4 && amax.a_rows) MVML_X3W_RB(true, 2, true);
-      else if (il4) MVML_X3W_RB(true, 2, false);
-      else MVML_X3W_RB(true, 0, true);
-    } else {
-      if (il4 && amax.a_rows) MVML_X3W_RB(false, 2, true);
-      else if (il4) MVML_X3W_RB(false, 2, false);
-      else MVML_X3W_RB(false, 0, true);
-    }
-  } else
-#undef MVML_X3W_RB
-  if (amax.a_rows && plan.wide) {  // per-row A maxima on the 256x256 tile (host: !a_kmajor)
-    if (b_kmajor && x3w_fast(false, true, M, N, K, av, bv))
-      gemm_x3w_kernel<false, true, -1, true, 2, 0, true><<<grid, kXThreads, 0, st>>>(
-          M, N, K, A, lda, B, ldb, bias, beta, act, C, ldc, kc, slab, av, bv, ProjEpi{}, bst, CellEpi{}, amax);
-    else if (b_kmajor)
-      gemm_x3w_kernel<false, true, -1, false, 2, 0, true><<<grid, kXThreads, 0, st>>>(
-          M, N, K, A, lda, B, ldb, bias, beta, act, C, ldc, kc, slab, av, bv, ProjEpi{}, bst, CellEpi{}, amax);
-    else if (x3w_fast(false, false, M, N, K, av, bv))
-      gemm_x3w_kernel<false, false, -1, true, 2, 0, true><<<grid, kXThreads, 0, st>>>(
-          M, N, K, A, lda, B, ldb, bias, beta, act, C, ldc, kc, slab, av, bv, ProjEpi{}, bst, CellEpi{}, amax);
-    else
-      gemm_x3w_kernel<false, false, -1, false, 2, 0, true><<<grid, kXThreads, 0, st>>>(
-          M, N, K, A, lda, B, ldb, bias, beta, act, C, ldc, kc, slab, av, bv, ProjEpi{}, bst, CellEpi{}, amax);
-  } else
-#define MVML_GEMM_LAUNCH(AKV, BKV)                                                              \
-  do {                                                                                          \
-    if (hf && plan.wide && x3w_fast(AKV, BKV, M, N, K, av, bv))                                 \
-      gemm_x3w_kernel<AKV, BKV, -1, true, 2><<<grid, kXThreads, 0, st>>>(                       \
-          M, N, K, A, lda, B, ldb, bias, beta, act, C, ldc, kc, slab, av, bv, ProjEpi{}, bst,   \
-          CellEpi{}, amax);                                                                     \
-    else if (hf && plan.wide)                                                                   \
-      gemm_x3w_kernel<AKV, BKV, -1, false, 2><<<grid, kXThreads, 0, st>>>(                      \
-          M, N, K, A, lda, B, ldb, bias, beta, act, C, ldc, kc, slab, av, bv, ProjEpi{}, bst,   \
-          CellEpi{}, amax);                                                                     \
-    else if (bf && x3w_fast(AKV, BKV, M, N, K, av, bv))                                         \
-      gemm_x3w_kernel<AKV, BKV, -1, true, 1><<<grid, kXThreads, 0, st>>>(                       \
-          M, N, K, A, lda, B, ldb, bias, beta, act, C, ldc, kc, slab, av, bv, ProjEpi{}, bst);  \
-    else if (bf)                                                                                \
-      gemm_x3w_kernel<AKV, BKV, -1, false, 1><<<grid, kXThreads, 0, st>>>(                      \
-          M, N, K, A, lda, B, ldb, bias, beta, act, C, ldc, kc, slab, av, bv, ProjEpi{}, bst);  \
-    else if (plan.wide && x3w_fast(AKV, BKV, M, N, K, av, bv))                                  \
-      gemm_x3w_kernel<AKV, BKV, -1, true><<<grid, kXThreads, 0, st>>>(                          \
-          M, N, K, A, lda, B, ldb, bias, beta, act, C, ldc, kc, slab, av, bv, ProjEpi{}, bst);  \
-    else if (plan.wide)                                                                         \
-      gemm_x3w_kernel<AKV, BKV, -1, false><<<grid, kXThreads, 0, st>>>(                         \
-          M, N, K, A, lda, B, ldb, bias, beta, act, C, ldc, kc, slab, av, bv, ProjEpi{}, bst);  \
-    else if (hf && AKV && BKV && amax.a_rowsum) /* + A's row sums (host: AKV) */               \
-      gemm_f32_kernel<AKV, BKV, -1, true, true, false, AKV><<<grid, kThreads, 0, st>>>(         \
-          M, N, K, A, lda, B, ldb, bias, beta, act, C, ldc, kc, slab, av, bv, ProjEpi{}, bst,   \
-          amax);                                                                                \
-    else if (hf && AKV && BKV) /* skinny, both k-major: split-fp16 fragment split */           \
-      gemm_f32_kernel<AKV, BKV, -1, true, true><<<grid, kThreads, 0, st>>>(                     \
-          M, N, K, A, lda, B, ldb, bias, beta, act, C, ldc, kc, slab, av, bv, ProjEpi{}, bst,   \
-          amax);                                                                                \
-    else if (x3 && AKV && BKV) /* both k-major: fragment split measured faster at 128x128 */    \
-      gemm_f32_kernel<AKV, BKV, -1, true><<<grid, kThreads, 0, st>>>(                           \
-          M, N, K, A, lda, B, ldb, bias, beta, act, C, ldc, kc, slab, av, bv, ProjEpi{}, bst);  \
-    else if (hf) /* skinny: split-fp16 planes staged once per workgroup */                    \
-      gemm_x3s_kernel<AKV, BKV, -1, true><<<grid, kThreads, 0, st>>>(                           \
-          M, N, K, A, lda, B, ldb, bias, beta, act, C, ldc, kc, slab, av, bv, ProjEpi{}, bst,   \
-          amax);                                                                                \
-    else if (x3)                                                                                \
-      gemm_x3s_kernel<AKV, BKV><<<grid, kThreads, 0, st>>>(                                     \
-          M, N, K, A, lda, B, ldb, bias, beta, act, C, ldc, kc, slab, av, bv, ProjEpi{}, bst);  \
-    else                                                                                        \
-      gemm_f32_kernel<AKV, BKV><<<grid, kThreads, 0, st>>>(M, N, K, A, lda, B, ldb, bias, beta, \
-                                                           act, C, ldc, kc, slab, av, bv,       \
-                                                           ProjEpi{}, bst);                     \
-  } while (0)
-  if (!a_kmajor && !b_kmajor) MVML_GEMM_LAUNCH(false, false);
-  else if (!a_kmajor && b_kmajor) MVML_GEMM_LAUNCH(false, true);
-  else if (a_kmajor && !b_kmajor) MVML_GEMM_LAUNCH(true, false);
-  else MVML_GEMM_LAUNCH(true, true);
-#undef MVML_GEMM_LAUNCH
-  int rc = check_launch("gemm_f32_kernel");
-  if (rc) return rc;
-  if (S > 1) {
-    const int64_t total = M * N;
-    const unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(total, 256), 4096);
-    splitk_reduce_kernel<<<blocks, 256, 0, st>>>(M, N, S, slab, bias, beta, act, C, ldc);
-    rc = check_launch("splitk_reduce_kernel");
-  }
-  return rc;
-}
-}  // namespace
-
 namespace mvml {
 // Projection GEMM with the logits-partial epilogue: C[M,N] = A[M,K] B[N,K]^T (both
 // K-contiguous, no split-K: K is the small feature dimension), part as in ProjEpi.
 int gemm_proj_epi(int prec, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda,
                   const float* B, int64_t ldb, float* C, int64_t ldc, const float* vec, int cols,
                   int logw, float* part, uint32_t* amax_ws, const uint32_t* amax_x,
-                  const uint32_t* amax_w, const uint16_t* w_planes, int64_t w_plane,
-                  hipStream_t st) {
+                  const uint32_t* amax_w, const uint16_t* w_planes, hipStream_t st) {
   const bool hf = prec == kPrecF16x2;
   const bool x3 = prec == kPrecX3 || hf, bf = prec == kPrecBf16;
   const bool wide = bf || (x3 && plan_gemm(kPrecX3, M, N, K).wide);
-  AmaxPtrs amx{amax_x, amax_w, w_plane};
+  AmaxPtrs amx{amax_x, amax_w};
   MVML_REQUIRE(!w_planes, "gat_proj_fwd: w_planes must be NULL (the two-plane weight image was removed)");
   if (hf && wide && !(amax_x && amax_w)) {  // maxima not supplied: one pass per operand
     MVML_REQUIRE(amax_ws != nullptr, "gat_proj_fwd: split-fp16 needs the maxima workspace");
@@ -2754,76 +1991,20 @@ int gemm_proj_epi(int prec, int64_t M, int64_t N, int64_t K, const float* A, int
   MVML_REQUIRE(cols <= N && (logw >= 2 && logw <= 5), "gat_proj_fwd: bad partial width");
   const int av = (lda % 4 == 0) && ((uintptr_t)A % 16 == 0);
   const int bv = (ldb % 4 == 0) && ((uintptr_t)B % 16 == 0);
-  dim3 grid(wide ? x3w_grid_x(tiles, 1) : (unsigned)tiles, 1);
-#define MVML_PROJ(LW)                                                                          \
-  do {                                                                                         \
-    if (hf && wide && x3w_fast(false, false, M, N, K, av, bv))                                 \
-      gemm_x3w_kernel<false, false, LW, true, 2><<<grid, kXThreads, 0, st>>>(                  \
-          M, N, K, A, lda, B, ldb, nullptr, 0.f, 0, C, ldc, K > 0 ? K : 1, nullptr, av, bv,    \
-          ProjEpi{vec, cols, part}, BatchStrides{}, CellEpi{}, amx);                       \
-    else if (hf && wide)                                                                       \
-      gemm_x3w_kernel<false, false, LW, false, 2><<<grid, kXThreads, 0, st>>>(                 \
-          M, N, K, A, lda, B, ldb, nullptr, 0.f, 0, C, ldc, K > 0 ? K : 1, nullptr, av, bv,    \
-          ProjEpi{vec, cols, part}, BatchStrides{}, CellEpi{}, amx);                       \
-    else if (bf && x3w_fast(false, false, M, N, K, av, bv))                                    \
-      gemm_x3w_kernel<false, false, LW, true, 1><<<grid, kXThreads, 0, st>>>(                  \
-          M, N, K, A, lda, B, ldb, nullptr, 0.f, 0, C, ldc, K > 0 ? K : 1, nullptr, av, bv,    \
-          ProjEpi{vec, cols, part});                                                           \
-    else if (bf)                                                                               \
-      gemm_x3w_kernel<false, false, LW, false, 1><<<grid, kXThreads, 0, st>>>(                 \
-          M, N, K, A, lda, B, ldb, nullptr, 0.f, 0, C, ldc, K > 0 ? K : 1, nullptr, av, bv,    \
-          ProjEpi{vec, cols, part});                                                           \
-    else if (wide && x3w_fast(false, false, M, N, K, av, bv))                                  \
-      gemm_x3w_kernel<false, false, LW, true><<<grid, kXThreads, 0, st>>>(                     \
-          M, N, K, A, lda, B, ldb, nullptr, 0.f, 0, C, ldc, K > 0 ? K : 1, nullptr, av, bv,    \
-          ProjEpi{vec, cols, part});                                                           \
-    else if (wide)                                                                             \
-      gemm_x3w_kernel<false, false, LW, false><<<grid, kXThreads, 0, st>>>(                    \
-          M, N, K, A, lda, B, ldb, nullptr, 0.f, 0, C, ldc, K > 0 ? K : 1, nullptr, av, bv,    \
-          ProjEpi{vec, cols, part});                                                           \
-    else if (x3)                                                                               \
-      gemm_x3s_kernel<false, false, LW><<<grid, kThreads, 0, st>>>(                            \
-          M, N, K, A, lda, B, ldb, nullptr, 0.f, 0, C, ldc, K > 0 ? K : 1, nullptr, av, bv,    \
-          ProjEpi{vec, cols, part});                                                           \
-    else                                                                                       \
-      gemm_f32_kernel<false, false, LW><<<grid, kThreads, 0, st>>>(                            \
-          M, N, K, A, lda, B, ldb, nullptr, 0.f, 0, C, ldc, K > 0 ? K : 1, nullptr, av, bv,    \
-          ProjEpi{vec, cols, part});                                                           \
-  } while (0)
-  switch (logw) {
-    case 5: MVML_PROJ(5); break;
-    case 4: MVML_PROJ(4); break;
-    case 3: MVML_PROJ(3); break;
-    default: MVML_PROJ(2); break;
+  TileArgs a{M, N, K, A, lda, B, ldb, nullptr, 0.f, 0, C, ldc, K > 0 ? K : 1, nullptr, av, bv,
+             dim3(wide ? x3w_grid_x(tiles, 1) : (unsigned)tiles, 1), st, "gemm_f32_kernel(proj)"};
+  a.epi = ProjEpi{vec, cols, part};
+  const bool fast = x3w_fast(false, false, M, N, K, av, bv);
+  if (hf && wide) {
+    a.amax = amx;
+    return launch_x3w(a, false, false, logw, fast, 2);
   }
-#undef MVML_PROJ
-  return check_launch("gemm_f32_kernel(proj)");
+  if (bf) return launch_x3w(a, false, false, logw, fast, 1);
+  if (wide) return launch_x3w(a, false, false, logw, fast, 3);
+  if (x3) return launch_x3s(a, false, false, logw);
+  return launch_f32(a, false, false, logw);
 }
 }  // namespace mvml
-
-extern "C" size_t mvml_colsum_workspace_size(int64_t M, int64_t N) {
-  return carve_size((size_t)colsum_splits(M, N) * N * sizeof(float));
-}
-
-extern "C" int mvml_colsum_f32(int64_t M, int64_t N, const float* X, int64_t ldx, float alpha,
-                               float beta, float* out, void* workspace, size_t workspace_bytes,
-                               void* stream) {
-  clear_error();
-  MVML_REQUIRE(M >= 0 && N >= 0 && ldx >= N, "colsum: bad shape");
-  if (N == 0) return MVML_OK;
-  if (workspace_bytes < mvml_colsum_workspace_size(M, N) || !workspace) {
-    set_error("colsum: workspace too small");
-    return MVML_ERR_WORKSPACE;
-  }
-  hipStream_t st = as_stream(stream);
-  const int S = colsum_splits(M, N);
-  const int64_t rows_per = ceil_div(M > 0 ? M : 1, S);
-  float* part = static_cast<float*>(workspace);
-  dim3 g1((unsigned)ceil_div(N, 256), (unsigned)S);
-  colsum_partial_kernel<<<g1, 256, 0, st>>>(M, N, X, ldx, rows_per, part);
-  colsum_final_kernel<<<(unsigned)ceil_div(N, 16), 256, 0, st>>>(N, S, part, N, alpha, beta, out);
-  return check_launch("colsum");
-}
 
 // ---- weight gradient + bias gradient from one read of the gradient ------------------------
 // C[M][N] = A^T B^T with both operands k-major (A = gY [K][lda]: a layer's weight gradient,
@@ -2871,9 +2052,8 @@ extern "C" int mvml_gemm_f16x2_amax_colsum(int64_t M, int64_t N, int64_t K, cons
                          stream, 1, BatchStrides{}, am);
     if (rc || sum_n == 0) return rc;
     const int parts = 2 * plan_gemm(kPrecF16x2, M, N, K).S;
-    colsum_final_kernel<<<(unsigned)ceil_div(sum_n, 16), 256, 0, st>>>(sum_n, parts, extra + sum_off, M, alpha,
-                                                                       0.f, sum_out);
-    return check_launch("colsum_final_kernel(gemm row sums)");
+    return colsum_final_launch(sum_n, parts, extra + sum_off, M, alpha, 0.f, sum_out, st,
+                               "colsum_final_kernel(gemm row sums)");
   }
   int rc = gemm_launch(kPrecF16x2, 1, 1, M, N, K, A, lda, B, ldb, nullptr, 0.f, 0, C, ldc, workspace, gws, stream,
                        1, BatchStrides{}, AmaxPtrs{amax_a, amax_b});
@@ -2961,7 +2141,7 @@ static int wide_step_fwd(
     const uint32_t* amax_w1, void* stream, const float* Wi0, const float* Wi1) {
   const int64_t N = 4 * (int64_t)D;
   MVML_REQUIRE(M0 > 0 && M1 > 0 && D > 0 && K >= 0 && K % 4 == 0 && ldw >= K && ldw % 4 == 0 &&
-                   ldgx >= N && ldh >= D && amax_a && amax_w0 && amax_w1 && MVML_X3W_LDSEPI,
+                   ldgx >= N && ldh >= D && amax_a && amax_w0 && amax_w1,
                "bilstm_wide_step_fwd: bad shape");
   MVML_REQUIRE(K == 0 || (A0 && A1 && lda >= K && lda % 4 == 0 && (uintptr_t)A0 % 16 == 0 &&
                           (uintptr_t)A1 % 16 == 0),
@@ -2975,26 +2155,24 @@ static int wide_step_fwd(
   e1.gx = gx1;
   const float* a0 = K ? A0 : gx0;  // K = 0 (a direction's first step): no A rows are read
   const float* a1 = K ? A1 : gx1;
+  TileArgs a{M0, N, K, a0, K ? lda : 4, W0, ldw, nullptr, 0.f, 0, nullptr, N, K > 0 ? K : 1, nullptr, 1, 1,
+             dim3(), as_stream(stream), "gemm_f32_kernel(bilstm step)"};
+  a.amax = AmaxPtrs{amax_a, amax_w0};
+  a.cep = e0;
+  a.dual = DualPtrs{a1, W1, nullptr, amax_w1, M1, e1};
   if (lstm_small_tile(std::max(M0, M1), false)) {
-    const int64_t tiles = ceil_div(std::max(M0, M1), BM) * ceil_div(N, BN);
-    const dim3 grid((unsigned)tiles, 1, 2);
-    if (Wi0 && Wi1 && K % BKT == 0)
-      gemm_f32_kernel<false, false, -1, true, true, true><<<grid, kThreads, 0, as_stream(stream)>>>(
-          M0, N, K, a0, K ? lda : 4, Wi0, K, nullptr, 0.f, 0, nullptr, N, K > 0 ? K : 1, nullptr, 1, 1,
-          ProjEpi{}, BatchStrides{}, AmaxPtrs{amax_a, amax_w0}, e0, DualPtrs{a1, Wi1, nullptr, amax_w1, M1, e1});
-    else
-      gemm_f32_kernel<false, false, -1, true, true><<<grid, kThreads, 0, as_stream(stream)>>>(
-          M0, N, K, a0, K ? lda : 4, W0, ldw, nullptr, 0.f, 0, nullptr, N, K > 0 ? K : 1, nullptr, 1, 1,
-          ProjEpi{}, BatchStrides{}, AmaxPtrs{amax_a, amax_w0}, e0, DualPtrs{a1, W1, nullptr, amax_w1, M1, e1});
-    return check_launch("gemm_f32_kernel(bilstm step)");
+    a.grid = dim3((unsigned)(ceil_div(std::max(M0, M1), BM) * ceil_div(N, BN)), 1, 2);
+    const bool pre = Wi0 && Wi1 && K % BKT == 0;  // both W ready-split (ld K)
+    if (pre) {
+      a.B = Wi0;
+      a.ldb = K;
+      a.dual.b = Wi1;
+    }
+    return launch_f32(a, false, false, -1, true, true, pre);
   }
-  const int64_t tn = ceil_div(N, XBN);
-  const int64_t tiles = std::max(ceil_div(M0, XBM), ceil_div(M1, XBM)) * tn;
-  const dim3 grid((unsigned)tiles, 1, 2);
-  gemm_x3w_kernel<false, false, -1, true, 2><<<grid, kXThreads, 0, as_stream(stream)>>>(
-      M0, N, K, a0, K ? lda : 4, W0, ldw, nullptr, 0.f, 0, nullptr, N, K > 0 ? K : 1, nullptr, 1, 1,
-      ProjEpi{}, BatchStrides{}, e0, AmaxPtrs{amax_a, amax_w0}, DualPtrs{a1, W1, nullptr, amax_w1, M1, e1});
-  return check_launch("gemm_x3w_kernel(bilstm step)");
+  a.grid = dim3((unsigned)(std::max(ceil_div(M0, XBM), ceil_div(M1, XBM)) * ceil_div(N, XBN)), 1, 2);
+  a.what = "gemm_x3w_kernel(bilstm step)";
+  return launch_x3w(a, false, false, -1, true, 2);
 }
 
 extern "C" int mvml_bilstm_wide_step_fwd(
@@ -3039,31 +2217,26 @@ static int wide_step_bwd(
                  "bilstm_wide_step_bwd: alignment");
     const int S = 2;
     const int64_t kc = k_chunk(K, S);
+    TileArgs a{R0, N, K, gn0, K, wT0, ldwT, nullptr, 0.f, 0, nullptr, N, kc, slab0, 1, 1,
+               dim3(), st, "gemm_f32_kernel(bilstm step bwd)"};
+    a.amax = AmaxPtrs{gg_amax0, amax_w0};
+    a.dual = DualPtrs{gn1, wT1, slab1, amax_w1, R1, CellEpi{}, gg_amax1};
+    int rc;
     if (lstm_small_tile(std::max(R0, R1), true)) {
-      const int64_t tiles = ceil_div(std::max(R0, R1), BM) * ceil_div(N, BN);
-      const dim3 grid((unsigned)tiles, (unsigned)S, 2);
-      if (Wi0 && Wi1 && kc % BKT == 0)
-        gemm_f32_kernel<false, false, -1, true, true, true><<<grid, kThreads, 0, st>>>(
-            R0, N, K, gn0, K, Wi0, K, nullptr, 0.f, 0, nullptr, N, kc, slab0, 1, 1, ProjEpi{},
-            BatchStrides{}, AmaxPtrs{gg_amax0, amax_w0}, CellEpi{},
-            DualPtrs{gn1, Wi1, slab1, amax_w1, R1, CellEpi{}, gg_amax1});
-      else
-        gemm_f32_kernel<false, false, -1, true, true><<<grid, kThreads, 0, st>>>(
-            R0, N, K, gn0, K, wT0, ldwT, nullptr, 0.f, 0, nullptr, N, kc, slab0, 1, 1, ProjEpi{},
-            BatchStrides{}, AmaxPtrs{gg_amax0, amax_w0}, CellEpi{},
-            DualPtrs{gn1, wT1, slab1, amax_w1, R1, CellEpi{}, gg_amax1});
-      int rc = check_launch("gemm_f32_kernel(bilstm step bwd)");
-      if (rc) return rc;
+      a.grid = dim3((unsigned)(ceil_div(std::max(R0, R1), BM) * ceil_div(N, BN)), (unsigned)S, 2);
+      const bool pre = Wi0 && Wi1 && kc % BKT == 0;  // both W^T ready-split (ld K)
+      if (pre) {
+        a.B = Wi0;
+        a.ldb = K;
+        a.dual.b = Wi1;
+      }
+      rc = launch_f32(a, false, false, -1, true, true, pre);
     } else {
-    const int64_t tiles = std::max(ceil_div(R0, XBM), ceil_div(R1, XBM)) * ceil_div(N, XBN);
-    const dim3 grid((unsigned)tiles, (unsigned)S, 2);
-    gemm_x3w_kernel<false, false, -1, true, 2><<<grid, kXThreads, 0, st>>>(
-        R0, N, K, gn0, K, wT0, ldwT, nullptr, 0.f, 0, nullptr, N, kc, slab0, 1, 1, ProjEpi{},
-        BatchStrides{}, CellEpi{}, AmaxPtrs{gg_amax0, amax_w0},
-        DualPtrs{gn1, wT1, slab1, amax_w1, R1, CellEpi{}, gg_amax1});
-    int rc = check_launch("gemm_x3w_kernel(bilstm step bwd)");
-    if (rc) return rc;
+      a.grid = dim3((unsigned)(std::max(ceil_div(R0, XBM), ceil_div(R1, XBM)) * ceil_div(N, XBN)), (unsigned)S, 2);
+      a.what = "gemm_x3w_kernel(bilstm step bwd)";
+      rc = launch_x3w(a, false, false, -1, true, 2);
     }
+    if (rc) return rc;
   }
   LstmBwdArgs a0, a1;
   a0.M = M0; a0.R = R0; a0.gout = gout0; a0.ldgo = ldgo; a0.slab = slab0; a0.act = act0; a0.c = c0;

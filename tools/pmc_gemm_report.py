@@ -59,7 +59,7 @@ def main():
         v = c.get(k)
         return sum(v) / len(v) if v else float("nan")
 
-    print("kernel <AK, BKM, EPI, FAST, NP, BPS, ROWS, EX>  (x3w/x3s/f32 as in csrc/gemm_f32.hip;")
+    print("kernel <AK, BKM, EPI, FAST, NP, BPS, ROWS, EX>  (x3w/x3s/f32: the tile kernels of csrc/gemm_f32.hip;")
     print("  planes <APS, ROWS, EX, CELL, BK, ABL> as in csrc/gemm_planes.hip); clk_GHz = GRBM_GUI_ACTIVE / 8 / duration")
     hdr = ("calls", "avg_us", "step%", "mfma_busy", "issue", "parked", "stalled", "lds_stall",
            "lds_conf", "valu/mfma", "clk_GHz")
