@@ -87,28 +87,28 @@ def node_group_plan_ref(node_offsets, in_rowptr, group_atoms=64, win_atoms=128, 
     """Node-group plan of mvml_build_node_groups (launch geometry; no reference counterpart):
     group g starts at the first atom of the molecule containing atom group_atoms*g; kind bit 0
     = forward LDS kernel (atom, edge and in-degree caps), bit 1 = backward LDS kernel (atom and
-    edge caps).  Returns (starts [G+1], kinds [G], fwd fallback set, bwd fallback set)."""
+    edge caps), bit 2 = the group fits the big LDS window (big_atoms atoms, big_edge_cap
+    in-edges, any in-degree).  Empty groups have kind 0 and are on no list.  Returns (starts
+    [G+1], kinds [G], fwd fallback set, bwd fallback set).  Whole-array numpy: the largest plans
+    tested have over 10^5 groups."""
     node_offsets = np.asarray(node_offsets, dtype=np.int64)
     rp = np.asarray(in_rowptr, dtype=np.int64)
     N = int(node_offsets[-1])
     G = -(-N // group_atoms) if N > 0 else 0
-    starts = np.empty(G + 1, dtype=np.int32)
-    for g in range(G):
-        m = np.searchsorted(node_offsets, g * group_atoms, side="right") - 1
-        starts[g] = node_offsets[m]
+    starts = np.empty(G + 1, dtype=np.int64)
+    m = np.searchsorted(node_offsets, np.arange(G, dtype=np.int64) * group_atoms, side="right") - 1
+    starts[:G] = node_offsets[m]
     starts[G] = N
     kinds = np.zeros(G, dtype=np.int32)
-    fwd, bwd = set(), set()
-    for g in range(G):
-        a0, a1 = int(starts[g]), int(starts[g + 1])
-        if a1 <= a0:
-            continue
-        fits = a1 - a0 <= win_atoms and rp[a1] - rp[a0] <= edge_cap
-        dmax = int(np.max(rp[a0 + 1:a1 + 1] - rp[a0:a1]))
-        big = a1 - a0 <= big_atoms and rp[a1] - rp[a0] <= big_edge_cap
-        kinds[g] = (1 if fits and dmax <= deg_cap else 0) | (2 if fits else 0) | (4 if big else 0)
-        if not kinds[g] & 1:
-            fwd.add(g)
-        if not kinds[g] & 2:
-            bwd.add(g)
-    return starts, kinds, fwd, bwd
+    live = np.flatnonzero(starts[1:] > starts[:-1])
+    if live.size:
+        a0, a1 = starts[live], starts[live + 1]
+        atoms, edges = a1 - a0, rp[a1] - rp[a0]
+        # live groups tile [0, N) in order, so each one's atoms are one reduceat segment
+        dmax = np.maximum.reduceat(np.diff(rp[:N + 1]), a0)
+        fits = (atoms <= win_atoms) & (edges <= edge_cap)
+        big = (atoms <= big_atoms) & (edges <= big_edge_cap)
+        kinds[live] = (fits & (dmax <= deg_cap)) * 1 + fits * 2 + big * 4
+    fwd = set(live[(kinds[live] & 1) == 0].tolist())
+    bwd = set(live[(kinds[live] & 2) == 0].tolist())
+    return starts.astype(np.int32), kinds, fwd, bwd

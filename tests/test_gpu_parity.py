@@ -26,7 +26,8 @@ def _to_dev(sb, group_size=None):
     ([11, 23, 80, 5, 1, 40, 23], False),
     ([150, 300, 220], True),
     ([1] * 5, False),
-    # one wave per molecule up to 256 atoms / 1024 edges, a workgroup for the rest, in one batch
+    # one wave per molecule in two sizes (up to 128 atoms / 512 edges, up to 1024 / 4096), in
+    # one batch; the limits themselves are straddled in test_gpu_batching_tiers.py
     ([25, 300, 255, 257, 1, 64, 90, 256], True),
     ([256, 255, 257, 2, 3], False),
 ])
