@@ -82,8 +82,9 @@ const char* mvml_version(void);
                                    molecule / big windows + gather kernel.  The Python layer sets
                                    it per call for batches of large molecules; 2 = the same
                                    with the edge softmax as its own launch first */
-#define MVML_OPT_DST_UNR 10     /* MVML_DST_UNR: projection rows in flight per wave of the
-                                   destination-wave forward (0 = the default per width; tuning) */
+#define MVML_OPT_DST_UNR 10     /* (round 5: rows in flight per wave of the destination-wave
+                                   forward, a tuning A/B; removed — the option is accepted and
+                                   ignored) */
 #define MVML_OPT_SMALLK 11      /* MVML_SMALLK: 1 (default) mvml_gemm_f16x2_rows products with
                                    K <= 96 (layer 1's projection) on the wave-per-64-columns
                                    memory kernel (non-temporal stores; 2 = plain stores;

@@ -141,7 +141,7 @@ inline int proj_logw(int F) {
   } while (0)
 
 namespace mvml {
-// Head count and width of the graph-attention aggregations (gat_agg.hip, gatv2_agg.hip); each
+// Head count and width of the graph-attention aggregations (gat_agg_common.h, gatv2_agg.hip); each
 // file checks `mode` itself, in its own words.
 inline int check_heads(int H, int F, const char* who) {
   MVML_REQUIRE(H == 1 || H == 2 || H == 4 || H == 8, "%s: num_heads must be 1, 2, 4 or 8 (got %d)", who, H);

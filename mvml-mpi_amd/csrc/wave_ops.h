@@ -1,4 +1,4 @@
-// Device helpers shared by the wave-per-row kernels (gat_agg.hip, gatv2_agg.hip, the readouts):
+// Device helpers shared by the wave-per-row kernels (gat_agg_*.hip, gatv2_agg.hip, the readouts):
 // lane broadcasts, float4 arithmetic and access, per-head selects and the H-value all-reduce.
 // All are forced inline, so a kernel's machine code does not depend on whether its helpers come
 // from here or from its own file (tools/codeobj_diff.py compares them; DESIGN.md, "GATv2").
@@ -51,7 +51,7 @@ __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 
 // a[h] of H wave-uniform per-head values, h per lane, as a select chain.  Two forms:
-// by reference (gat_agg.hip): the array stays in registers in every instance there
+// by reference (gat_agg_fwd.hip, gat_agg_bwd.hip): the array stays in registers in every instance there
 template <int H>
 __device__ __forceinline__ float pick(const float (&a)[H], int h) {
   float r = a[0];

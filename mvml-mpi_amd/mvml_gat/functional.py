@@ -307,9 +307,9 @@ def colsum(X, M, N, ldx, out, beta=0.0, offset=0, alpha=1.0):
 
 # Kernel paths picked per call from the batch's molecule sizes (host counts, no device work):
 # "large" batches have half their atoms or more in molecules past the LDS molecule window
-# (FLAT_SRC_MIN_ATOMS, gat_agg.hip kWinL) — BASELINE config 5.
+# (FLAT_SRC_MIN_ATOMS, gat_agg_common.h kWinL) — BASELINE config 5.
 #  * Aggregation forward by destination wave (one wave per atom gathers whole projection rows
-#    from L2; csrc/gat_agg.hip gat_agg_fwd_dst_kernel), every layer (MVML_DST_FWD_POLICY = all |
+#    from L2; csrc/gat_agg_fwd.hip gat_agg_fwd_dst_kernel), every layer (MVML_DST_FWD_POLICY = all |
 #    auto: the head-mean layer on large batches only | off): on small-molecule batches with the
 #    edge softmax as its own launch first (dst_fwd = 2: 2.9 / 3.4 ms against the molecule
 #    window's 3.5 / 3.7 at config 3), on large ones inside the wave (dst_fwd = 1: 4.5 / 6.2 ms
@@ -317,7 +317,7 @@ def colsum(X, M, N, ldx, out, beta=0.0, offset=0, alpha=1.0):
 #  * Flatten layers' aggregation backward by source atom in one pass (option flat_src = 2,
 #    gat_flat_bwd_src1_kernel) on large batches (MVML_FLAT_SRC_AUTO = 0 turns it off).
 FLAT_SRC_AUTO = os.environ.get("MVML_FLAT_SRC_AUTO", "1") == "1"
-FLAT_SRC_MIN_ATOMS = 128  # the LDS molecule window (gat_agg.hip kWinL)
+FLAT_SRC_MIN_ATOMS = 128  # the LDS molecule window (gat_agg_common.h kWinL)
 DST_FWD_POLICY = os.environ.get("MVML_DST_FWD_POLICY", "all")
 DST_FWD_KIND = int(os.environ.get("MVML_DST_FWD_KIND", "0"))  # 0: by batch (see above)
 #  * The ELU link (EluLink, below): the second layer's data-gradient GEMM applies ELU' in its

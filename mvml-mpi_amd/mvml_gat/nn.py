@@ -33,7 +33,7 @@ class GATConv(nn.Module):
         super().__init__()
         if feat_drop or attn_drop:
             raise NotImplementedError("GATConv: feat_drop/attn_drop > 0 are not on the fused path")
-        # the aggregation kernels' range (csrc/gat_agg.hip check_shapes): refuse here, not in forward
+        # the aggregation kernels' range (csrc/gat_agg_common.h check_shapes): refuse here, not in forward
         if num_heads not in (1, 2, 4, 8) or out_feats <= 0 or out_feats % 4 or num_heads * out_feats > 2048:
             raise ValueError(
                 f"GATConv: num_heads must be 1, 2, 4 or 8 and out_feats a positive multiple of 4 with "

@@ -1,4 +1,4 @@
-"""mvml_gat_agg_fwd_res / mvml_gat_agg_bwd_res (csrc/gat_agg.hip) through the C ABI: the residual
+"""mvml_gat_agg_fwd_res / mvml_gat_agg_bwd_res (csrc/gat_agg_*.hip) through the C ABI: the residual
 as an input of its own (R, its own row pitch), no residual (R = NULL), each with and without a
 bias, against float64 (oracle.gnn_ref.gat_agg_ref at the same cut, with R = zeros for no residual
 and bias = zeros for no bias), on every kernel-path option list of test_gpu_agg_shapes._paths.

@@ -1,4 +1,4 @@
-"""The GAT aggregation (mvml_gat_agg_fwd / mvml_gat_agg_bwd, csrc/gat_agg.hip) through the C ABI
+"""The GAT aggregation (mvml_gat_agg_fwd / mvml_gat_agg_bwd, csrc/gat_agg_*.hip) through the C ABI
 against float64 (oracle.gnn_ref.gat_agg_ref, the same cut: Z, R and [el | er] given) over the
 dispatch grid: every head count H in {1, 2, 4, 8}, the column chunks CW 32 / 16 / 8 / 4 of the
 window kernels, the destination-wave forward's NJ = 1, 2, 3, 4, 8 slots with full and partly
@@ -177,7 +177,7 @@ def test_agg_against_float64(H, F, mode, graph):
         results[name] = res
     print(f"worst err/budget {worst[1]} on {worst[2]}: {worst[0]:.3f}")
 
-    # Bitwise promises of the source (csrc/gat_agg.hip): the destination-wave forward sums each row
+    # Bitwise promises of the source (csrc/gat_agg_*.hip): the destination-wave forward sums each row
     # in edge order from 0 as the window / gather kernels do, with softmax_pair's arithmetic — on
     # molecules without hubs (the gather kernel's hub pass sums long rows in another order) — and
     # its two kinds (softmax fused / as its own launch) agree on every graph.

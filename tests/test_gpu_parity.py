@@ -61,7 +61,7 @@ def test_node_group_plan_bit_exact(sizes, hubs):
     np.testing.assert_array_equal(plan[:G + 1], starts)
     np.testing.assert_array_equal(plan[G + 1:2 * G + 1], kinds)
     nf, nb = int(plan[2 * G + 1]), int(plan[2 * G + 2])
-    # the fallback lists come in group order (XCD-contiguous walks, gat_agg.hip list_block)
+    # the fallback lists come in group order (XCD-contiguous walks, gat_agg_common.h list_block)
     assert plan[2 * G + 3:2 * G + 3 + nf].tolist() == sorted(fwd)
     assert plan[3 * G + 3:3 * G + 3 + nb].tolist() == sorted(bwd)
 

@@ -2,19 +2,31 @@
 float64 oracle (oracle/gnn_ref.py) on seeded batches drawn from the SAME generators the bench
 uses (mvml_gat.synth.config2 / config3 / config5), forward + backward, every parameter gradient.
 
-Which aggregation kernels each case reaches (csrc/gat_agg.hip launch_fwd / launch_bwd; H = 4):
+Which aggregation kernels each case reaches (csrc/gat_agg_fwd.hip launch_fwd, gat_agg_bwd.hip
+launch_bwd; H = 4, so both layers hold 3 float4 column slots per lane).  The Python layer picks the
+path per batch (mvml_gat.functional: _fwd_path, flat_src); the tests below that name an option
+switch it themselves, and so reach the other kernels:
 
 * config 5 (150-400 atoms, 1-4 hubs of in-degree 32-128): every molecule is larger than the
-  128-atom LDS window, so the node-group plan sends ALL groups to the fallbacks:
-    layer 0 (F = 192, flatten + ELU): gat_softmax_kernel<4>, gat_agg_fwd_gather_kernel<4, 64, 0>,
-                                      gat_agg_bwd_dst_kernel<4, 3>, gat_agg_bwd_src_kernel<4, 3>
-    layer 1 (F = 384, mean):          gat_agg_fwd_gather_kernel<4, 64, 1>,
-                                      gat_agg_bwd_dst_kernel<4, 6>, gat_agg_bwd_src_kernel<4, 6>
-* config 3 (KEGG-like 11-80 atoms, GraphNorm groups of 64 molecules, the bench shape): the LDS
-  kernels gat_agg_fwd_lds_kernel<4, 64, {0,1}, 1024> and gat_agg_bwd_lds_kernel<4, {0,1}, 64>
-  (one or two passes per node group), the fallbacks for groups that hold an 80-atom molecule
-  next to others (> 128 atoms) or an in-degree > 5 atom.
-* config 2 (25 atoms, 27 bonds): single GAT layers 0 and 1 on the LDS kernels.
+  128-atom LDS window, a "large" batch: the forward by destination wave with the softmax in the
+  wave (dst_fwd = 1), the backward by source atom:
+    layer 0 (F = 192, flatten + ELU): gat_agg_fwd_dst_kernel<4, 0, 3, 1, SM, LR>,
+                                      gat_flat_bwd_src1_kernel<4, 3, MODE, 1> (flat_src = 2)
+    layer 1 (F = 384, mean):          gat_agg_fwd_dst_kernel<4, 1, 3, 1, SM, LR>,
+                                      gat_mean_bwd_src_kernel<4, 2> (mean_src = 1)
+  each source-atom backward followed by gat_mean_bwd_softmax_kernel<4> and
+  gat_mean_bwd_gel_kernel<4>.  With dst_fwd = 0, big_window = 0 and mean_src = 0 the node-group
+  plan sends ALL its groups to the fallbacks (gat_agg_fwd_gather_kernel<4, 32, {0,1}>,
+  gat_agg_bwd_dst_kernel / gat_agg_bwd_src_kernel<4, 3> and <4, 6>); with big_window = 1 to the big
+  windows (gat_agg_fwd_lds_kernel<4, 16, M, 512, 512, 2432, true> and the backward likewise).
+* config 3 (KEGG-like 11-80 atoms, GraphNorm groups of 64 molecules, the bench shape): a "small"
+  batch: gat_softmax_dst4_kernel, then gat_agg_fwd_dst_kernel<4, {0,1}, 3, 1, !SM> (dst_fwd = 2);
+  layer 0's backward on the molecule window gat_agg_bwd_lds_kernel<4, 0, 32> (one or two passes
+  per node group) with the per-atom pair for groups that hold an 80-atom molecule next to others
+  (> 128 atoms), layer 1's by source atom.  With dst_fwd = 0: gat_agg_fwd_lds_kernel<4, 32,
+  {0,1}, 512> and the gather kernel for such groups or an in-degree > 5 atom; with mean_src = 0:
+  gat_agg_bwd_lds_kernel<4, 1, 32>.
+* config 2 (25 atoms, 27 bonds): single GAT layers 0 and 1, the small-batch kernels.
 * hub case at layer 0: flatten + ELU through the fallback kernels at the production width.
 
 Bar (BASELINE.json north_star): outputs within 1e-5 norm-wise relative error of float64.
