@@ -5,9 +5,11 @@ import pytest
 import torch
 
 SUPPORTED = "16 <= hidden_feats[-1] <= 384"
+# the ends, and every 64-column group boundary of the kernels with the width just above it
+ACCEPTED = [16, 68, 128, 132, 196, 256, 260, 320, 324, 384]
 
 
-@pytest.mark.parametrize("D", [16, 128, 384])
+@pytest.mark.parametrize("D", ACCEPTED)
 def test_mvfusion_constructs_with_oracle_layout(D):
     from mvml_gat import MVFusion
     from oracle.fusion_ref import MVFusionRef
@@ -23,7 +25,7 @@ def test_mvfusion_constructs_with_oracle_layout(D):
     assert mod.mlp[0].in_features == 12 * (D - 2) and mod.linear_q.out_features == 12 * D
 
 
-@pytest.mark.parametrize("D", [16, 128, 384])
+@pytest.mark.parametrize("D", ACCEPTED)
 def test_mvp_constructs_with_oracle_layout(D):
     from mvml_gat.mvp import MVP
     from oracle.fusion_ref import MVPRef

@@ -5,7 +5,9 @@ oracle/fusion_ref.py MVFusionRef(D, 12, 11) on identical seeded weights and inpu
 
 Widths: 16 (one partial 64-column group, 14 output columns, all in wave 0's conv tile), 20 (no
 multiple of 8), 64 (exactly one full group), 100 (a partial second group, the conv tiles end
-inside wave 3), 192 (the reference's other layer size), 380 (six groups, the last partial).
+inside wave 3), 192 (the reference's other layer size), 380 (six groups, the last partial); and
+every group boundary 128, 256, 320 with the width just above each of the five (68 .. 324), so that
+every <kMask, kV> instance is launched and a width mapped to the wrong one fails.
 Batches: 300 gives the fused kernels (256 workgroups) more than one molecule per workgroup with a
 short last run."""
 import math
@@ -20,11 +22,17 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 TOL = 1e-5
 WIDTHS = [16, 20, 64, 100, 192, 380]
+# every 64-column group boundary and the width just above it: with WIDTHS these launch the masked
+# instances of all six group counts (kV = 4 at 196 and 256, kV = 5 at 260 and 320) and sit on both
+# sides of every step of the width dispatch.  Two small batches: they are here to reach the
+# instance, not the molecule loop.
+BOUNDARY_WIDTHS = [68, 128, 132, 196, 256, 260, 320, 324]
+WIDTH_BATCHES = ([(D, B) for D in WIDTHS for B in (1, 5, 67, 300)] +
+                 [(D, B) for D in BOUNDARY_WIDTHS for B in (1, 5)])
 
 
 @pytest.mark.parametrize("path", ["fused", "fold", "qkv"])
-@pytest.mark.parametrize("B", [1, 5, 67, 300])
-@pytest.mark.parametrize("D", WIDTHS)
+@pytest.mark.parametrize("D,B", WIDTH_BATCHES)
 def test_fusion_width_parity(D, B, path, monkeypatch):
     """test_fusion_forward_backward_parity at width D: natural biases, the oracle on the
     product's own ReLU sides; logits, the three input gradients and every parameter gradient
@@ -55,7 +63,7 @@ def test_fusion_width_parity(D, B, path, monkeypatch):
 
 
 @pytest.mark.parametrize("B", [1, 300])
-@pytest.mark.parametrize("D", [16, 100, 380])
+@pytest.mark.parametrize("D", [16, 100, 256, 260, 380])
 def test_attn_conv_fused_matches_unfused_at_width(D, B, monkeypatch):
     """test_attn_conv_fused_matches_unfused at width D: logits, input gradients and the Q / K / V
     weight gradients bit-identical; the Conv2d weight / bias gradients within 1e-5."""
@@ -106,7 +114,7 @@ class _Guarded:
         assert not torch.any(self.view == SENTINEL), name + ": elements left unwritten"
 
 
-@pytest.mark.parametrize("D", [16, 100])
+@pytest.mark.parametrize("D", [16, 100, 196, 260])
 def test_width_abi_stores_stay_inside_rows(D):
     """mvml_token_attn_fold_fwd / _bwd and mvml_attn_conv_fwd / _bwd called directly: every
     output lives in a sentinel-filled allocation (g_pv with ldg > 2 * 12 * D, g_k with ldgk > D)
