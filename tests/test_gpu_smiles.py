@@ -11,14 +11,16 @@ DEV = "cuda"
 TOL = 1e-5
 
 
-def _batch(B, seed, Tmax=60, ragged=True, space=False):
+def _batch(B, seed, Tmax=60, ragged=True, space=False, lens=None):
     from mvml_gat.smiles import collate_smiles, tokens_struct
     vocab = tokens_struct()
     rng = np.random.default_rng(seed)
     chars = [t for t in vocab.tokens if len(t) == 1 and t != ' '] + ['X', '%']  # '%','X' -> unk
     if space:  # the pad token ' ' (index 0) inside live positions
         chars += [' '] * 4
-    lens = rng.integers(1, Tmax + 1, size=B) if ragged else np.full(B, Tmax)
+    if lens is None:
+        lens = rng.integers(1, Tmax + 1, size=B) if ragged else np.full(B, Tmax)
+    assert len(lens) == B
     smiles = ["".join(rng.choice(chars, size=int(n))) for n in lens]
     return vocab, collate_smiles(smiles, vocab)
 
@@ -104,20 +106,23 @@ def test_wide_step_plans_bitwise(monkeypatch):
         assert torch.equal(a, b)
 
 
-def _rnn_parity(B, Tmax, layers, ragged, space, H=384):
+def _rnn_parity(B, Tmax, layers, ragged, space, H=384, lens=None, E=128):
+    """Output and every parameter gradient within TOL of the float64 restatement; explicit
+    ``lens`` (length B) replace the random ones.  Returns {name: rel_err}."""
     from mvml_gat.smiles import RNNModule
     from oracle.smiles_ref import RNNModuleRef
     torch.manual_seed(B + layers)
-    vocab, batch = _batch(B, B * 7 + Tmax, Tmax, ragged, space)
+    vocab, batch = _batch(B, B * 7 + Tmax, Tmax, ragged, space, lens)
     if space:
         assert any((row[:n] == 0).any() for row, n in zip(batch["smiles"], batch["seq_len"]))
-    ref = RNNModuleRef(39, 128, H, layers, 384, 0.5).double().eval()
-    mod = RNNModule(vocab, 128, H, layers, 384, 0.5).to(DEV).eval()
+    ref = RNNModuleRef(39, E, H, layers, 384, 0.5).double().eval()
+    mod = RNNModule(vocab, E, H, layers, 384, 0.5).to(DEV).eval()
     mod.load_state_dict({k: v.float() for k, v in ref.state_dict().items()})
     zr = ref(batch)
     zd = mod({"smiles": batch["smiles"].to(DEV), "seq_len": batch["seq_len"]})
     assert zd.shape == (B, 384)
-    assert rel_err(zd, zr) < TOL
+    errs = {"out": rel_err(zd, zr)}
+    assert errs["out"] < TOL
     g = torch.Generator().manual_seed(B)
     up = torch.randn(zr.shape, generator=g, dtype=torch.float64)
     (zr * up).sum().backward()
@@ -127,7 +132,9 @@ def _rnn_parity(B, Tmax, layers, ragged, space, H=384):
         if pr[name].grad is None:
             assert p.grad is None or float(p.grad.abs().max()) == 0.0, name
             continue
-        assert rel_err(p.grad, pr[name].grad) < TOL, name
+        errs[name] = rel_err(p.grad, pr[name].grad)
+        assert errs[name] < TOL, (name, errs[name])
+    return errs
 
 
 def test_rnn_module_deterministic():
