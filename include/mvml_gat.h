@@ -90,6 +90,9 @@ const char* mvml_version(void);
                                    memory kernel (non-temporal stores; 2 = plain stores;
                                    3 .. 6, 10: timing variants, tools/smallk_bench.py);
                                    0 = the 256x256 tile */
+#define MVML_OPT_GCN_SUBWAVE 12 /* MVML_GCN_SUBWAVE: mvml_gcn_agg at D <= 64 with four rows per
+                                   wave, 16 lanes each (1), or one row per wave as at every
+                                   other width (0); the two give the same bits */
 int mvml_set_option(int option, int value);
 int mvml_get_option(int option);
 
@@ -558,6 +561,38 @@ int mvml_gatv2_agg_bwd(int64_t num_nodes, const int32_t* in_rowptr, const int32_
  * share_weights adds gZR onto gZL before the single weight block's products. */
 int mvml_add_cols_f32(int64_t rows, int cols, const float* src, int64_t lds, float* dst, int64_t ldd,
                       void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * GraphConv aggregation (dgl 0.9.1 GraphConv.forward: update_all(copy_u, sum) between its two
+ * degree normalisations; restated, parity with dgl unpinned), over the rows of one CSR:
+ *   out[v, 0:D) = act( row_scale[v] * sum_s nbr_scale[nbr[s]] * X[nbr[s], 0:D) + bias[0:D) ),
+ * s ascending over [rowptr[v], rowptr[v+1]), the sum started from 0.
+ * nbr_scale / row_scale / bias may be NULL (1, 1, 0).  act: 0 none, 1 ReLU.
+ * A row without entries gives act(bias).  D a positive multiple of 4, <= 2048.
+ * X, out and bias 16-byte aligned; ldx, ldo multiples of 4 and >= D; out must not alias X (the
+ * address ranges of their rows must not meet).
+ * Columns [D, ld) of X are never read and of out never written.
+ * out_amax / out_row_amax (may be NULL) as in mvml_gat_agg_fwd.
+ * Anything else: MVML_ERR_INVALID before any launch, nothing written.
+ * The forward of a GraphConv is this entry over (in_rowptr, in_src) with nbr_scale = src_scale and
+ * row_scale = dst_scale; the input gradient of the sum is the same entry over (out_rowptr,
+ * out_dst) with the two scales swapped and no bias or act:
+ *   dX[u] = src_scale[u] * sum_{u -> w} dst_scale[w] * g[w].
+ * Both are gathers: no atomics, bitwise repeatable; every product and sum is rounded once in a
+ * fixed order, so a row's bits depend on neither the kernel instance (MVML_OPT_GCN_SUBWAVE) nor
+ * the batch the row is computed in.
+ * ------------------------------------------------------------------------------------- */
+int mvml_gcn_agg(int64_t num_nodes, const int32_t* rowptr, const int32_t* nbr, const float* X,
+                 int64_t ldx, int D, const float* nbr_scale, const float* row_scale,
+                 const float* bias, int act, float* out, int64_t ldo, uint32_t* out_amax,
+                 uint32_t* out_row_amax, void* stream);
+/* GraphConv's degree factors from the two CSR row pointers, degrees clamped to >= 1.
+ * norm 0 none (writes 1s), 1 both: src = outdeg^-1/2, dst = indeg^-1/2;
+ * 2 right: src = 1, dst = 1/indeg; 3 left: src = 1/outdeg, dst = 1.
+ * src_scale, dst_scale: [num_nodes].  A row pointer whose degrees the norm does not read may be
+ * NULL. */
+int mvml_gcn_norm_scales(int64_t num_nodes, const int32_t* in_rowptr, const int32_t* out_rowptr,
+                         int norm, float* src_scale, float* dst_scale, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Set2Set (dgl 0.9.1, model.py:82-84, 92) building blocks.

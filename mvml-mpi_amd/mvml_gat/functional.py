@@ -1449,3 +1449,227 @@ class GATv2LayerFunction(torch.autograd.Function):
             gX = None
         return (gX, g_ws, g_wd, g_wr, g_bs, g_bd, g_br, g_av.view(ctx.attn_shape),
                 None, None, None, None, None, None)
+
+
+# ---- GCN (dgl 0.9.1 GraphConv; csrc/gcn_agg.hip) ------------------------------------------------
+GCN_NORMS = {"none": 0, "both": 1, "right": 2, "left": 3}
+
+
+def gcn_agg_bytes(N, E, D):
+    """Algorithmic HBM bytes of one mvml_gcn_agg: read X and write out once, the row pointers, the
+    neighbour ids and the two scale vectors (re-gathers of rows not counted)."""
+    return 4 * (2 * N * D + N + 1 + E + 2 * N)
+
+
+def gcn_scales(g, norm):
+    """(src_scale, dst_scale) of GraphConv's `norm` on the device batch g (mvml_gcn_norm_scales),
+    None where the factor is 1 for every atom.  Computed once per (graph, norm) and kept on the
+    batch; BatchedMolGraph.recollate() drops them with the indices it rebuilds."""
+    if norm not in GCN_NORMS:
+        raise ValueError(f'Invalid norm value. Must be either "none", "both", "right" or "left". But got "{norm}".')
+    if norm == "none":
+        return None, None
+    cache = g._dev.setdefault("gcn_scales", {})
+    if norm not in cache:
+        N = g.num_nodes()
+        s = torch.empty((2, max(N, 1)), dtype=torch.float32, device=g.device)
+        call("mvml_gcn_norm_scales", N, ptr(g.in_rowptr), ptr(g.out_rowptr), GCN_NORMS[norm], ptr(s[0]), ptr(s[1]),
+             _stream(g.device))
+        cache[norm] = (s[0] if norm != "right" else None, s[1] if norm != "left" else None)
+    return cache[norm]
+
+
+def gcn_agg(X, ldx, D, g, scales, transpose=False, bias=None, act=0, rows=False):
+    """mvml_gcn_agg of the [N, D] rows of X (row stride ldx) over g's in-CSR, or (transpose) the
+    adjoint over its out-CSR with the two scales swapped; a new dense [N, D] tensor, with its
+    per-row maxima recorded on it (fold_rows) when `rows`."""
+    N, E = g.num_nodes(), g.num_edges()
+    dev = X.device
+    out = torch.empty((N, D), dtype=torch.float32, device=dev)
+    rmx = torch.empty(max(N, 1), dtype=torch.int32, device=dev) if rows else None
+    src_scale, dst_scale = scales
+    rowptr, nbr = (g.out_rowptr, g.out_dst) if transpose else (g.in_rowptr, g.in_src)
+    nbr_scale, row_scale = (dst_scale, src_scale) if transpose else (src_scale, dst_scale)
+    _lib.call_tag[0] = {"layer": f"D{D}", "bytes": gcn_agg_bytes(N, E, D)}
+    call("mvml_gcn_agg", N, ptr(rowptr), ptr(nbr), ptr(X), ldx, D, ptr(nbr_scale), ptr(row_scale), ptr(bias),
+         int(act), ptr(out), D, None, ptr(rmx), _stream(dev))
+    if rows:
+        fold_rows(out, rmx)
+    return out
+
+
+def _graph_conv_forward(X, weight, bias, g, norm, act):
+    """GraphConv's forward.  Returns (out, (A, Wp), state): A the product's [N, Fp] operand (the
+    zero-padded input, or the aggregated input), Wp the [Fp, out] weight it met, state what the
+    backward needs beside them and `out`."""
+    for t, n in ((X, "feat"), (weight, "weight"), (bias, "bias")):
+        if t is not None:
+            _check_cuda_f32(t, n)
+    Xpad = zero_padded(X, _round4(X.shape[1])) if X.dim() == 2 else None
+    if Xpad is None:
+        X = _c(X)
+    N, Fin = X.shape
+    Fout = weight.shape[1]
+    dev = X.device
+    Fp = _round4(Fin)
+    weight = _c(weight)
+    bias = None if bias is None else _c(bias)
+    scales = gcn_scales(g, norm)
+    proj_first = Fin > Fout or Fin != Fp
+    rows = GEMM_ALGO == "f16x2" and ROW_SCALES
+    amx = zeros(3, dtype=torch.int32, device=dev) if rows else None  # [A operand, W, gradient]
+    if proj_first:
+        # operands of the product padded to 16-B rows / a K of 4 q (zeros add nothing)
+        Xp, Wp = Xpad if Xpad is not None else X, weight
+        if Xpad is None and Fp != Fin:
+            Xp = zeros((N, Fp), device=dev)
+            copy2d(Xp[:, :Fin], X)
+        if Fp != Fin:
+            Wp = zeros((Fp, Fout), device=dev)
+            copy2d(Wp[:Fin], weight)
+        A = Xp
+    else:
+        Wp = weight
+        A = gcn_agg(X, Fin, Fin, g, scales, rows=rows)
+    xr = None
+    if rows:
+        xr = known_rows(X) if proj_first else known_rows(A)
+        if xr is None:
+            xr = absmax_rows(A, N, Fp, Fp)
+        absmax(xr, N, 1, 1, amx, 0)
+        absmax(Wp, Fp, Fout, Fout, amx, 1)
+    last_gemm = not proj_first
+    Y = torch.empty((N, Fout), dtype=torch.float32, device=dev)
+    gemm(A, Wp, N, Fout, Fp, 0, 1, Fp, Fout, Y, Fout, bias=bias if last_gemm else None,
+         act=act if last_gemm else 0, amax=(None, slot(amx, 1)) if rows else None, arows=xr, role="gcn_proj")
+    out = Y if last_gemm else gcn_agg(Y, Fout, Fout, g, scales, bias=bias, act=act, rows=rows)
+    if DEBUG_CAPTURE is not None and act:  # the ReLU sides the product took (parity tests)
+        DEBUG_CAPTURE.setdefault("gcn_out", []).append(out.detach().clone())
+    return out, (A, Wp), (g, scales, proj_first, Fin, amx, bias is not None)
+
+
+def _graph_conv_backward(A, Wp, out, state, g_out, need_gx, gx_acc=None):
+    """(gX, gW, gb) of GraphConv from g_out; out: the saved output of a ReLU layer, else None.
+    gx_acc: an [N, in_feats] gradient the input already has from another branch (GCNLayer's
+    residual), accumulated onto with the data-gradient product's beta = 1 or mvml_add_cols_f32,
+    so that no framework add runs."""
+    g, scales, proj_first, Fin, amx, has_bias = state
+    N, Fp = A.shape
+    Fout = Wp.shape[1]
+    dev = A.device
+    g_out = _c(g_out)
+    if out is not None:
+        g_pre = torch.empty_like(g_out)
+        call("mvml_relu_bwd", g_out.numel(), ptr(out), ptr(g_out), ptr(g_pre), 1.0, _stream(dev))
+    else:
+        g_pre = g_out
+    gb = None
+    if has_bias:
+        gb = torch.empty(Fout, dtype=torch.float32, device=dev)
+        colsum(g_pre, N, Fout, Fout, gb)
+    rows = amx is not None
+    # the gradient at the product's output: through the sum's adjoint when the sum came last
+    gY = gcn_agg(g_pre, Fout, Fout, g, scales, transpose=True, rows=rows) if proj_first else g_pre
+    gyr = None
+    if rows:
+        gyr = known_rows(gY)
+        if gyr is None:
+            gyr = absmax_rows(gY, N, Fout, Fout)
+        absmax(gyr, N, 1, 1, amx, 2)
+    gW = torch.empty((Fp, Fout), dtype=torch.float32, device=dev)
+    gemm(A, gY, Fp, Fout, N, 1, 1, Fp, Fout, gW, Fout,
+         amax=(slot(amx, 0), slot(amx, 2)) if rows else None, role="gcn_dw")
+    gX = None
+    if need_gx:
+        into = proj_first and gx_acc is not None  # the product writes dX itself: accumulate there
+        gA = gx_acc if into else torch.empty((N, Fin), dtype=torch.float32, device=dev)
+        gemm(gY, Wp, N, Fin, Fout, 0, 0, Fout, Fout, gA, Fin, beta=1.0 if into else 0.0,
+             amax=(None, slot(amx, 1)) if rows else None, arows=gyr, role="gcn_dx")
+        gX = gA
+        if not proj_first:
+            gX = gcn_agg(gA, Fin, Fin, g, scales, transpose=True)
+            if gx_acc is not None:  # (in_feats % 4 == 0 in this order)
+                call("mvml_add_cols_f32", N, Fin, ptr(gx_acc), Fin, ptr(gX), Fin, _stream(dev))
+    return gX, gW[:Fin], gb
+
+
+class GraphConvFunction(torch.autograd.Function):
+    """dgl 0.9.1 GraphConv.forward (restated; parity with dgl is unpinned):
+    act(D_dst (A (D_src X)) W + b), the sum over in-edges on mvml_gcn_agg and the product on the
+    fp32-accurate GEMM with the [in, out] weight read K-major (no transposed copy).  The sum runs
+    on the narrower side as in DGL (the product first when in_feats > out_feats), and on the
+    projected side whenever in_feats is no multiple of 4 (the aggregation's float4 rows; the two
+    orders are the same function).  Bias and ReLU ride in whichever launch comes last.  Backward:
+    mvml_relu_bwd on the saved output, the aggregation over the out-CSR with the scales swapped
+    (a gather: no atomics), the split-K weight-gradient product and mvml_colsum_f32."""
+
+    @staticmethod
+    def forward(ctx, X, weight, bias, g, norm, act):
+        out, (A, Wp), ctx.state = _graph_conv_forward(X, weight, bias, g, norm, act)
+        ctx.save_for_backward(A, Wp, out if act else None)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        A, Wp, out = ctx.saved_tensors
+        gX, gW, gb = _graph_conv_backward(A, Wp, out, ctx.state, g_out, ctx.needs_input_grad[0])
+        return gX, gW, gb, None, None, None
+
+
+class GCNConvResidualFunction(torch.autograd.Function):
+    """dgllife GCNLayer up to its Dropout: graph_conv(g, x) + act(res_connection(x)), act ReLU or
+    none on both branches, as ONE autograd node.  The input feeds both branches; as two Functions
+    the autograd engine would add their two input gradients with a framework kernel, so the
+    backward here forms the residual Linear's dX first and the conv's data gradient accumulates
+    onto it (_graph_conv_backward's gx_acc).  The sum goes to a new tensor (mvml_copy_cols, then
+    mvml_add_cols_f32): both branch outputs are kept for their ReLU backwards."""
+
+    @staticmethod
+    def forward(ctx, X, weight, bias, res_w, res_b, g, norm, act):
+        conv, (A, Wp), ctx.state = _graph_conv_forward(X, weight, bias, g, norm, act)
+        _check_cuda_f32(res_w, "res_connection.weight")
+        x = _c(X)
+        M, K = x.shape
+        Fout = res_w.shape[0]
+        res_w = _c(res_w)
+        y = torch.empty((M, Fout), dtype=torch.float32, device=x.device)
+        lm = ctx.lm = linear_maxima(x, res_w)
+        linear_fwd(x, res_w, y, M, Fout, K, lm, bias=None if res_b is None else _c(res_b), act=int(act))
+        if DEBUG_CAPTURE is not None and act:
+            DEBUG_CAPTURE.setdefault("relu_out", []).append(y.detach().clone())
+        s = copy2d(torch.empty_like(conv), conv)
+        if M:
+            call("mvml_add_cols_f32", M, Fout, ptr(y), Fout, ptr(s), Fout, _stream(x.device))
+        ctx.save_for_backward(A, Wp, conv if act else None, x, res_w, y if act else None)
+        ctx.has_res_b = res_b is not None
+        return s
+
+    @staticmethod
+    def backward(ctx, g_s):
+        A, Wp, conv, x, res_w, y = ctx.saved_tensors
+        g_s = _c(g_s)
+        M, K = x.shape
+        Fout = res_w.shape[0]
+        dev = x.device
+        if y is not None:
+            g_pre = torch.empty_like(g_s)
+            call("mvml_relu_bwd", g_s.numel(), ptr(y), ptr(g_s), ptr(g_pre), 1.0, _stream(dev))
+        else:
+            g_pre = g_s
+        lm = ctx.lm
+        if lm is not None:
+            absmax(g_pre, M, Fout, Fout, lm[0], 2)
+        g_rw = torch.empty_like(res_w)
+        gemm(g_pre, x, Fout, K, M, 1, 1, Fout, K, g_rw, K,
+             amax=None if lm is None else (slot(lm[0], 2), slot(*lm[1])))
+        g_rb = None
+        if ctx.has_res_b:
+            g_rb = torch.empty((Fout,), dtype=torch.float32, device=dev)
+            colsum(g_pre, M, Fout, Fout, g_rb)
+        need = ctx.needs_input_grad[0]
+        gx = None
+        if need:
+            gx = torch.empty_like(x)
+            linear_dx(g_pre, res_w, gx, M, Fout, K, lm)
+        gX, gW, gb = _graph_conv_backward(A, Wp, conv, ctx.state, g_s, need, gx_acc=gx)
+        return gX, gW, gb, g_rw, g_rb, None, None, None

@@ -7,7 +7,9 @@ Drop-in replacements, on the MI355X HIP path, for
   * torch_geometric 2.2.0 ``GraphNorm`` (model.py:10, 85, 93),
   * ``GNNModule`` itself (model.py:77-95),
   * dgllife 0.3.0 ``MLPPredictor`` / ``GATPredictor`` / ``GATv2Predictor`` (the single-view graph
-    classifiers; not in model.py).
+    classifiers; not in model.py),
+  * dgl 0.9.1 ``GraphConv`` and dgllife 0.3.0 ``GCNLayer`` / ``GCN`` / ``GCNPredictor`` (the GCN
+    baseline; not in model.py).
 Parameter names/shapes/registration order follow the reference so a ``net_i.pkl``
 ``model_state_dict`` (keys under ``gnn.``) loads unchanged.
 """
@@ -578,6 +580,178 @@ class GATv2Predictor(nn.Module):
         self.gnn_out_feats = _gnn_out_feats(self.gnn)
         self.readout = WeightedSumAndMax(self.gnn_out_feats)
         self.predict = MLPPredictor(2 * self.gnn_out_feats, predictor_out_feats, n_tasks, predictor_dropout)
+
+    def forward(self, bg, feats):
+        node_feats = self.gnn(bg, feats)
+        return self.predict(self.readout(bg, node_feats))
+
+
+def _is_relu(activation):
+    return activation is F.relu or activation is torch.relu or isinstance(activation, nn.ReLU)
+
+
+class GraphConv(nn.Module):
+    """dgl.nn.pytorch.GraphConv (0.9.1; restated, parity with dgl is unpinned): weight
+    [in_feats, out_feats] (xavier-uniform) and bias [out_feats] (zeros), registered in that order;
+    forward(graph, feat) = activation(D_dst (A (D_src feat)) weight + bias) with `norm` one of
+    "none", "both", "right", "left" (degrees clamped to 1), on Fn.GraphConvFunction: the neighbour
+    sum in csrc/gcn_agg.hip, the product on the fp32-accurate GEMM, bias and ReLU in the last
+    launch.  activation: None or ReLU (F.relu, torch.relu, nn.ReLU()), the fused epilogue; any
+    other callable is refused.  weight=False, a weight passed to forward and edge weights are
+    refused."""
+
+    def __init__(self, in_feats, out_feats, norm="both", weight=True, bias=True, activation=None,
+                 allow_zero_in_degree=False):
+        super().__init__()
+        if norm not in Fn.GCN_NORMS:
+            raise ValueError(f'Invalid norm value. Must be either "none", "both", "right" or "left". But got "{norm}".')
+        if not weight:
+            raise NotImplementedError("GraphConv: weight=False (a weight passed to forward) is not on the HIP path")
+        if activation is not None and not _is_relu(activation):
+            raise ValueError("GraphConv: activation must be None or ReLU (F.relu, torch.relu, nn.ReLU()) on the HIP path")
+        # the aggregation kernel's range (csrc/gcn_agg.hip mvml_gcn_agg): refuse here, not in forward
+        if out_feats <= 0 or out_feats % 4 or out_feats > 2048:
+            raise ValueError(f"GraphConv: out_feats must be a positive multiple of 4 <= 2048 (got {out_feats})")
+        # (the sum runs on the input side only when in_feats <= out_feats: inside the range too)
+        if in_feats <= 0:
+            raise ValueError(f"GraphConv: in_feats must be positive (got {in_feats})")
+        self._in_feats = in_feats
+        self._out_feats = out_feats
+        self._norm = norm
+        self._allow_zero_in_degree = allow_zero_in_degree
+        self.weight = nn.Parameter(torch.empty(in_feats, out_feats))
+        if bias:
+            self.bias = nn.Parameter(torch.empty(out_feats))
+        else:
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+        self._activation = activation
+
+    def reset_parameters(self):
+        nn.init.xavier_uniform_(self.weight)
+        if self.bias is not None:
+            nn.init.zeros_(self.bias)
+
+    _check_graph = GATConv._check_graph
+
+    def forward(self, graph, feat, weight=None, edge_weight=None):
+        if weight is not None:
+            raise NotImplementedError("GraphConv: an external weight is not on the HIP path")
+        if edge_weight is not None:
+            raise NotImplementedError("GraphConv: edge weights are not on the HIP path")
+        self._check_graph(graph)
+        return Fn.GraphConvFunction.apply(feat, self.weight, self.bias, graph, self._norm,
+                                          int(self._activation is not None))
+
+
+class GCNLayer(nn.Module):
+    """dgllife.model.gnn.gcn.GCNLayer (0.3.0; restated, parity with dgllife is unpinned):
+    new = graph_conv(g, x) (activation inside); residual: new = new + activation(res_connection(x));
+    then dropout and bn_layer.  Members in dgllife's order: graph_conv, dropout, res_connection =
+    Linear(in_feats, out_feats), bn_layer = BatchNorm1d(out_feats); the torch modules are parameter
+    containers, the arithmetic runs on the HIP kernels (Fn.GCNConvResidualFunction: both branches and
+    their sum as one autograd node, so no framework add joins their input gradients; Fn.GraphConvFunction
+    without a residual; Fn.dropout, Fn.batch_norm1d).  activation: F.relu (or torch.relu / nn.ReLU())
+    or None, anything else is refused here.  Deviation: activation=None with a residual is the
+    identity on the residual branch (dgllife would call None)."""
+
+    def __init__(self, in_feats, out_feats, gnn_norm="none", activation=None, residual=True, batchnorm=True,
+                 dropout=0., allow_zero_in_degree=False):
+        super().__init__()
+        if activation is not None and not _is_relu(activation):
+            raise ValueError("GCNLayer: activation must be F.relu or None on the HIP path")
+        if not 0.0 <= dropout < 1.0:
+            raise ValueError("GCNLayer: dropout probability must be in [0, 1) on the HIP path")
+        self.activation = activation
+        self.graph_conv = GraphConv(in_feats=in_feats, out_feats=out_feats, norm=gnn_norm, activation=activation,
+                                    allow_zero_in_degree=allow_zero_in_degree)
+        self.dropout = nn.Dropout(dropout)
+        self.residual = residual
+        if residual:
+            self.res_connection = nn.Linear(in_feats, out_feats)
+        self.bn = batchnorm
+        if batchnorm:
+            self.bn_layer = nn.BatchNorm1d(out_feats)
+
+    def reset_parameters(self):
+        self.graph_conv.reset_parameters()
+        if self.residual:
+            self.res_connection.reset_parameters()
+        if self.bn:
+            self.bn_layer.reset_parameters()
+
+    def forward(self, g, feats):
+        conv = self.graph_conv
+        if self.residual:
+            # both branches read feats: one autograd node, so that their two input gradients are
+            # summed by the HIP kernels and not by the autograd engine
+            conv._check_graph(g)
+            lin = self.res_connection
+            new_feats = Fn.GCNConvResidualFunction.apply(feats, conv.weight, conv.bias, lin.weight, lin.bias, g,
+                                                         conv._norm, int(self.activation is not None))
+        else:
+            new_feats = conv(g, feats)
+        new_feats = Fn.dropout(new_feats, Fn.dropout_p(self.dropout))
+        if self.bn:
+            new_feats = Fn.batch_norm1d(new_feats, self.bn_layer)
+        return new_feats
+
+
+class GCN(nn.Module):
+    """dgllife.model.gnn.gcn.GCN (0.3.0) with its defaults: hidden_feats [64, 64], per layer
+    gnn_norm "none", activation F.relu, residual, batchnorm, dropout 0."""
+
+    def __init__(self, in_feats, hidden_feats=None, gnn_norm=None, activation=None, residual=None,
+                 batchnorm=None, dropout=None, allow_zero_in_degree=None):
+        super().__init__()
+        hidden_feats = list(hidden_feats) if hidden_feats is not None else [64, 64]
+        n = len(hidden_feats)
+        gnn_norm = gnn_norm if gnn_norm is not None else ["none"] * n
+        activation = activation if activation is not None else [F.relu] * n
+        residual = residual if residual is not None else [True] * n
+        batchnorm = batchnorm if batchnorm is not None else [True] * n
+        dropout = dropout if dropout is not None else [0.] * n
+        lengths = [len(hidden_feats), len(gnn_norm), len(activation), len(residual), len(batchnorm), len(dropout)]
+        assert len(set(lengths)) == 1, (
+            "Expect the lengths of hidden_feats, gnn_norm, activation, residual, batchnorm and dropout to "
+            f"be the same, got {lengths}")
+        self.hidden_feats = hidden_feats
+        self.gnn_layers = nn.ModuleList()
+        for i in range(n):
+            self.gnn_layers.append(GCNLayer(in_feats, hidden_feats[i], gnn_norm[i], activation[i], residual[i],
+                                            batchnorm[i], dropout[i], allow_zero_in_degree=allow_zero_in_degree))
+            in_feats = hidden_feats[i]
+
+    def reset_parameters(self):
+        for gnn in self.gnn_layers:
+            gnn.reset_parameters()
+
+    def forward(self, g, feats):
+        for gnn in self.gnn_layers:
+            feats = gnn(g, feats)
+        return feats
+
+
+class GCNPredictor(nn.Module):
+    """dgllife.model.model_zoo.gcn_predictor.GCNPredictor (0.3.0; restated, parity with dgllife is
+    unpinned): gnn = GCN(...) -> readout = WeightedSumAndMax(hidden_feats[-1]) -> predict =
+    MLPPredictor(2 * hidden_feats[-1], predictor_hidden_feats, n_tasks, predictor_dropout).  The
+    deprecated classifier_hidden_feats / classifier_dropout override the predictor_* pair when only
+    they are non-default (GATPredictor's rule).  forward(bg, feats) returns (B, n_tasks) logits."""
+
+    def __init__(self, in_feats, hidden_feats=None, gnn_norm=None, activation=None, residual=None,
+                 batchnorm=None, dropout=None, classifier_hidden_feats=128, classifier_dropout=0., n_tasks=1,
+                 predictor_hidden_feats=128, predictor_dropout=0.):
+        super().__init__()
+        if predictor_hidden_feats == 128 and classifier_hidden_feats != 128:
+            predictor_hidden_feats = classifier_hidden_feats
+        if predictor_dropout == 0. and classifier_dropout != 0.:
+            predictor_dropout = classifier_dropout
+        self.gnn = GCN(in_feats=in_feats, hidden_feats=hidden_feats, gnn_norm=gnn_norm, activation=activation,
+                       residual=residual, batchnorm=batchnorm, dropout=dropout)
+        gnn_out_feats = self.gnn.hidden_feats[-1]
+        self.readout = WeightedSumAndMax(gnn_out_feats)
+        self.predict = MLPPredictor(2 * gnn_out_feats, predictor_hidden_feats, n_tasks, predictor_dropout)
 
     def forward(self, bg, feats):
         node_feats = self.gnn(bg, feats)
