@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .functional import fold_padded
 
 
 class MolGraph:
@@ -76,7 +77,7 @@ def pad_columns(v, device, mult=4):
     buf = torch.zeros((n, (f + mult - 1) // mult * mult), dtype=torch.float32, device=device)
     out = buf[:, :f]
     out.copy_(v, non_blocking=True)
-    out._mvml_padded = (buf, out._version, (out.data_ptr(), tuple(out.shape), out.stride()))
+    fold_padded(out, buf)
     return out
 
 

@@ -4,6 +4,7 @@ Each Function owns one stage of GNNModule (model.py:89-95) and calls only the C 
 no PyTorch math on the hot path besides allocation (and nn.Dropout, which the reference
 applies with torch's own RNG, model.py:87).
 """
+import collections
 import contextlib
 import ctypes
 import os
@@ -93,12 +94,9 @@ def _round4(x):
 
 # Row pitch of the N-row projection / gradient matrices: a multiple of 64 floats, so every row
 # starts on a 256-B boundary and the aggregation kernels' 64-column chunks (256-B row segments)
-# never straddle an extra cache line (MVML_ROW_PITCH64=0: multiples of 4 floats only)
-_PITCH64 = os.environ.get("MVML_ROW_PITCH64", "1") != "0"
-
-
+# never straddle an extra cache line
 def _row_pitch(cols):
-    return (cols + 63) // 64 * 64 if _PITCH64 else _round4(cols)
+    return (cols + 63) // 64 * 64
 
 
 def agg_fwd_bytes(N, E, H, F, out_cols, res_cols):
@@ -128,16 +126,29 @@ _GEMM_ENTRY = {"f32": ("mvml_gemm_f32", 0), "x3": ("mvml_gemm_f32x3", 1),
                "f16x2": ("mvml_gemm_f16x2", 3)}
 
 
+# A record (_mvml_amax, _mvml_rows, _mvml_padded, _mvml_elu) is set by the producer on the exact
+# tensor it wrote and trusted only while that tensor is unmodified by torch (same _version) and
+# still is the storage the producer wrote (same data pointer, shape and strides) — a view, a copy
+# or an in-place update through autograd-visible ops gets a fresh pass instead.
+def _stamp(t):
+    return t._version, t.data_ptr(), tuple(t.shape), t.stride()
+
+
+def _remember(t, attr, *what):
+    setattr(t, attr, (*what, _stamp(t)))
+
+
+def _recall(t, attr):
+    """What _remember put on t under attr (the stamp last), or None if nothing or t changed."""
+    rec = getattr(t, attr, None)
+    return rec if rec is not None and rec[-1] == _stamp(t) else None
+
+
 def known_amax(X):
     """(int32 tensor, slot) holding max |X| bits if the kernel that produced X folded it into
-    its stores, else None.  X._mvml_amax is set by the producer on the exact tensor it wrote;
-    the record is trusted only while that tensor is unmodified by torch (same _version) and
-    still is the storage the producer wrote (same data pointer, shape and strides) — a view, a
-    copy or an in-place update through autograd-visible ops gets a fresh |max| pass instead."""
-    rec = getattr(X, "_mvml_amax", None)
-    if rec is None or rec[2] != X._version or rec[3] != (X.data_ptr(), tuple(X.shape), X.stride()):
-        return None
-    return rec[0], rec[1]
+    its stores (fold_amax) and X is unchanged since, else None."""
+    rec = _recall(X, "_mvml_amax")
+    return None if rec is None else rec[:2]
 
 
 # Per-row A maxima (mvml_gemm_f16x2_rows): the split-fp16 products whose A rows are atoms or
@@ -150,24 +161,25 @@ ROW_SCALES = os.environ.get("MVML_ROW_SCALES", "1") != "0"
 def known_rows(X):
     """Per-row |max| bits of X (int32 [rows]) if its producer recorded them (same rule as
     known_amax), else None."""
-    rec = getattr(X, "_mvml_rows", None)
-    if rec is None or rec[1] != X._version or rec[2] != (X.data_ptr(), tuple(X.shape), X.stride()):
-        return None
-    return rec[0]
+    rec = _recall(X, "_mvml_rows")
+    return None if rec is None else rec[0]
 
 
 def zero_padded(X, Fp):
     """The zero-padded [N, Fp] buffer X is the [:, :F] view of (batching.pad_columns: the
     batch's resident atom features), if unchanged since recorded, else None."""
-    rec = getattr(X, "_mvml_padded", None)
-    if rec is None or rec[1] != X._version or rec[2] != (X.data_ptr(), tuple(X.shape), X.stride()):
-        return None
-    return rec[0] if rec[0].shape[1] == Fp else None
+    rec = _recall(X, "_mvml_padded")
+    return rec[0] if rec is not None and rec[0].shape[1] == Fp else None
+
+
+def fold_padded(out, buf):
+    """Record that out is the [:, :F] view of the zero-padded buffer buf."""
+    _remember(out, "_mvml_padded", buf)
 
 
 def fold_rows(out, rows):
     """Record that rows[r] holds max |out[r, :]| bits (written with out by its producer)."""
-    out._mvml_rows = (rows, out._version, (out.data_ptr(), tuple(out.shape), out.stride()))
+    _remember(out, "_mvml_rows", rows)
 
 
 def absmax_rows(P, rows, cols, ld, out=None, offset=0, accumulate=False):
@@ -185,9 +197,20 @@ def row_maxima(X, rows, cols, ld):
     return r if r is not None else absmax_rows(X, rows, cols, ld)
 
 
+def _row_scales(X, A, N, K, amx, slot_idx=0):
+    """Per-row |max| bits (int32 [N]) of the split-fp16 operand A [N, K]: the record X's producer
+    left (A is X, or X with zero pad columns: the same row maxima), else one pass over A; their
+    max, max |A|, goes to amx[slot_idx] (N floats read, not N x K)."""
+    xr = known_rows(X)
+    if xr is None:
+        xr = absmax_rows(A, N, K, K)
+    absmax(xr, N, 1, 1, amx, slot_idx)
+    return xr
+
+
 def fold_amax(out, amx, slot_idx):
     """Record that out's |max| bits are in amx[slot_idx] (folded by the kernel that wrote out)."""
-    out._mvml_amax = (amx, slot_idx, out._version, (out.data_ptr(), tuple(out.shape), out.stride()))
+    _remember(out, "_mvml_amax", amx, slot_idx)
 
 
 def absmax(P, rows, cols, ld, out, slot=0, offset=0, accumulate=False):
@@ -201,10 +224,6 @@ def slot(t, i):
     """Device pointer to element i of an int32 maxima tensor (None passes through)."""
     return None if t is None else ctypes.c_void_p(t.data_ptr() + 4 * i)
 
-
-# split-fp16 projection: el / er as 2H extra GEMM columns against Wcat's A_l / A_r rows (True)
-# or mvml_gat_proj_fwd's logit-partial epilogue over the Z tile (False)
-PROJ_ELR_GEMM = os.environ.get("MVML_PROJ_ELR_GEMM", "1") != "0"
 
 # Weights split ONCE per step into the interleaved-by-4 fp16 image (mvml_split_f16x2_il4) that
 # the 256x256 split-fp16 tiles load in place of fp32 B: one 16-B load per piece as before and no
@@ -220,6 +239,14 @@ def split_il4(W, rows, cols, ld, amax_ptr):
     img = torch.empty((rows, ld), dtype=torch.float32, device=W.device)
     call("mvml_split_f16x2_il4", rows, cols, ptr(W), ld, amax_ptr, ptr(img), _stream(W.device))
     return img
+
+
+def _split_weight(W, amx):
+    """max |W| of the dense weight W into amx[1], and W's interleaved image made with it
+    (split_il4; None where that does not apply)."""
+    rows, cols = W.shape
+    absmax(W, rows, cols, cols, amx, 1)
+    return split_il4(W, rows, cols, cols, slot(amx, 1))
 
 
 def split_il8(P, rows, K, ld, kmajor=0, amax_ptr=None, rows_max=None, out=None):
@@ -363,10 +390,57 @@ ELU_LINK = [False]
 
 
 def _elu_link_of(X):
-    rec = getattr(X, "_mvml_elu", None)
-    if rec is None or rec[1] != X._version or rec[2] != (X.data_ptr(), tuple(X.shape), X.stride()):
-        return None
-    return rec[0]
+    rec = _recall(X, "_mvml_elu")
+    return None if rec is None else rec[0]
+
+
+# ---- what GATLayerFunction and GATv2LayerFunction do alike ---------------------------------------
+def _check_res_kind(who, res_kind, res_w):
+    if res_kind not in (RES_PROJ, RES_IDENTITY, RES_NONE):
+        raise ValueError(f"{who}: unknown residual kind {res_kind!r}")
+    if (res_w is None) != (res_kind != RES_PROJ):
+        raise ValueError(f"{who}: res_fc.weight goes with the projected residual only")
+
+
+def _padded_input(X):
+    """(X, Xp): X contiguous and Xp its GEMM operand, the feature dimension padded to a multiple
+    of 4 (e.g. 74 atom features -> 76) so every operand row is 16-B aligned and the LDS-DMA path
+    applies; pad columns are zero.  The batch's atom features may already sit in such a buffer
+    (zero_padded): X then stays the view it is."""
+    Xp = zero_padded(X, _round4(X.shape[1])) if X.dim() == 2 else None
+    if Xp is None:
+        X = _c(X)
+        N, Fin = X.shape
+        Xp = X if Fin % 4 == 0 else torch.nn.functional.pad(X, (0, _round4(Fin) - Fin))
+    return X, Xp
+
+
+def _identity_residual(Xp, H, F, mean, st):
+    """(R, ldr) of an identity residual: the input itself, or its head mean in a head-mean layer."""
+    N, Fp = Xp.shape
+    if not mean:
+        return Xp, Fp
+    R = torch.empty((N, F), dtype=torch.float32, device=Xp.device)
+    call("mvml_head_mean_f32", N, H, F, ptr(Xp), Fp, ptr(R), F, st)
+    return R, F
+
+
+def _head_mean_bias_grad(g_bias, N, H, F, G=None, ldg=0, offset=0):
+    """Every head's bias of a head-mean layer sees g_out / H: one column sum (G's F columns at
+    `offset`; G None: g_bias[:F] holds it already), replicated over the heads."""
+    if G is not None:
+        colsum(G, N, F, ldg, g_bias, offset=offset, alpha=1.0 / H)
+    if H > 1:
+        copy2d(g_bias.view(H, F)[1:], g_bias[:F].view(1, F).expand(H - 1, F))
+
+
+def _new_gx(g_out, N, Fin, H, F, identity, st):
+    """[N, Fin] for the data-gradient product; a head-mean layer's identity residual puts its
+    share there first (g_out / H spread over the heads) and the product accumulates onto it."""
+    gX = torch.empty((N, Fin), dtype=torch.float32, device=g_out.device)
+    if identity:
+        call("mvml_head_mean_bwd_f32", N, H, F, ptr(g_out), F, ptr(gX), Fin, st)
+    return gX
 
 
 class GATLayerFunction(torch.autograd.Function):
@@ -384,21 +458,18 @@ class GATLayerFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, X, fc_w, res_w, attn_l, attn_r, bias, g, H, F, slope, mode, algo=None,
                 res_kind=RES_PROJ):
-        if res_kind not in (RES_PROJ, RES_IDENTITY, RES_NONE):
-            raise ValueError(f"GATLayerFunction: unknown residual kind {res_kind!r}")
+        _check_res_kind("GATLayerFunction", res_kind, res_w)
         sep = res_kind != RES_PROJ  # no residual rows in Wcat / Y / gY
-        if (res_w is None) != sep:
-            raise ValueError("GATLayerFunction: res_fc.weight goes with the projected residual only")
         if sep and (algo or GEMM_ALGO) == "bf16":
             raise NotImplementedError("GATLayerFunction: the bf16 projection needs a projected residual")
         for t, n in ((X, "feat"), (fc_w, "fc.weight"), (res_w, "res_fc.weight"), (bias, "bias")):
             if t is not None:
                 _check_cuda_f32(t, n)
-        # the batch's atom features may already sit in a zero-padded 16-B-row buffer
-        Xpad = zero_padded(X, _round4(X.shape[1])) if X.dim() == 2 else None
-        if Xpad is None:
-            X = _c(X)
-        N, Fin = X.shape
+        # (A ones pad column that would make the dW GEMM emit the bias gradient as well was
+        # measured 1.02e-5 from float64 on config 3 — the bias sums cancel and the split-fp16
+        # representation error shows — so the bias keeps its exact fp32 column sum.)
+        X, Xp = _padded_input(X)
+        (N, Fin), Fp = X.shape, Xp.shape[1]
         dev = X.device
         HF = H * F
         if res_kind == RES_IDENTITY and Fin != HF:
@@ -406,16 +477,6 @@ class GATLayerFunction(torch.autograd.Function):
         mean_res = int(mode == MODE_MEAN)
         C = HF if sep else _lib.lib().mvml_gat_proj_cols(H, F, mean_res)
         st = _stream(dev)
-        # Pad the feature dimension to a multiple of 4 (e.g. 74 atom features -> 76) so every
-        # GEMM operand row is 16-B aligned and the LDS-DMA path applies; pad columns are zero.
-        # (A ones pad column that would make the dW GEMM emit the bias gradient as well was
-        # measured 1.02e-5 from float64 on config 3 — the bias sums cancel and the split-fp16
-        # representation error shows — so the bias keeps its exact fp32 column sum.)
-        Fp = _round4(Fin)
-        if Xpad is not None:
-            Xp = Xpad
-        else:
-            Xp = X if Fp == Fin else torch.nn.functional.pad(X, (0, Fp - Fin))
         attn_l, attn_r = _c(attn_l), _c(attn_r)
         HFa = attn_l.numel()
         attn_lr = torch.empty(2 * HFa, dtype=torch.float32, device=X.device)
@@ -423,7 +484,7 @@ class GATLayerFunction(torch.autograd.Function):
         copy2d(attn_lr[HFa:], attn_r.reshape(-1))
         ctx.elu_claim = None
         link = _elu_link_of(X) if (ELU_LINK[0] and (algo or GEMM_ALGO) == "f16x2" and ROW_SCALES
-                                   and PROJ_ELR_GEMM and X.requires_grad) else None
+                                   and X.requires_grad) else None
         # [fc.weight ; res_fc.weight (or its head mean) ; A_l ; A_r]: the projection GEMM uses
         # the first C rows, the backward all C + 2H (the el / er paths, see mvml_gat_agg_bwd)
         Wcat = torch.empty((C + 2 * H, Fp), dtype=torch.float32, device=dev)
@@ -442,28 +503,24 @@ class GATLayerFunction(torch.autograd.Function):
         wil = None  # Wcat's interleaved split image (BSPLIT_IL)
         if (algo or GEMM_ALGO) == "f16x2":
             amx = zeros(4, dtype=torch.int32, device=dev)  # [X, Wcat, gY (bwd), out]
-            if ROW_SCALES and PROJ_ELR_GEMM:
+            if ROW_SCALES:
                 # the projection splits every atom row with its own scale; max |X| (the weight
                 # gradient's A-side scale) is the max of the row maxima (N floats, not N x Fp).
                 # Layer 1's rows are those of the resident atom features (the pad columns are
-                # zeros): computed once and recorded on the feature tensor itself
-                xr = known_rows(X)
-                if xr is None:
-                    # Xp's pad columns are zeros: the whole padded row (float4 loads) has the
-                    # same |max| as its Fin features
-                    xr = absmax_rows(Xp, N, Fp, Fp)
-                    if not X.requires_grad:
-                        fold_rows(X, xr)
-                absmax(xr, N, 1, 1, amx, 0)
+                # zeros): computed once and recorded on the feature tensor itself.  (Xp's pad
+                # columns are zeros: the whole padded row, float4 loads, has the same |max| as
+                # its Fin features)
+                xr = _row_scales(X, Xp, N, Fp, amx)
+                if not X.requires_grad:
+                    fold_rows(X, xr)
                 ax = (amx, 0)
             else:
                 ax = known_amax(Xp) if Xp is X else None  # layer 2: folded by layer 1's aggregation
             if ax is None:
                 absmax(Xp, N, Fp, Fp, amx, 0)
                 ax = (amx, 0)
-            absmax(Wcat, C + 2 * H, Fp, Fp, amx, 1)
             # Wcat split once: the projection's tiles and the backward's dL/dX read the image
-            wil = split_il4(Wcat, C + 2 * H, Fp, Fp, slot(amx, 1))
+            wil = _split_weight(Wcat, amx)
         # claim the previous layer's ELU link only where the fused data-gradient product will
         # run (per-row scales and the interleaved weight image: see backward).  An identity-
         # residual layer never claims: its residual's share of dL/dX is added to the product
@@ -473,8 +530,7 @@ class GATLayerFunction(torch.autograd.Function):
                 and wil is not None and res_kind != RES_IDENTITY):
             link.claimed = True
             ctx.elu_claim = link
-        bf16_elr = (algo or GEMM_ALGO) == "bf16" and PROJ_ELR_GEMM
-        if (amx is not None or bf16_elr) and PROJ_ELR_GEMM:
+        if amx is not None or (algo or GEMM_ALGO) == "bf16":
             # el / er as 2H more GEMM columns: X [A_l ; A_r]^T with A_l[h] = sum_f attn_l[h, f]
             # fc.weight[h F + f] (Wcat's last 2H rows) — the same values re-associated, no
             # logit-partial epilogue and no finalize pass; then gathered into elr [N, 2H].  The
@@ -502,8 +558,7 @@ class GATLayerFunction(torch.autograd.Function):
             _lib.call_tag[0] = {"flops": 2 * N * C * Fp}
             call("mvml_gat_proj_fwd", N, ptr(Xp), Fp, Fp, ptr(Wcat), Fp, ptr(attn_lr), H, F,
                  _MVML_RES_NONE if sep else mean_res,
-                 _GEMM_ENTRY[algo or GEMM_ALGO][1], ptr(Y), ldy, ptr(elr),
-                 None if ax is None else slot(*ax), slot(amx, 1), None, 0, wp, wn, st)
+                 _GEMM_ENTRY[algo or GEMM_ALGO][1], ptr(Y), ldy, ptr(elr), None, None, None, 0, wp, wn, st)
         out_cols = F if mode == MODE_MEAN else HF
         out = torch.empty((N, out_cols), dtype=torch.float32, device=dev)
         E = g.num_edges()
@@ -513,12 +568,7 @@ class GATLayerFunction(torch.autograd.Function):
         # the residual rows: Y's columns past H F (projected), the input itself or its head mean
         # (identity), or none
         rw = out_cols
-        R, ldr = None, 0
-        if res_kind == RES_IDENTITY and mode == MODE_MEAN:
-            R, ldr = torch.empty((N, F), dtype=torch.float32, device=dev), F
-            call("mvml_head_mean_f32", N, H, F, ptr(Xp), Fp, ptr(R), ldr, st)
-        elif res_kind == RES_IDENTITY:
-            R, ldr = Xp, Fp
+        R, ldr = _identity_residual(Xp, H, F, mean_res, st) if res_kind == RES_IDENTITY else (None, 0)
         _lib.call_tag[0] = {"layer": f"H{H}xF{F}",
                             "bytes": agg_fwd_bytes(N, E, H, F, out_cols, 0 if res_kind == RES_NONE else rw)}
         with _fwd_path(g, mode):
@@ -540,10 +590,9 @@ class GATLayerFunction(torch.autograd.Function):
         # in its epilogue (EluLink), so this layer's backward receives g_rst and reads no `out`
         ctx.link = None
         if (mode == MODE_FLATTEN_ELU and ELU_LINK[0] and amx is not None and ROW_SCALES
-                and PROJ_ELR_GEMM
                 and (ELU_LINK_POLICY == "on" or (ELU_LINK_POLICY == "auto" and _large_batch(g)))):
             ctx.link = EluLink(dev)
-            out._mvml_elu = (ctx.link, out._version, (out.data_ptr(), tuple(out.shape), out.stride()))
+            _remember(out, "_mvml_elu", ctx.link)
         if DEBUG_CAPTURE is not None:
             DEBUG_CAPTURE.setdefault("elr_fwd", []).append(elr.detach().clone())
         ctx.save_for_backward(Xp, Wcat, Y, attn, elr, out, attn_l, attn_r, attn_lr)
@@ -633,7 +682,7 @@ class GATLayerFunction(torch.autograd.Function):
         g_bias = torch.empty((HF,), dtype=torch.float32, device=dev) if has_bias else None
         bias_done = False
         # (the fused column sums read gY's residual block: the projected layout with a bias only)
-        if amx is not None and (ctx.algo or GEMM_ALGO) == "f16x2" and COLSUM_FUSED and has_bias and \
+        if amx is not None and (ctx.algo or GEMM_ALGO) == "f16x2" and has_bias and \
                 not sep and L.mvml_gemm_colsum_fused(CE, Fp, N):
             sum_n = F if mean_res else HF
             _lib.call_tag[0] = {"flops": 2 * CE * Fp * N, "shape": (CE, Fp, N, 1, 1),
@@ -665,13 +714,9 @@ class GATLayerFunction(torch.autograd.Function):
         g_ar = g_alr[1].view_as(attn_r)
         if DEBUG_CAPTURE is not None:
             DEBUG_CAPTURE.update(elr=elr, gelr=gelr, attn=attn)
-        if has_bias and mean_res:  # every head's bias sees g_out / H: one column sum, replicated over heads
-            if sep:  # (dR = g_out)
-                colsum(g_out, N, F, F, g_bias, alpha=1.0 / H)
-            elif not bias_done:
-                colsum(gY, N, F, ldg, g_bias, offset=HF, alpha=1.0 / H)
-            if H > 1:
-                copy2d(g_bias.view(H, F)[1:], g_bias[:F].view(1, F).expand(H - 1, F))
+        if has_bias and mean_res:
+            # (identity / absent residual: dR = g_out; the fused product has summed gY's already)
+            _head_mean_bias_grad(g_bias, N, H, F, *((g_out, F) if sep else () if bias_done else (gY, ldg, HF)))
         elif has_bias and sep:  # (before the product below accumulates onto gR where it is gX)
             colsum(gR, N, HF, ldgr, g_bias)
         elif has_bias and not bias_done:
@@ -681,9 +726,7 @@ class GATLayerFunction(torch.autograd.Function):
             # g_out / H spread over the heads) and the product accumulates onto it
             beta = 1.0 if res_kind == RES_IDENTITY else 0.0
             if gX is None:
-                gX = torch.empty((N, Fin), dtype=torch.float32, device=dev)
-                if beta:
-                    call("mvml_head_mean_bwd_f32", N, H, F, ptr(g_out), F, ptr(gX), Fin, st)
+                gX = _new_gx(g_out, N, Fin, H, F, res_kind == RES_IDENTITY, st)
             link = ctx.elu_claim
             if link is not None and amx is not None and ROW_SCALES and ctx.wil is not None:
                 # the previous layer's ELU backward in this product's epilogue: gX leaves as its
@@ -703,11 +746,6 @@ class GATLayerFunction(torch.autograd.Function):
         else:
             gX = None
         return gX, g_fc, g_res, g_al, g_ar, g_bias, None, None, None, None, None, None, None
-
-
-# GAT layer weight + bias gradients from one read of gY where the product's plan allows
-# (mvml_gemm_f16x2_amax_colsum); MVML_COLSUM_FUSED=0: the product, then a column-sum pass
-COLSUM_FUSED = os.environ.get("MVML_COLSUM_FUSED", "1") != "0"
 
 
 # Set2Set's gates GEMM + LSTM cell as one launch (mvml_lstm_gates_cell_fwd: the cell in the
@@ -1023,47 +1061,84 @@ class GraphNormFunction(torch.autograd.Function):
         return gx, gw, gb, gms, None, None
 
 
+# linear_maxima's result: amx the int32 maxima tensor, slots [x, w, grad]; kx the (tensor, slot)
+# holding max |x|; xrows x's per-row maxima (ROW_SCALES, else None); wil the weight's interleaved
+# image (split_il4, may be None)
+LinearMaxima = collections.namedtuple("LinearMaxima", "amx kx xrows wil")
+
+
 def linear_maxima(x, w):
-    """Split-fp16 maxima of a Linear's three products: slots [x, w, grad] (x's from its
-    producer when it folded one), one pass per operand instead of one per product, and (ROW_SCALES)
-    x's per-row maxima for the forward product; None for the other algorithms."""
+    """Split-fp16 maxima of a Linear's three products (LinearMaxima): x's from its producer when
+    it folded one, one pass per operand instead of one per product, and (ROW_SCALES) x's per-row
+    maxima for the forward product; None for the other algorithms."""
     if GEMM_ALGO != "f16x2":
         return None
     amx = zeros(3, dtype=torch.int32, device=x.device)
-    xr = None
-    if ROW_SCALES:
-        xr = row_maxima(x, x.shape[0], x.shape[1], x.shape[1])
-        absmax(xr, x.shape[0], 1, 1, amx, 0)
-        kx = (amx, 0)
-    else:
-        kx = known_amax(x)
+    M, K = x.shape
+    xr = _row_scales(x, x, M, K, amx) if ROW_SCALES else None
+    kx = (amx, 0) if ROW_SCALES else known_amax(x)
     if kx is None:
-        absmax(x, x.shape[0], x.shape[1], x.shape[1], amx, 0)
+        absmax(x, M, K, K, amx, 0)
         kx = (amx, 0)
-    absmax(w, w.shape[0], w.shape[1], w.shape[1], amx, 1)
-    return amx, kx, xr, split_il4(w, w.shape[0], w.shape[1], w.shape[1], slot(amx, 1))
+    return LinearMaxima(amx, kx, xr, _split_weight(w, amx))
 
 
 def linear_fwd(x, weight, y, M, Nout, K, lm, bias=None, act=0):
     """y = act(x W^T + b): the forward product of a Linear (per-row x scales when lm has them)."""
-    if lm is not None and lm[2] is not None:
-        gemm(x, weight, M, Nout, K, 0, 0, K, K, y, Nout, bias=bias, act=act, amax=(None, slot(lm[0], 1)),
-             arows=lm[2], bil4=lm[3])
+    if lm is not None and lm.xrows is not None:
+        gemm(x, weight, M, Nout, K, 0, 0, K, K, y, Nout, bias=bias, act=act, amax=(None, slot(lm.amx, 1)),
+             arows=lm.xrows, bil4=lm.wil)
     else:
         gemm(x, weight, M, Nout, K, 0, 0, K, K, y, Nout, bias=bias, act=act,
-             amax=None if lm is None else (slot(*lm[1]), slot(lm[0], 1)),
-             bil4=None if lm is None else lm[3])
+             amax=None if lm is None else (slot(*lm.kx), slot(lm.amx, 1)),
+             bil4=None if lm is None else lm.wil)
 
 
 def linear_dx(g, weight, gx, M, Nout, K, lm):
     """gx = g W (the data gradient of a Linear; per-row g scales under ROW_SCALES)."""
-    if lm is not None and lm[2] is not None:
-        gemm(g, weight, M, K, Nout, 0, 1, Nout, K, gx, K, amax=(None, slot(lm[0], 1)),
-             arows=absmax_rows(g, M, Nout, Nout), bil4=lm[3])
+    if lm is not None and lm.xrows is not None:
+        gemm(g, weight, M, K, Nout, 0, 1, Nout, K, gx, K, amax=(None, slot(lm.amx, 1)),
+             arows=absmax_rows(g, M, Nout, Nout), bil4=lm.wil)
     else:
         gemm(g, weight, M, K, Nout, 0, 1, Nout, K, gx, K,
-             amax=None if lm is None else (slot(lm[0], 2), slot(lm[0], 1)),
-             bil4=None if lm is None else lm[3])
+             amax=None if lm is None else (slot(lm.amx, 2), slot(lm.amx, 1)),
+             bil4=None if lm is None else lm.wil)
+
+
+def linear_forward(x, weight, bias, act=0):
+    """y = act(x W^T + b) of an nn.Linear (weight [out, in]; bias may be None) as one GEMM with
+    a bias (+ ReLU, act 1) epilogue.  Returns (x, weight, y, lm): the contiguous operands and the
+    maxima record that linear_backward takes."""
+    x = _c(x)
+    M, K = x.shape
+    Nout = weight.shape[0]
+    y = torch.empty((M, Nout), dtype=torch.float32, device=x.device)
+    weight = _c(weight)
+    lm = linear_maxima(x, weight)
+    linear_fwd(x, weight, y, M, Nout, K, lm, bias=None if bias is None else _c(bias), act=act)
+    return x, weight, y, lm
+
+
+def linear_backward(x, weight, g, lm, need_gb=True, need_gx=True):
+    """(gx, gw, gb) of linear_forward from g, the contiguous gradient at its pre-activation:
+    max |g| folded into lm's slot 2, gw = g^T x, gb = g's column sums, gx = g W (linear_dx);
+    gb / gx None where not wanted."""
+    M, K = x.shape
+    Nout = weight.shape[0]
+    if lm is not None:
+        absmax(g, M, Nout, Nout, lm.amx, 2)
+    gw = torch.empty_like(weight)
+    gemm(g, x, Nout, K, M, 1, 1, Nout, K, gw, K,
+         amax=None if lm is None else (slot(lm.amx, 2), slot(*lm.kx)))
+    gb = None
+    if need_gb:
+        gb = torch.empty((Nout,), dtype=torch.float32, device=x.device)
+        colsum(g, M, Nout, Nout, gb)
+    gx = None
+    if need_gx:
+        gx = torch.empty_like(x)
+        linear_dx(g, weight, gx, M, Nout, K, lm)
+    return gx, gw, gb
 
 
 def dropout_seed():
@@ -1196,13 +1271,7 @@ class LinearReLUFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, p=0.0):
         _check_cuda_f32(x, "x")
-        x = _c(x)
-        M, K = x.shape
-        Nout = weight.shape[0]
-        y = torch.empty((M, Nout), dtype=torch.float32, device=x.device)
-        weight = _c(weight)
-        lm = ctx.lm = linear_maxima(x, weight)
-        linear_fwd(x, weight, y, M, Nout, K, lm, bias=_c(bias), act=1)
+        x, weight, y, ctx.lm = linear_forward(x, weight, bias, act=1)
         if DEBUG_CAPTURE is not None:  # the ReLU sides the product took (parity tests)
             DEBUG_CAPTURE.setdefault("relu_out", []).append(y.detach().clone())
         ctx.scale = relu_dropout_(y, p)
@@ -1213,24 +1282,9 @@ class LinearReLUFunction(torch.autograd.Function):
     def backward(ctx, g_y):
         x, weight, y = ctx.saved_tensors
         g_y = _c(g_y)
-        M, K = x.shape
-        Nout = weight.shape[0]
-        dev = x.device
         g_pre = torch.empty_like(y)
-        call("mvml_relu_bwd", y.numel(), ptr(y), ptr(g_y), ptr(g_pre), float(ctx.scale), _stream(dev))
-        lm = ctx.lm
-        if lm is not None:
-            absmax(g_pre, M, Nout, Nout, lm[0], 2)
-        gw = torch.empty_like(weight)
-        gemm(g_pre, x, Nout, K, M, 1, 1, Nout, K, gw, K,
-             amax=None if lm is None else (slot(lm[0], 2), slot(*lm[1])))
-        gb = torch.empty((Nout,), dtype=torch.float32, device=dev)
-        colsum(g_pre, M, Nout, Nout, gb)
-        gx = None
-        if ctx.needs_input_grad[0]:
-            gx = torch.empty_like(x)
-            linear_dx(g_pre, weight, gx, M, Nout, K, lm)
-        return gx, gw, gb, None
+        call("mvml_relu_bwd", y.numel(), ptr(y), ptr(g_y), ptr(g_pre), float(ctx.scale), _stream(x.device))
+        return (*linear_backward(x, weight, g_pre, ctx.lm, need_gx=ctx.needs_input_grad[0]), None)
 
 
 def gatv2_fwd_bytes(N, E, H, F, out_cols, res_cols):
@@ -1261,18 +1315,13 @@ class GATv2LayerFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, X, w_src, w_dst, w_res, b_src, b_dst, b_res, attn, g, H, F, slope, mode,
                 res_kind=RES_PROJ):
-        if res_kind not in (RES_PROJ, RES_IDENTITY, RES_NONE):
-            raise ValueError(f"GATv2LayerFunction: unknown residual kind {res_kind!r}")
-        if (w_res is None) != (res_kind != RES_PROJ):
-            raise ValueError("GATv2LayerFunction: res_fc.weight goes with the projected residual only")
+        _check_res_kind("GATv2LayerFunction", res_kind, w_res)
         for t, n in ((X, "feat"), (w_src, "fc_src.weight"), (w_dst, "fc_dst.weight"), (w_res, "res_fc.weight"),
                      (b_src, "fc_src.bias"), (b_dst, "fc_dst.bias"), (b_res, "res_fc.bias"), (attn, "attn")):
             if t is not None:
                 _check_cuda_f32(t, n)
-        Xpad = zero_padded(X, _round4(X.shape[1])) if X.dim() == 2 else None
-        if Xpad is None:
-            X = _c(X)
-        N, Fin = X.shape
+        X, Xp = _padded_input(X)
+        (N, Fin), Fp = X.shape, Xp.shape[1]
         dev = X.device
         st = _stream(dev)
         HF = H * F
@@ -1284,8 +1333,6 @@ class GATv2LayerFunction(torch.autograd.Function):
         c_r = 0 if shared else HF               # ZR's column in Y / gZR's in gY
         c_res = HF if shared else 2 * HF        # the projected residual's
         C = c_res + (RW if res_kind == RES_PROJ else 0)
-        Fp = _round4(Fin)
-        Xp = Xpad if Xpad is not None else (X if Fp == Fin else torch.nn.functional.pad(X, (0, Fp - Fin)))
         # Wcat = [W_src ; W_dst ; W_res (head mean in a head-mean layer)], pad columns zero
         Wcat = torch.empty((C, Fp), dtype=torch.float32, device=dev)
         if Fp != Fin:
@@ -1317,12 +1364,8 @@ class GATv2LayerFunction(torch.autograd.Function):
         amx = xr = wil = None
         if rows:
             amx = zeros(3, dtype=torch.int32, device=dev)  # [X, Wcat, gY (bwd)]
-            xr = known_rows(X)
-            if xr is None:
-                xr = absmax_rows(Xp, N, Fp, Fp)
-            absmax(xr, N, 1, 1, amx, 0)
-            absmax(Wcat, C, Fp, Fp, amx, 1)
-            wil = split_il4(Wcat, C, Fp, Fp, slot(amx, 1))
+            xr = _row_scales(X, Xp, N, Fp, amx)
+            wil = _split_weight(Wcat, amx)
         ldy = _row_pitch(C)
         Y = torch.empty((N, ldy), dtype=torch.float32, device=dev)
         if rows:
@@ -1334,11 +1377,8 @@ class GATv2LayerFunction(torch.autograd.Function):
         R, ldr = None, 0
         if res_kind == RES_PROJ:
             R, ldr = Y[:, c_res:], ldy
-        elif res_kind == RES_IDENTITY and mean:
-            R, ldr = torch.empty((N, F), dtype=torch.float32, device=dev), F
-            call("mvml_head_mean_f32", N, H, F, ptr(Xp), Fp, ptr(R), ldr, st)
         elif res_kind == RES_IDENTITY:
-            R, ldr = Xp, Fp
+            R, ldr = _identity_residual(Xp, H, F, mean, st)
         out_cols = F if mean else HF
         E = g.num_edges()
         out = torch.empty((N, out_cols), dtype=torch.float32, device=dev)
@@ -1411,10 +1451,8 @@ class GATv2LayerFunction(torch.autograd.Function):
             colsum(gY, N, HF, ldg, g_bd, offset=HF)
         if has_br:
             g_br = torch.empty(HF, **f32)
-            if mean:  # every head's bias sees g_out / H: one column sum, replicated over the heads
-                colsum(g_out, N, F, F, g_br, alpha=1.0 / H)
-                if H > 1:
-                    copy2d(g_br.view(H, F)[1:], g_br[:F].view(1, F).expand(H - 1, F))
+            if mean:
+                _head_mean_bias_grad(g_br, N, H, F, g_out, F)
             else:
                 colsum(gY, N, HF, ldg, g_br, offset=c_res)
         # dL/dWcat = gY^T X and dL/dX = gY Wcat (+ the identity residual's share)
@@ -1437,9 +1475,7 @@ class GATv2LayerFunction(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             beta = 1.0 if res_kind == RES_IDENTITY else 0.0
             if gX is None:
-                gX = torch.empty((N, Fin), **f32)
-                if beta:
-                    call("mvml_head_mean_bwd_f32", N, H, F, ptr(g_out), F, ptr(gX), Fin, st)
+                gX = _new_gx(g_out, N, Fin, H, F, res_kind == RES_IDENTITY, st)
             if amx is not None:
                 gemm(gY, Wcat, N, Fin, C, 0, 1, ldg, Fp, gX, Fin, amax=(None, slot(amx, 1)),
                      arows=absmax_rows(gY, N, C, ldg), bil4=ctx.wil, beta=beta)
@@ -1533,10 +1569,7 @@ def _graph_conv_forward(X, weight, bias, g, norm, act):
         A = gcn_agg(X, Fin, Fin, g, scales, rows=rows)
     xr = None
     if rows:
-        xr = known_rows(X) if proj_first else known_rows(A)
-        if xr is None:
-            xr = absmax_rows(A, N, Fp, Fp)
-        absmax(xr, N, 1, 1, amx, 0)
+        xr = _row_scales(X if proj_first else A, A, N, Fp, amx)
         absmax(Wp, Fp, Fout, Fout, amx, 1)
     last_gemm = not proj_first
     Y = torch.empty((N, Fout), dtype=torch.float32, device=dev)
@@ -1570,12 +1603,7 @@ def _graph_conv_backward(A, Wp, out, state, g_out, need_gx, gx_acc=None):
     rows = amx is not None
     # the gradient at the product's output: through the sum's adjoint when the sum came last
     gY = gcn_agg(g_pre, Fout, Fout, g, scales, transpose=True, rows=rows) if proj_first else g_pre
-    gyr = None
-    if rows:
-        gyr = known_rows(gY)
-        if gyr is None:
-            gyr = absmax_rows(gY, N, Fout, Fout)
-        absmax(gyr, N, 1, 1, amx, 2)
+    gyr = _row_scales(gY, gY, N, Fout, amx, 2) if rows else None
     gW = torch.empty((Fp, Fout), dtype=torch.float32, device=dev)
     gemm(A, gY, Fp, Fout, N, 1, 1, Fp, Fout, gW, Fout,
          amax=(slot(amx, 0), slot(amx, 2)) if rows else None, role="gcn_dw")
@@ -1628,16 +1656,11 @@ class GCNConvResidualFunction(torch.autograd.Function):
     def forward(ctx, X, weight, bias, res_w, res_b, g, norm, act):
         conv, (A, Wp), ctx.state = _graph_conv_forward(X, weight, bias, g, norm, act)
         _check_cuda_f32(res_w, "res_connection.weight")
-        x = _c(X)
-        M, K = x.shape
-        Fout = res_w.shape[0]
-        res_w = _c(res_w)
-        y = torch.empty((M, Fout), dtype=torch.float32, device=x.device)
-        lm = ctx.lm = linear_maxima(x, res_w)
-        linear_fwd(x, res_w, y, M, Fout, K, lm, bias=None if res_b is None else _c(res_b), act=int(act))
+        x, res_w, y, ctx.lm = linear_forward(X, res_w, res_b, act=int(act))
         if DEBUG_CAPTURE is not None and act:
             DEBUG_CAPTURE.setdefault("relu_out", []).append(y.detach().clone())
         s = copy2d(torch.empty_like(conv), conv)
+        M, Fout = y.shape
         if M:
             call("mvml_add_cols_f32", M, Fout, ptr(y), Fout, ptr(s), Fout, _stream(x.device))
         ctx.save_for_backward(A, Wp, conv if act else None, x, res_w, y if act else None)
@@ -1648,28 +1671,12 @@ class GCNConvResidualFunction(torch.autograd.Function):
     def backward(ctx, g_s):
         A, Wp, conv, x, res_w, y = ctx.saved_tensors
         g_s = _c(g_s)
-        M, K = x.shape
-        Fout = res_w.shape[0]
-        dev = x.device
         if y is not None:
             g_pre = torch.empty_like(g_s)
-            call("mvml_relu_bwd", g_s.numel(), ptr(y), ptr(g_s), ptr(g_pre), 1.0, _stream(dev))
+            call("mvml_relu_bwd", g_s.numel(), ptr(y), ptr(g_s), ptr(g_pre), 1.0, _stream(x.device))
         else:
             g_pre = g_s
-        lm = ctx.lm
-        if lm is not None:
-            absmax(g_pre, M, Fout, Fout, lm[0], 2)
-        g_rw = torch.empty_like(res_w)
-        gemm(g_pre, x, Fout, K, M, 1, 1, Fout, K, g_rw, K,
-             amax=None if lm is None else (slot(lm[0], 2), slot(*lm[1])))
-        g_rb = None
-        if ctx.has_res_b:
-            g_rb = torch.empty((Fout,), dtype=torch.float32, device=dev)
-            colsum(g_pre, M, Fout, Fout, g_rb)
         need = ctx.needs_input_grad[0]
-        gx = None
-        if need:
-            gx = torch.empty_like(x)
-            linear_dx(g_pre, res_w, gx, M, Fout, K, lm)
+        gx, g_rw, g_rb = linear_backward(x, res_w, g_pre, ctx.lm, need_gb=ctx.has_res_b, need_gx=need)
         gX, gW, gb = _graph_conv_backward(A, Wp, conv, ctx.state, g_s, need, gx_acc=gx)
         return gX, gW, gb, g_rw, g_rb, None, None, None

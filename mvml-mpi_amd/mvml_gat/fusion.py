@@ -33,35 +33,14 @@ class LinearFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias):
         _check_cuda_f32(x, "x")
-        x = _c(x)
-        M, K = x.shape
-        Nout = weight.shape[0]
-        y = torch.empty((M, Nout), dtype=torch.float32, device=x.device)
-        weight = _c(weight)
-        lm = ctx.lm = _F.linear_maxima(x, weight)
-        _F.linear_fwd(x, weight, y, M, Nout, K, lm, bias=_c(bias))
+        x, weight, y, ctx.lm = _F.linear_forward(x, weight, bias)
         ctx.save_for_backward(x, weight)
         return y
 
     @staticmethod
     def backward(ctx, g_y):
         x, weight = ctx.saved_tensors
-        g_y = _c(g_y)
-        M, K = x.shape
-        Nout = weight.shape[0]
-        lm = ctx.lm
-        if lm is not None:
-            absmax(g_y, M, Nout, Nout, lm[0], 2)
-        gw = torch.empty_like(weight)
-        gemm(g_y, x, Nout, K, M, 1, 1, Nout, K, gw, K,
-             amax=None if lm is None else (slot(lm[0], 2), slot(*lm[1])))
-        gb = torch.empty((Nout,), dtype=torch.float32, device=x.device)
-        colsum(g_y, M, Nout, Nout, gb)
-        gx = None
-        if ctx.needs_input_grad[0]:
-            gx = torch.empty_like(x)
-            _F.linear_dx(g_y, weight, gx, M, Nout, K, lm)
-        return gx, gw, gb
+        return _F.linear_backward(x, weight, _c(g_y), ctx.lm, need_gx=ctx.needs_input_grad[0])
 
 
 # Q.K re-associated (mvml_token_attn_fold_*): s = (x M_h) . x with M_h = W_q,h^T W_k,h, so the

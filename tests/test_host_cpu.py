@@ -175,6 +175,46 @@ def test_fusion_state_dict_matches_reference_layout():
     assert tuple(mod.linear_q.weight.shape) == (4608, 384) and mod.mlp[3].out_features == 11
 
 
+def test_producer_records_hold_only_for_the_unchanged_tensor():
+    """What a kernel recorded on a tensor (per-row maxima, max |X|, the zero-padded buffer) is
+    recalled for that tensor alone, and not after a view, a copy or an in-place update."""
+    from mvml_gat import functional as Fn
+
+    def lost(known, t):
+        assert known(t[:, :]) is None and known(t.clone()) is None
+        t.add_(1)
+        assert known(t) is None
+
+    t = torch.arange(15.0).reshape(5, 3)
+    rows = torch.zeros(5, dtype=torch.int32)
+    assert Fn.known_rows(t) is None
+    Fn.fold_rows(t, rows)
+    assert Fn.known_rows(t) is rows
+    lost(Fn.known_rows, t)
+
+    u = torch.arange(15.0).reshape(5, 3)
+    amx = torch.zeros(4, dtype=torch.int32)
+    assert Fn.known_amax(u) is None
+    Fn.fold_amax(u, amx, 3)
+    kt, ks = Fn.known_amax(u)
+    assert kt is amx and ks == 3
+    assert u._mvml_amax[0] is amx and u._mvml_amax[1] == 3
+    lost(Fn.known_amax, u)
+
+    buf = torch.zeros(5, 76)
+    v = buf[:, :74]
+    assert Fn.zero_padded(v, 76) is None
+    Fn.fold_padded(v, buf)  # as batching.pad_columns records it
+    assert Fn.zero_padded(v, 76) is buf
+    assert Fn.zero_padded(v, 80) is None
+    lost(lambda x: Fn.zero_padded(x, 76), v)
+
+    # off the GPU pad_columns returns the tensor as it is: nothing padded, nothing recorded
+    x = torch.ones(5, 74)
+    out = batching.pad_columns(x, "cpu")
+    assert out.shape == (5, 74) and torch.equal(out, x) and Fn.zero_padded(out, 76) is None
+
+
 def test_node_group_plan_oracle_invariants():
     """Every group is a run of whole molecules, groups tile the atoms, and the kinds route
     exactly the groups that exceed the LDS kernels' caps to the fallback lists."""
