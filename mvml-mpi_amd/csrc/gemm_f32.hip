@@ -1700,9 +1700,10 @@ int gemm_launch(int prec, int a_kmajor, int b_kmajor, int64_t M, int64_t N, int6
                            ldc, workspace, workspace_bytes, stream, 1, BatchStrides{}, amax, bps);
       if (rc) return rc;
       const int64_t boff = b_kmajor ? N1 : N1 * ldb;
+      // (the il4 image has B's float indexing: 2 boff of its 16-bit halves)
       return gemm_launch(prec, a_kmajor, b_kmajor, M, N2, K, A, lda, B + boff, ldb,
                          bias ? bias + N1 : nullptr, beta, act, C + N1, ldc, workspace,
-                         workspace_bytes, stream, 1, BatchStrides{}, amax, bps ? bps + boff : nullptr);
+                         workspace_bytes, stream, 1, BatchStrides{}, amax, bps ? bps + 2 * boff : nullptr);
     }
   }
   if (batch > 1) plan.S = 1;  // batched products are small: no split-K slab
