@@ -93,6 +93,9 @@ const char* mvml_version(void);
 #define MVML_OPT_GCN_SUBWAVE 12 /* MVML_GCN_SUBWAVE: mvml_gcn_agg at D <= 64 with four rows per
                                    wave, 16 lanes each (1), or one row per wave as at every
                                    other width (0); the two give the same bits */
+#define MVML_OPT_SAGE_SUBWAVE 13 /* MVML_SAGE_SUBWAVE: mvml_sage_max_fwd / mvml_sage_max_bwd at
+                                   D <= 64 with four rows per wave, 16 lanes each (1), or one
+                                   row per wave as at every other width (0); the same bits */
 int mvml_set_option(int option, int value);
 int mvml_get_option(int option);
 
@@ -593,6 +596,43 @@ int mvml_gcn_agg(int64_t num_nodes, const int32_t* rowptr, const int32_t* nbr, c
  * NULL. */
 int mvml_gcn_norm_scales(int64_t num_nodes, const int32_t* in_rowptr, const int32_t* out_rowptr,
                          int norm, float* src_scale, float* dst_scale, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * SAGEConv's aggregations beside the neighbour sum (dgl 0.9.1 SAGEConv.forward; restated, parity
+ * with dgl unpinned; csrc/sage_agg.hip).  `mean` is mvml_gcn_agg with norm "right".
+ *
+ * pool: the element-wise maximum over in-neighbours, over the in-CSR:
+ *   out[v, c] = max_s X[in_src[s], c],  s over [in_rowptr[v], in_rowptr[v+1]);
+ *   arg[v, c] = the global in-CSR slot s of the first slot in row order that attains it (a later
+ *               slot replaces the running maximum only when strictly greater).
+ * A row without entries gives out = 0 and arg = -1.  D a positive multiple of 4, <= 2048.  X, out
+ * and arg 16-byte aligned; ldx, ldo, lda multiples of 4 and >= D; out and arg must not alias X or
+ * each other.  Columns [D, ld) of X are never read and of out / arg never written.  out_amax /
+ * out_row_amax (may be NULL) as in mvml_gcn_agg.  Anything else: MVML_ERR_INVALID before any
+ * launch, nothing written.  A maximum rounds nothing: a row's bits depend on neither the kernel
+ * instance nor the batch the row is computed in.
+ *
+ * Its backward, over the out-CSR (a gather: no atomics, bitwise repeatable):
+ *   gX[u, c] = sum_t (arg[out_dst[t], c] == out_inslot[t] ? G[out_dst[t], c] : 0),
+ * t ascending over [out_rowptr[u], out_rowptr[u+1]), the sum started from 0 and rounded once per
+ * term.  The slot is compared, not the source id: of two parallel edges only the one at arg
+ * receives.  P (may be NULL; its own row stride): a ReLU output that was the forward's X; where
+ * P[u, c] <= 0 gX[u, c] is 0 (that ReLU's backward in the same pass).  gX must not alias G or arg.
+ * ------------------------------------------------------------------------------------- */
+int mvml_sage_max_fwd(int64_t num_nodes, const int32_t* in_rowptr, const int32_t* in_src,
+                      const float* X, int64_t ldx, int D, float* out, int64_t ldo, int32_t* arg,
+                      int64_t lda, uint32_t* out_amax, uint32_t* out_row_amax, void* stream);
+int mvml_sage_max_bwd(int64_t num_nodes, const int32_t* out_rowptr, const int32_t* out_dst,
+                      const int32_t* out_inslot, const float* G, int64_t ldg, const int32_t* arg,
+                      int64_t lda, int D, const float* P, int64_t ldp, float* gX, int64_t ldgx,
+                      void* stream);
+/* The gcn aggregator's factor scale[v] = 1 / (in_degree(v) + 1), rounded once from double, and
+ * its self term  out[v, 0:D) = act(scale[v] * X[v, 0:D) + out[v, 0:D) + bias)  (one fma, one add
+ * for the bias; bias may be NULL; act 0 none, 1 ReLU).  The self term's adjoint is the same call
+ * on the gradients without bias or act.  Shapes as mvml_gcn_agg's; out must not alias X. */
+int mvml_sage_gcn_scale(int64_t num_nodes, const int32_t* in_rowptr, float* scale, void* stream);
+int mvml_sage_self_add(int64_t num_nodes, const float* X, int64_t ldx, int D, const float* scale,
+                       const float* bias, int act, float* out, int64_t ldo, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Set2Set (dgl 0.9.1, model.py:82-84, 92) building blocks.

@@ -30,7 +30,7 @@ int check_launch(const char* what) {
 }
 
 // Kernel-path options (include/mvml_gat.h, MVML_OPT_*): environment defaults read once at load.
-constexpr int kOptCount = 13;
+constexpr int kOptCount = 14;
 static std::atomic<int> g_opt[kOptCount];
 static int env_int(const char* name, int dflt) {
   const char* e = getenv(name);
@@ -50,6 +50,7 @@ static const bool g_opt_init = [] {
   g_opt[MVML_OPT_DST_UNR] = env_int("MVML_DST_UNR", 0);
   g_opt[MVML_OPT_SMALLK] = env_int("MVML_SMALLK", 1);
   g_opt[MVML_OPT_GCN_SUBWAVE] = env_int("MVML_GCN_SUBWAVE", 1);
+  g_opt[MVML_OPT_SAGE_SUBWAVE] = env_int("MVML_SAGE_SUBWAVE", 1);
   return true;
 }();
 

@@ -20,10 +20,11 @@ from .smiles import RNNModule, collate_smiles, tokens_struct
 from .nn import GAT, GATConv, GATLayer, GATv2, GATv2Conv, GATv2Layer, GNNModule, GraphNorm, Set2Set, WeightAndSum, WeightedSumAndMax
 from .nn import GATPredictor, GATv2Predictor, MLPPredictor
 from .nn import GCN, GCNLayer, GCNPredictor, GraphConv
+from .nn import GraphSAGE, GraphSAGEPredictor, SAGEConv
 from .optim import FlatAdam
 from .mvp import MVP
 from .metrics import MultiLabelMeter, evaluate, evaluate_class_wise
 
-__all__ = ["MultiLabelMeter", "evaluate", "evaluate_class_wise","GNNModule", "MVFusion", "FPNModule", "RNNModule", "tokens_struct", "collate_smiles", "bce_with_logits", "GAT", "GATLayer", "GATConv", "GATv2", "GATv2Layer", "GATv2Conv", "Set2Set", "WeightAndSum", "WeightedSumAndMax", "GATPredictor", "GATv2Predictor", "MLPPredictor", "GraphConv", "GCNLayer", "GCN", "GCNPredictor", "GraphNorm", "BatchedMolGraph",
+__all__ = ["MultiLabelMeter", "evaluate", "evaluate_class_wise","GNNModule", "MVFusion", "FPNModule", "RNNModule", "tokens_struct", "collate_smiles", "bce_with_logits", "GAT", "GATLayer", "GATConv", "GATv2", "GATv2Layer", "GATv2Conv", "Set2Set", "WeightAndSum", "WeightedSumAndMax", "GATPredictor", "GATv2Predictor", "MLPPredictor", "GraphConv", "GCNLayer", "GCN", "GCNPredictor", "SAGEConv", "GraphSAGE", "GraphSAGEPredictor", "GraphNorm", "BatchedMolGraph",
            "MolGraph", "batch", "graph", "bigraph_from_bonds", "from_arrays", "lib", "MvmlError", "FlatAdam", "MVP"]
 __version__ = "0.1.0"

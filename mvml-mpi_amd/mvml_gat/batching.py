@@ -234,6 +234,7 @@ class BatchedMolGraph:
         bnn, bne, src_l, dst_l, flags = d["_inputs"]
         B, N, E = self.batch_size, self.num_nodes(), self.num_edges()
         d.pop("gcn_scales", None)  # GraphConv's degree factors (functional.gcn_scales) go with the indices
+        d.pop("sage_gcn_scale", None)  # ... and SAGEConv's 1 / (deg + 1) (functional.sage_gcn_scale)
         L = _lib.lib()
         wp, wn = _lib.ws_ptr_size(L.mvml_build_csr_workspace_size(B, N, E), self.device)
         P = _lib.ptr

@@ -84,7 +84,9 @@ def copy2d(dst, src):
 # GATLayerFunction.forward appends each layer's el/er to DEBUG_CAPTURE["elr_fwd"] and the
 # backward stores its saved el/er, attention and el/er gradients; LinearReLUFunction appends its
 # post-ReLU output to ["relu_out"], the fusion its Conv2d+ReLU output to ["conv_out"] and
-# WeightedSumAndMaxFunction its forward's argmax to ["readout_argmax"].  None in normal use.
+# WeightedSumAndMaxFunction its forward's argmax to ["readout_argmax"]; SAGEConvFunction appends its
+# post-ReLU output to ["sage_out"], fc_pool's to ["sage_pool"] and the neighbour maximum's owner
+# slots to ["sage_arg"].  None in normal use.
 DEBUG_CAPTURE = None
 
 
@@ -1083,46 +1085,50 @@ def linear_maxima(x, w):
     return LinearMaxima(amx, kx, xr, _split_weight(w, amx))
 
 
-def linear_fwd(x, weight, y, M, Nout, K, lm, bias=None, act=0):
-    """y = act(x W^T + b): the forward product of a Linear (per-row x scales when lm has them)."""
+def linear_fwd(x, weight, y, M, Nout, K, lm, bias=None, act=0, beta=0.0):
+    """y = act(x W^T + b + beta y): the forward product of a Linear (per-row x scales when lm has
+    them)."""
     if lm is not None and lm.xrows is not None:
-        gemm(x, weight, M, Nout, K, 0, 0, K, K, y, Nout, bias=bias, act=act, amax=(None, slot(lm.amx, 1)),
-             arows=lm.xrows, bil4=lm.wil)
+        gemm(x, weight, M, Nout, K, 0, 0, K, K, y, Nout, bias=bias, act=act, beta=beta,
+             amax=(None, slot(lm.amx, 1)), arows=lm.xrows, bil4=lm.wil)
     else:
-        gemm(x, weight, M, Nout, K, 0, 0, K, K, y, Nout, bias=bias, act=act,
+        gemm(x, weight, M, Nout, K, 0, 0, K, K, y, Nout, bias=bias, act=act, beta=beta,
              amax=None if lm is None else (slot(*lm.kx), slot(lm.amx, 1)),
              bil4=None if lm is None else lm.wil)
 
 
-def linear_dx(g, weight, gx, M, Nout, K, lm):
-    """gx = g W (the data gradient of a Linear; per-row g scales under ROW_SCALES)."""
+def linear_dx(g, weight, gx, M, Nout, K, lm, beta=0.0):
+    """gx = g W + beta gx (the data gradient of a Linear; per-row g scales under ROW_SCALES)."""
     if lm is not None and lm.xrows is not None:
-        gemm(g, weight, M, K, Nout, 0, 1, Nout, K, gx, K, amax=(None, slot(lm.amx, 1)),
+        gemm(g, weight, M, K, Nout, 0, 1, Nout, K, gx, K, beta=beta, amax=(None, slot(lm.amx, 1)),
              arows=absmax_rows(g, M, Nout, Nout), bil4=lm.wil)
     else:
-        gemm(g, weight, M, K, Nout, 0, 1, Nout, K, gx, K,
+        gemm(g, weight, M, K, Nout, 0, 1, Nout, K, gx, K, beta=beta,
              amax=None if lm is None else (slot(lm.amx, 2), slot(lm.amx, 1)),
              bil4=None if lm is None else lm.wil)
 
 
-def linear_forward(x, weight, bias, act=0):
+def linear_forward(x, weight, bias, act=0, onto=None):
     """y = act(x W^T + b) of an nn.Linear (weight [out, in]; bias may be None) as one GEMM with
-    a bias (+ ReLU, act 1) epilogue.  Returns (x, weight, y, lm): the contiguous operands and the
-    maxima record that linear_backward takes."""
+    a bias (+ ReLU, act 1) epilogue; onto: a contiguous [M, out] tensor the product is added to
+    before bias and act (the GEMM's beta = 1), and which is then y.  Returns (x, weight, y, lm): the
+    contiguous operands and the maxima record that linear_backward takes."""
     x = _c(x)
     M, K = x.shape
     Nout = weight.shape[0]
-    y = torch.empty((M, Nout), dtype=torch.float32, device=x.device)
+    y = torch.empty((M, Nout), dtype=torch.float32, device=x.device) if onto is None else onto
     weight = _c(weight)
     lm = linear_maxima(x, weight)
-    linear_fwd(x, weight, y, M, Nout, K, lm, bias=None if bias is None else _c(bias), act=act)
+    linear_fwd(x, weight, y, M, Nout, K, lm, bias=None if bias is None else _c(bias), act=act,
+               beta=0.0 if onto is None else 1.0)
     return x, weight, y, lm
 
 
-def linear_backward(x, weight, g, lm, need_gb=True, need_gx=True):
+def linear_backward(x, weight, g, lm, need_gb=True, need_gx=True, gx_acc=None):
     """(gx, gw, gb) of linear_forward from g, the contiguous gradient at its pre-activation:
     max |g| folded into lm's slot 2, gw = g^T x, gb = g's column sums, gx = g W (linear_dx);
-    gb / gx None where not wanted."""
+    gb / gx None where not wanted.  gx_acc: a gradient x already has from another branch; gx is
+    then that tensor with g W added by the product itself (beta = 1)."""
     M, K = x.shape
     Nout = weight.shape[0]
     if lm is not None:
@@ -1136,8 +1142,8 @@ def linear_backward(x, weight, g, lm, need_gb=True, need_gx=True):
         colsum(g, M, Nout, Nout, gb)
     gx = None
     if need_gx:
-        gx = torch.empty_like(x)
-        linear_dx(g, weight, gx, M, Nout, K, lm)
+        gx = torch.empty_like(x) if gx_acc is None else gx_acc
+        linear_dx(g, weight, gx, M, Nout, K, lm, beta=0.0 if gx_acc is None else 1.0)
     return gx, gw, gb
 
 
@@ -1680,3 +1686,200 @@ class GCNConvResidualFunction(torch.autograd.Function):
         gx, g_rw, g_rb = linear_backward(x, res_w, g_pre, ctx.lm, need_gb=ctx.has_res_b, need_gx=need)
         gX, gW, gb = _graph_conv_backward(A, Wp, conv, ctx.state, g_s, need, gx_acc=gx)
         return gX, gW, gb, g_rw, g_rb, None, None, None
+
+
+# ---- GraphSAGE (dgl 0.9.1 SAGEConv; csrc/sage_agg.hip) ------------------------------------------
+SAGE_AGGREGATORS = ("mean", "gcn", "pool")
+
+
+def sage_max_fwd_bytes(N, E, D):
+    """Algorithmic HBM bytes of one mvml_sage_max_fwd: read X, write out and arg once, the row
+    pointers and the neighbour ids (gcn_agg_bytes without the scale vectors, plus the arg row)."""
+    return 4 * (3 * N * D + N + 1 + E)
+
+
+def sage_max_bwd_bytes(N, E, D, gated):
+    """Algorithmic bytes of one mvml_sage_max_bwd: read G and arg (and the gate P) once, write gX,
+    the row pointers, the destination ids and the in-slots."""
+    return 4 * ((3 + int(bool(gated))) * N * D + N + 1 + 2 * E)
+
+
+def sage_gcn_scale(g):
+    """1 / (in_degree + 1) per atom of the device batch g (mvml_sage_gcn_scale), computed once and
+    kept on the batch as gcn_scales' factors are; BatchedMolGraph.recollate() drops it."""
+    s = g._dev.get("sage_gcn_scale")
+    if s is None:
+        N = g.num_nodes()
+        s = g._dev["sage_gcn_scale"] = torch.empty(max(N, 1), dtype=torch.float32, device=g.device)
+        call("mvml_sage_gcn_scale", N, ptr(g.in_rowptr), ptr(s), _stream(g.device))
+    return s
+
+
+def sage_max(X, ldx, D, g, rows=False):
+    """(out, arg) of mvml_sage_max_fwd on the [N, D] rows of X (row stride ldx) over g's in-CSR: new
+    dense [N, D] tensors, out's per-row maxima recorded on it (fold_rows) when `rows`."""
+    N, E = g.num_nodes(), g.num_edges()
+    dev = X.device
+    out = torch.empty((N, D), dtype=torch.float32, device=dev)
+    arg = torch.empty((N, D), dtype=torch.int32, device=dev)
+    rmx = torch.empty(max(N, 1), dtype=torch.int32, device=dev) if rows else None
+    _lib.call_tag[0] = {"layer": f"D{D}", "bytes": sage_max_fwd_bytes(N, E, D)}
+    call("mvml_sage_max_fwd", N, ptr(g.in_rowptr), ptr(g.in_src), ptr(X), ldx, D, ptr(out), D, ptr(arg), D, None,
+         ptr(rmx), _stream(dev))
+    if rows:
+        fold_rows(out, rmx)
+    return out, arg
+
+
+def sage_max_grad(G, arg, D, g, gate=None):
+    """mvml_sage_max_bwd: the [N, D] gradient of sage_max's input from G, the gradient at its
+    output, gathered over g's out-CSR at the saved arg; gate: the pooled ReLU output, whose
+    backward rides in the same pass."""
+    N, E = g.num_nodes(), g.num_edges()
+    gX = torch.empty((N, D), dtype=torch.float32, device=G.device)
+    _lib.call_tag[0] = {"layer": f"D{D}", "bytes": sage_max_bwd_bytes(N, E, D, gate is not None)}
+    call("mvml_sage_max_bwd", N, ptr(g.out_rowptr), ptr(g.out_dst), ptr(g.out_inslot), ptr(G), D, ptr(arg), D, D,
+         ptr(gate), D, ptr(gX), D, _stream(G.device))
+    return gX
+
+
+def sage_self_add(X, scale, out, bias=None, act=0):
+    """out = act(scale[:, None] * X + out + bias) in place on the dense [N, D] out (mvml_sage_self_add)."""
+    N, D = out.shape
+    call("mvml_sage_self_add", N, ptr(X), D, D, ptr(scale), ptr(bias), int(act), ptr(out), D, _stream(out.device))
+    return out
+
+
+def _share_rows(x, lm):
+    """Leave the per-row maxima that one Linear's forward took of x on x, for the next Linear
+    that reads the same tensor."""
+    if lm is not None and lm.xrows is not None and known_rows(x) is None:
+        fold_rows(x, lm.xrows)
+
+
+class SAGEConvFunction(torch.autograd.Function):
+    """dgl 0.9.1 SAGEConv.forward after feat_drop (restated; parity with dgl is unpinned), as ONE
+    autograd node:
+      mean: act(fc_self(x) + fc_neigh(mean_in x) + b)       (mvml_gcn_agg, norm "right")
+      gcn:  act(fc_neigh((sum_in x + x) / (deg + 1)) + b)   (mvml_gcn_agg, mvml_sage_self_add)
+      pool: act(fc_self(x) + fc_neigh(max_in relu(fc_pool(x))) + b)   (mvml_sage_max_fwd)
+    mean and gcn apply fc_neigh before the aggregation when in_feats > out_feats, as DGL does, and
+    whenever in_feats is no multiple of 4 (the aggregation's float4 rows; the same function); pool
+    runs its in_feats-wide middle zero-padded to a multiple of 4.  The products are nn.Linear
+    products on the fp32-accurate GEMM; the second branch's product adds onto the first's output
+    (beta = 1) with bias and ReLU in its epilogue, so no separate add runs.  Backward: the input
+    feeds fc_self and the neighbour branch (and fc_pool); the later data-gradient product
+    accumulates onto the earlier one (beta = 1), so the autograd engine adds nothing.  The
+    maximum's backward is a gather at the saved arg with fc_pool's ReLU folded in."""
+
+    @staticmethod
+    def forward(ctx, X, w_pool, b_pool, w_self, w_neigh, bias, g, aggr, act):
+        for t, n in ((X, "feat"), (w_pool, "fc_pool.weight"), (b_pool, "fc_pool.bias"), (w_self, "fc_self.weight"),
+                     (w_neigh, "fc_neigh.weight"), (bias, "bias")):
+            if t is not None:
+                _check_cuda_f32(t, n)
+        if aggr not in SAGE_AGGREGATORS:
+            raise KeyError(f"Aggregator type {aggr} not recognized.")
+        N, Fin = X.shape
+        Fout = w_neigh.shape[0]
+        Fp = _round4(Fin)
+        dev = X.device
+        bias = None if bias is None else _c(bias)
+        rows = GEMM_ALGO == "f16x2" and ROW_SCALES
+        proj_first = aggr != "pool" and (Fin > Fout or Fp != Fin)
+        P = M = arg = A = lm_p = lm_s = wp = ws = None
+        if aggr == "pool":
+            wp, bp, wn = w_pool, b_pool, w_neigh
+            if Fp != Fin:  # the pooled rows and fc_neigh's K zero-padded to float4 rows (zeros add nothing)
+                wp = zeros((Fp, Fin), device=dev)
+                copy2d(wp[:Fin], _c(w_pool))
+                bp = zeros(Fp, device=dev)
+                copy2d(bp[:Fin], _c(b_pool))
+                wn = zeros((Fout, Fp), device=dev)
+                copy2d(wn[:, :Fin], _c(w_neigh))
+            x, wp, P, lm_p = linear_forward(X, wp, bp, act=1)
+            _share_rows(x, lm_p)
+            M, arg = sage_max(P, Fp, Fp, g, rows=rows)
+            _, ws, out, lm_s = linear_forward(x, w_self, None)
+            _, wn, out, lm_n = linear_forward(M, wn, bias, act=act, onto=out)
+            if DEBUG_CAPTURE is not None:  # fc_pool's ReLU sides and the maximum's ties (parity tests)
+                DEBUG_CAPTURE.setdefault("sage_pool", []).append(P.detach().clone())
+                DEBUG_CAPTURE.setdefault("sage_arg", []).append(arg.detach().clone())
+        elif aggr == "mean":
+            scales = gcn_scales(g, "right")
+            if proj_first:
+                x, wn, Y, lm_n = linear_forward(X, w_neigh, None)
+                _share_rows(x, lm_n)
+                H = gcn_agg(Y, Fout, Fout, g, scales)
+                _, ws, out, lm_s = linear_forward(x, w_self, bias, act=act, onto=H)
+            else:
+                x = _c(X)
+                A = gcn_agg(x, Fin, Fin, g, scales, rows=rows)
+                _, ws, out, lm_s = linear_forward(x, w_self, None)
+                _, wn, out, lm_n = linear_forward(A, w_neigh, bias, act=act, onto=out)
+        else:
+            s = sage_gcn_scale(g)
+            if proj_first:
+                x, wn, Y, lm_n = linear_forward(X, w_neigh, None)
+                out = gcn_agg(Y, Fout, Fout, g, (None, s))
+                sage_self_add(Y, s, out, bias, act)
+            else:
+                x = _c(X)
+                A = gcn_agg(x, Fin, Fin, g, (None, s))
+                sage_self_add(x, s, A)
+                _, wn, out, lm_n = linear_forward(A, w_neigh, bias, act=act)
+        if DEBUG_CAPTURE is not None and act:  # the ReLU sides the product took (parity tests)
+            DEBUG_CAPTURE.setdefault("sage_out", []).append(out.detach().clone())
+        ctx.save_for_backward(x, wp, ws, wn, P, M, arg, A, out if act else None)
+        ctx.state = (g, aggr, proj_first, Fin, Fout, Fp, lm_p, lm_s, lm_n, bias is not None)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        x, wp, ws, wn, P, M, arg, A, out = ctx.saved_tensors
+        g, aggr, proj_first, Fin, Fout, Fp, lm_p, lm_s, lm_n, has_bias = ctx.state
+        N = x.shape[0]
+        dev = x.device
+        need = ctx.needs_input_grad[0]
+        g_out = _c(g_out)
+        if out is not None:
+            g_pre = torch.empty_like(g_out)
+            call("mvml_relu_bwd", g_out.numel(), ptr(out), ptr(g_out), ptr(g_pre), 1.0, _stream(dev))
+        else:
+            g_pre = g_out
+        gb = None
+        if has_bias:
+            gb = torch.empty(Fout, dtype=torch.float32, device=dev)
+            colsum(g_pre, N, Fout, Fout, gb)
+        gX = gWp = gbp = gWs = None
+        if aggr == "pool":
+            gM, gWn, _ = linear_backward(M, wn, g_pre, lm_n, need_gb=False)
+            gP = sage_max_grad(gM, arg, Fp, g, gate=P)
+            gX, gWp, gbp = linear_backward(x, wp, gP, lm_p, need_gx=need)
+            gX, gWs, _ = linear_backward(x, ws, g_pre, lm_s, need_gb=False, need_gx=need, gx_acc=gX)
+            if Fp != Fin:
+                gWp, gbp = gWp[:Fin], gbp[:Fin]
+                gWn = copy2d(torch.empty((Fout, Fin), dtype=torch.float32, device=dev), gWn[:, :Fin])
+        elif aggr == "mean":
+            scales = gcn_scales(g, "right")
+            if proj_first:
+                gX, gWs, _ = linear_backward(x, ws, g_pre, lm_s, need_gb=False, need_gx=need)
+                gY = gcn_agg(g_pre, Fout, Fout, g, scales, transpose=True)
+                gX, gWn, _ = linear_backward(x, wn, gY, lm_n, need_gb=False, need_gx=need, gx_acc=gX)
+            else:
+                gA, gWn, _ = linear_backward(A, wn, g_pre, lm_n, need_gb=False, need_gx=need)
+                if need:
+                    gX = gcn_agg(gA, Fin, Fin, g, scales, transpose=True)
+                _, gWs, _ = linear_backward(x, ws, g_pre, lm_s, need_gb=False, need_gx=need, gx_acc=gX)
+        else:
+            s = sage_gcn_scale(g)
+            if proj_first:
+                gY = gcn_agg(g_pre, Fout, Fout, g, (None, s), transpose=True)
+                sage_self_add(g_pre, s, gY)
+                gX, gWn, _ = linear_backward(x, wn, gY, lm_n, need_gb=False, need_gx=need)
+            else:
+                gA, gWn, _ = linear_backward(A, wn, g_pre, lm_n, need_gb=False, need_gx=need)
+                if need:
+                    gX = gcn_agg(gA, Fin, Fin, g, (None, s), transpose=True)
+                    sage_self_add(gA, s, gX)
+        return gX, gWp, gbp, gWs, gWn, gb, None, None, None

@@ -9,6 +9,8 @@ Drop-in replacements, on the MI355X HIP path, for
   * dgllife 0.3.0 ``MLPPredictor`` / ``GATPredictor`` / ``GATv2Predictor`` (the single-view graph
     classifiers; not in model.py),
   * dgl 0.9.1 ``GraphConv`` and dgllife 0.3.0 ``GCNLayer`` / ``GCN`` / ``GCNPredictor`` (the GCN
+    baseline; not in model.py),
+  * dgl 0.9.1 ``SAGEConv`` and dgllife 0.3.0 ``GraphSAGE`` / ``GraphSAGEPredictor`` (the GraphSAGE
     baseline; not in model.py).
 Parameter names/shapes/registration order follow the reference so a ``net_i.pkl``
 ``model_state_dict`` (keys under ``gnn.``) loads unchanged.
@@ -749,6 +751,144 @@ class GCNPredictor(nn.Module):
             predictor_dropout = classifier_dropout
         self.gnn = GCN(in_feats=in_feats, hidden_feats=hidden_feats, gnn_norm=gnn_norm, activation=activation,
                        residual=residual, batchnorm=batchnorm, dropout=dropout)
+        gnn_out_feats = self.gnn.hidden_feats[-1]
+        self.readout = WeightedSumAndMax(gnn_out_feats)
+        self.predict = MLPPredictor(2 * gnn_out_feats, predictor_hidden_feats, n_tasks, predictor_dropout)
+
+    def forward(self, bg, feats):
+        node_feats = self.gnn(bg, feats)
+        return self.predict(self.readout(bg, node_feats))
+
+
+class SAGEConv(nn.Module):
+    """dgl.nn.pytorch.SAGEConv (0.9.1; restated, parity with dgl is unpinned), aggregator_type
+    "mean", "gcn" or "pool".  Members in dgl's order: fc_pool = Linear(in_feats, in_feats) (pool
+    only), fc_self = Linear(in_feats, out_feats, bias=False) (absent for gcn), fc_neigh =
+    Linear(in_feats, out_feats, bias=False), bias [out_feats] (zeros; a None buffer with
+    bias=False); the three weights xavier-uniform with the ReLU gain.  forward(graph, feat) =
+    activation(fc_self(h) + h_neigh + bias) (gcn: activation(h_neigh + bias)) with h =
+    feat_drop(feat) read by both branches, on Fn.SAGEConvFunction: the neighbour mean / sum on
+    csrc/gcn_agg.hip, the neighbour maximum and gcn's self term on csrc/sage_agg.hip, the products
+    on the fp32-accurate GEMM.  An atom without in-edges has h_neigh = 0 (mean, pool) or its own
+    row (gcn), as in DGL, which has no zero-in-degree check here.  activation: None or ReLU;
+    "lstm", norm, edge weights and a (source, destination) feature pair are refused.  A checkpoint
+    of a DGL release that keeps the bias inside fc_self (fc_self.bias, no bias) loads into bias."""
+
+    def __init__(self, in_feats, out_feats, aggregator_type, feat_drop=0., bias=True, norm=None, activation=None):
+        super().__init__()
+        if aggregator_type == "lstm":
+            raise NotImplementedError("SAGEConv: the lstm aggregator is not on the HIP path")
+        if aggregator_type not in Fn.SAGE_AGGREGATORS:
+            raise KeyError(f"Aggregator type {aggregator_type} not recognized.")
+        if norm is not None:
+            raise NotImplementedError("SAGEConv: norm is not on the HIP path")
+        if activation is not None and not _is_relu(activation):
+            raise ValueError("SAGEConv: activation must be None or ReLU (F.relu, torch.relu, nn.ReLU()) on the HIP path")
+        if not 0.0 <= feat_drop < 1.0:
+            raise ValueError("SAGEConv: feat_drop must be in [0, 1) on the HIP path")
+        # the aggregation kernels' range (csrc/gcn_agg.hip, csrc/sage_agg.hip): refuse here, not in forward
+        if out_feats <= 0 or out_feats % 4 or out_feats > 2048:
+            raise ValueError(f"SAGEConv: out_feats must be a positive multiple of 4 <= 2048 (got {out_feats})")
+        if in_feats <= 0 or (aggregator_type == "pool" and in_feats > 2048):
+            raise ValueError(f"SAGEConv: in_feats must be positive (pool: <= 2048), got {in_feats}")
+        self._in_src_feats = self._in_dst_feats = in_feats
+        self._out_feats = out_feats
+        self._aggre_type = aggregator_type
+        self._allow_zero_in_degree = True  # (no such check in DGL's SAGEConv)
+        self.norm = norm
+        self.feat_drop = nn.Dropout(feat_drop)
+        self.activation = activation
+        if aggregator_type == "pool":
+            self.fc_pool = nn.Linear(in_feats, in_feats)
+        if aggregator_type != "gcn":
+            self.fc_self = nn.Linear(in_feats, out_feats, bias=False)
+        self.fc_neigh = nn.Linear(in_feats, out_feats, bias=False)
+        if bias:
+            self.bias = nn.Parameter(torch.zeros(out_feats))
+        else:
+            self.register_buffer("bias", None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        gain = nn.init.calculate_gain("relu")
+        if self._aggre_type == "pool":
+            nn.init.xavier_uniform_(self.fc_pool.weight, gain=gain)
+        if self._aggre_type != "gcn":
+            nn.init.xavier_uniform_(self.fc_self.weight, gain=gain)
+        nn.init.xavier_uniform_(self.fc_neigh.weight, gain=gain)
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys,
+                              unexpected_keys, error_msgs):
+        """Accept both DGL SAGEConv layouts: dgl 0.9.1 keeps an explicit ``bias`` and a bias-free
+        ``fc_self``; other releases keep it inside fc_self (``fc_self.bias``, no ``bias``).  The
+        arithmetic is the same, so the folded form loads into ``bias`` (GATConv's rule for
+        res_fc.bias)."""
+        sb, b = prefix + "fc_self.bias", prefix + "bias"
+        if self._aggre_type != "gcn" and self.bias is not None and sb in state_dict and b not in state_dict:
+            state_dict[b] = state_dict.pop(sb)
+        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys,
+                                      unexpected_keys, error_msgs)
+
+    _check_graph = GATConv._check_graph
+
+    def forward(self, graph, feat, edge_weight=None):
+        if edge_weight is not None:
+            raise NotImplementedError("SAGEConv: edge weights are not on the HIP path")
+        if isinstance(feat, (tuple, list)):
+            raise NotImplementedError("SAGEConv: a (source, destination) feature pair is not on the HIP path")
+        self._check_graph(graph)
+        h = Fn.dropout(feat, Fn.dropout_p(self.feat_drop))
+        pool, gcn = self._aggre_type == "pool", self._aggre_type == "gcn"
+        return Fn.SAGEConvFunction.apply(h, self.fc_pool.weight if pool else None, self.fc_pool.bias if pool else None,
+                                         None if gcn else self.fc_self.weight, self.fc_neigh.weight, self.bias, graph,
+                                         self._aggre_type, int(self.activation is not None))
+
+
+class GraphSAGE(nn.Module):
+    """dgllife.model.gnn.graphsage.GraphSAGE (0.3.0; restated, parity with dgllife is unpinned)
+    with its defaults: hidden_feats [64, 64], per layer activation F.relu, dropout 0 and
+    aggregator_type "mean"; gnn_layers a ModuleList of SAGEConv(in, hidden, aggregator, dropout,
+    activation=activation)."""
+
+    def __init__(self, in_feats, hidden_feats=None, activation=None, dropout=None, aggregator_type=None):
+        super().__init__()
+        hidden_feats = list(hidden_feats) if hidden_feats is not None else [64, 64]
+        n = len(hidden_feats)
+        activation = activation if activation is not None else [F.relu] * n
+        dropout = dropout if dropout is not None else [0.] * n
+        aggregator_type = aggregator_type if aggregator_type is not None else ["mean"] * n
+        lengths = [len(hidden_feats), len(activation), len(dropout), len(aggregator_type)]
+        assert len(set(lengths)) == 1, (
+            "Expect the lengths of hidden_feats, activation, dropout and aggregator_type to be the same, "
+            f"got {lengths}")
+        self.hidden_feats = hidden_feats
+        self.gnn_layers = nn.ModuleList()
+        for i in range(n):
+            self.gnn_layers.append(SAGEConv(in_feats, hidden_feats[i], aggregator_type[i], dropout[i],
+                                            activation=activation[i]))
+            in_feats = hidden_feats[i]
+
+    def reset_parameters(self):
+        for gnn in self.gnn_layers:
+            gnn.reset_parameters()
+
+    def forward(self, g, feats):
+        for gnn in self.gnn_layers:
+            feats = gnn(g, feats)
+        return feats
+
+
+class GraphSAGEPredictor(nn.Module):
+    """dgllife.model.model_zoo.graphsage_predictor.GraphSAGEPredictor (0.3.0; restated, parity with
+    dgllife is unpinned): gnn = GraphSAGE(...) -> readout = WeightedSumAndMax(hidden_feats[-1]) ->
+    predict = MLPPredictor(2 * hidden_feats[-1], predictor_hidden_feats, n_tasks, predictor_dropout).
+    forward(bg, feats) returns (B, n_tasks) logits."""
+
+    def __init__(self, in_feats, hidden_feats=None, activation=None, dropout=None, aggregator_type=None,
+                 n_tasks=1, predictor_hidden_feats=128, predictor_dropout=0.):
+        super().__init__()
+        self.gnn = GraphSAGE(in_feats=in_feats, hidden_feats=hidden_feats, activation=activation, dropout=dropout,
+                             aggregator_type=aggregator_type)
         gnn_out_feats = self.gnn.hidden_feats[-1]
         self.readout = WeightedSumAndMax(gnn_out_feats)
         self.predict = MLPPredictor(2 * gnn_out_feats, predictor_hidden_feats, n_tasks, predictor_dropout)
