@@ -273,19 +273,6 @@ extern "C" int mvml_gat_attn_grad(int64_t num_nodes, int H, int F, const float* 
   return check_launch("attn_grad");
 }
 
-extern "C" int mvml_gat_fold_weights(const float* fc_w, const float* res_fc_w, const float* attn_lr,
-                                     int H, int F, int Fin, int ldw, int mean_residual, float* Wcat,
-                                     void* stream) {
-  clear_error();
-  MVML_REQUIRE(H > 0 && F > 0 && Fin > 0 && ldw >= Fin, "gat_fold_weights: bad shape");
-  hipStream_t st = as_stream(stream);
-  const int res = mean_residual ? MVML_RES_MEAN : MVML_RES_PROJ;
-  const int64_t total = (int64_t)(mvml_gat_proj_cols_res(H, F, res) + (attn_lr ? 2 * H : 0)) * ldw;
-  const unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(total, 256), 8192);
-  fold_weights_kernel<<<blocks, 256, 0, st>>>(fc_w, res_fc_w, attn_lr, H, F, Fin, ldw, res, Wcat);
-  return check_launch("fold_weights_kernel");
-}
-
 extern "C" int mvml_gat_fold_weights_res(const float* fc_w, const float* res_fc_w, const float* attn_lr,
                                          int H, int F, int Fin, int ldw, int res, float* Wcat,
                                          void* stream) {
@@ -301,17 +288,12 @@ extern "C" int mvml_gat_fold_weights_res(const float* fc_w, const float* res_fc_
   return check_launch("fold_weights_kernel");
 }
 
-extern "C" int mvml_gat_unfold_grads(const float* gWcat, const float* attn_lr, int H, int F,
-                                     int Fin, int ldg, int mean_residual, float* g_fc_w,
-                                     float* g_res_fc_w, void* stream) {
-  clear_error();
-  MVML_REQUIRE(H > 0 && F > 0 && Fin > 0 && ldg >= Fin, "gat_unfold_grads: bad shape");
-  hipStream_t st = as_stream(stream);
-  const int64_t total = (int64_t)H * F * Fin;
-  const unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(total, 256), 8192);
-  unfold_w_kernel<<<blocks, 256, 0, st>>>(gWcat, attn_lr, H, F, Fin, ldg,
-                                          mean_residual ? MVML_RES_MEAN : MVML_RES_PROJ, g_fc_w, g_res_fc_w);
-  return check_launch("unfold_w_kernel");
+// (the entries without _res: the same checks, so a NULL res_fc_w / g_res_fc_w is refused there too)
+extern "C" int mvml_gat_fold_weights(const float* fc_w, const float* res_fc_w, const float* attn_lr,
+                                     int H, int F, int Fin, int ldw, int mean_residual, float* Wcat,
+                                     void* stream) {
+  return mvml_gat_fold_weights_res(fc_w, res_fc_w, attn_lr, H, F, Fin, ldw,
+                                   mean_residual ? MVML_RES_MEAN : MVML_RES_PROJ, Wcat, stream);
 }
 
 extern "C" int mvml_gat_unfold_grads_res(const float* gWcat, const float* attn_lr, int H, int F,
@@ -327,4 +309,11 @@ extern "C" int mvml_gat_unfold_grads_res(const float* gWcat, const float* attn_l
   const unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(total, 256), 8192);
   unfold_w_kernel<<<blocks, 256, 0, st>>>(gWcat, attn_lr, H, F, Fin, ldg, res, g_fc_w, g_res_fc_w);
   return check_launch("unfold_w_kernel");
+}
+
+extern "C" int mvml_gat_unfold_grads(const float* gWcat, const float* attn_lr, int H, int F,
+                                     int Fin, int ldg, int mean_residual, float* g_fc_w,
+                                     float* g_res_fc_w, void* stream) {
+  return mvml_gat_unfold_grads_res(gWcat, attn_lr, H, F, Fin, ldg,
+                                   mean_residual ? MVML_RES_MEAN : MVML_RES_PROJ, g_fc_w, g_res_fc_w, stream);
 }

@@ -28,52 +28,13 @@ import pytest
 import torch
 
 import _gemm_cases as G
+from _placed import Placed
 from mvml_gat._lib import MvmlError, call, lib, option, stream_ptr, ws_ptr_size
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-MARGIN = 64      # floats of poison before and after an operand (a multiple of 4: keeps 16-B alignment)
 GROUPS = G.groups()
 MARGINS = {}
-
-
-def _poison(n):
-    return torch.full((n,), G.POISON_BITS, dtype=torch.int32, device=DEV).view(torch.float32)
-
-
-class Placed:
-    """[batch][rows][cols] at pitch ld and batch stride (rows + tail_rows) ld + gap inside a
-    poisoned buffer, `off` floats past a 16-B aligned address."""
-
-    def __init__(self, shape, ld, off=0, gap=0, tail_rows=0, data=None):
-        self.batch, self.rows, self.cols = shape
-        self.ld, self.stride = ld, (self.rows + tail_rows) * ld + gap
-        self.start = MARGIN + off
-        self.buf = _poison(self.start + self.batch * self.stride + MARGIN)
-        ar = torch.arange
-        self.idx = (self.start + ar(self.batch)[:, None, None] * self.stride + ar(self.rows)[None, :, None] * ld
-                    + ar(self.cols)[None, None, :])
-        if data is not None:
-            self.buf[self.idx.to(DEV)] = data.to(DEV).reshape(shape).to(self.buf.dtype)
-
-    def ptr(self, z=0):
-        return ctypes.c_void_p(self.buf.data_ptr() + 4 * (self.start + z * self.stride))
-
-    def read(self, dtype=torch.float32):
-        return self.buf.view(dtype).cpu()[self.idx]
-
-    def outside(self):
-        """(count, first (batch, row, col) position) of buffer words outside the matrix that are
-        no longer the poison."""
-        full = self.buf.view(torch.int32).cpu()
-        keep = torch.ones(full.numel(), dtype=torch.bool)
-        keep[self.idx.reshape(-1)] = False
-        bad = (keep & (full != G.POISON_BITS)).nonzero().reshape(-1)
-        if bad.numel() == 0:
-            return 0, None
-        o = int(bad[0]) - self.start
-        z, r = divmod(o, self.stride) if o >= 0 else (-1, o)
-        return int(bad.numel()), (z, r // self.ld, r % self.ld)
 
 
 def _p(t):
