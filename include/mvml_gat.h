@@ -561,7 +561,9 @@ int mvml_gatv2_agg_bwd(int64_t num_nodes, const int32_t* in_rowptr, const int32_
                        int64_t ldgzl, float* gZR, int64_t ldgzr, float* gR, int64_t ldgr,
                        float* g_attn_vec, void* workspace, size_t workspace_bytes, void* stream);
 /* dst[r][0:cols) += src[r][0:cols) (row pitches lds, ldd; cols % 4 == 0, rows 16-byte aligned):
- * share_weights adds gZR onto gZL before the single weight block's products. */
+ * share_weights adds gZR onto gZL before the single weight block's products.  Refused with
+ * MVML_ERR_INVALID before any launch: cols <= 0 or cols % 4 != 0, a NULL or not 16-byte aligned
+ * src or dst, a pitch below cols or not a multiple of 4.  rows == 0: MVML_OK, nothing written. */
 int mvml_add_cols_f32(int64_t rows, int cols, const float* src, int64_t lds, float* dst, int64_t ldd,
                       void* stream);
 
@@ -745,6 +747,16 @@ int mvml_wsum_max_bwd(int64_t B, int64_t N, int D, const int64_t* node_offsets, 
  * GraphNorm (torch_geometric 2.2.0, eps, batch=None at model.py:93): independent statistics
  * per normalisation group (group_offsets int64[G+1], in rows); the reference's group is its
  * 64-molecule mini-batch (config.py:21).
+ *   x, y, g_y, g_x: dense [rows, D], rows = group_offsets[G]; weight, bias, mean_scale and the
+ *   three parameter gradients: [D].  eps is the fp32 value given, widened to double: statistics
+ *   and per-element arithmetic run in fp64 and each output is rounded to fp32 once.  An empty
+ *   group writes nothing in the forward and adds exact zeros to the parameter gradients.
+ *   g_weight, g_bias, g_mean_scale may each be NULL (not formed; the others are bitwise the same).
+ *   The backward's fp64 partials use the first mvml_graphnorm_bwd_workspace_size(G, D) bytes of
+ *   `workspace` and nothing past them; sums run in a fixed order (bitwise repeatable).
+ * Refused before any launch, nothing written: MVML_ERR_INVALID for G < 0, G >= 2^31, D <= 0, or
+ * (G > 0) a NULL group_offsets, x, weight, bias / g_y, mean_scale, y / g_x; MVML_ERR_WORKSPACE for
+ * a NULL workspace or fewer bytes than mvml_graphnorm_bwd_workspace_size(G, D).  G == 0: MVML_OK.
  * ------------------------------------------------------------------------------------- */
 int mvml_graphnorm_fwd(int64_t G, int D, const int64_t* group_offsets, const float* x,
                        const float* weight, const float* bias, const float* mean_scale,
@@ -803,7 +815,9 @@ int mvml_batchnorm1d_bwd(int64_t M, int C, const float* x, int64_t ldx, const fl
 /* Small elementwise helpers.  ReLU backward (threshold_backward on the output), times the
  * Dropout scale when a Dropout followed the ReLU (scale = 1 / (1 - p), 1 without one):
  * g_x = g_y * scale * (y > 0).  y is the DROPPED output: a dropped element reads 0, so its
- * gradient is 0 without a stored mask (nn.Dropout's backward is g * mask * scale). */
+ * gradient is 0 without a stored mask (nn.Dropout's backward is g * mask * scale).  scale == 1
+ * copies g_y's bits; otherwise one fp32 multiply.  y = +-0, negative or NaN gives +0.  n < 0 or
+ * (n > 0) a NULL y, g_y or g_x: MVML_ERR_INVALID before any launch. */
 int mvml_relu_bwd(int64_t n, const float* y, const float* g_y, float* g_x, float scale, void* stream);
 /* nn.Dropout(p) in training mode (model.py:87, 36, 46; torch's fused_dropout): y = x * keep /
  * (1 - p), x == y allowed; element i kept iff a 32-bit counter-based hash of (seed, i) is at
@@ -850,7 +864,20 @@ int mvml_scale_by(int64_t n, const float* x, const float* s, float* y, void* str
  *   mvml_conv3_fwd/_bwd: Conv2d(12, 12, kernel 3) + ReLU on att (model.py:27, 69):
  *     in [B, 12, 3, W] -> out [B, 12, W-2] (post-ReLU); bwd gives g_in, g_weight [12,12,3,3],
  *     g_bias [12] (deterministic partial sums; workspace mvml_conv3_bwd_workspace_size(B)).
- *   mvml_bce_logits: BCEWithLogitsLoss (mean, main.py:91) element terms and dL/dz.
+ *   mvml_bce_logits: BCEWithLogitsLoss (mean, main.py:91) element terms and dL/dz:
+ *     loss_terms[i] = max(z, 0) - z y + log1p(exp(-|z|)), g_z[i] = (sigmoid(z) - y) / n, i < n
+ *     (z, y, loss_terms, g_z dense [n]; y any target in [0, 1]).
+ * Contracts of the row entries, each refused with MVML_ERR_INVALID before any launch and with
+ * nothing written:
+ *   mvml_layernorm_fwd / _bwd: rows < 0, D <= 0 or D > 512, a pitch (ldx, ldy / ldgy, ldgx) below
+ *     D, or (rows > 0) a NULL x, gamma, beta, y, mean, rstd / x, gamma, mean, rstd, g_y, g_x,
+ *     g_y_xhat.  x, y, g_y, g_x are pitched rows (only the D columns of a row are read or
+ *     written); mean, rstd are dense [rows]; g_y_xhat is DENSE [rows, D] (it has no pitch).
+ *   mvml_token_attn_fwd / _bwd: B < 0, H <= 0, dk outside the set above, ld or ldg below 3 H dk,
+ *     or (B > 0) a NULL qkv, att, P / qkv, P, g_att, g_qkv.  att, g_att [B, H, 3, dk] and
+ *     P [B, H, 3, 3] are dense; qkv and g_qkv are pitched rows 3b+t of 3 H dk columns.
+ *   mvml_bce_logits: n < 0, or (n > 0) a NULL z, y, loss_terms or g_z.
+ * rows == 0 / B == 0 / n == 0: MVML_OK, nothing written.
  * ------------------------------------------------------------------------------------- */
 int mvml_layernorm_fwd(int64_t rows, int D, const float* x, int64_t ldx, const float* gamma,
                        const float* beta, float eps, float* y, int64_t ldy, float* mean,
@@ -1031,6 +1058,12 @@ int mvml_bilstm_wide_bwd(int64_t T, int64_t B, int D, const int32_t* batch_sizes
  * across ranks, one whose all-reduced flag is 0).  Parameters occupy [param_off[i],
  * param_off[i] + n_i) of the flat buffers; a static chunk table (chunk c covers
  * [chunk_beg[c], chunk_end[c]) of parameter chunk_param[c]) gives one workgroup per chunk.
+ * The table's contract: the chunks of parameter i tile [param_off[i], param_off[i] + n_i) exactly
+ * (no overlap, no hole; an empty parameter may have one empty chunk), no chunk straddles two
+ * parameters, and param_off[i] % 4 == 0.  The pad floats between segments are never read or
+ * written.  Refused with MVML_ERR_INVALID before any launch, nothing written: nchunks < 0 or
+ * >= 2^31, P < 0, numel < 0, a NULL flat / flags / steps, (nchunks > 0) a NULL chunk table,
+ * param_off, src / param, grad, exp_avg, exp_avg_sq, or betas outside [0, 1), eps < 0, lr < 0.
  * ------------------------------------------------------------------------------------- */
 /* flat[param_off[i] ..] = the gradient at src[i] (a device pointer, 0 = none: zeros), and
  * flat[numel + i] = 1.0 / 0.0 (the presence flag) for i < P. */

@@ -413,6 +413,7 @@ extern "C" int mvml_layernorm_fwd(int64_t rows, int D, const float* x, int64_t l
   MVML_REQUIRE(rows >= 0 && D > 0 && D <= 64 * kFuseMaxVpl && ldx >= D && ldy >= D,
                "layernorm_fwd: bad shape (D must be <= %d)", 64 * kFuseMaxVpl);
   if (rows == 0) return MVML_OK;
+  MVML_REQUIRE(x && gamma && beta && y && mean && rstd, "layernorm_fwd: NULL pointer");
   layernorm_fwd_kernel<<<(unsigned)ceil_div(rows, 4), 256, 0, as_stream(stream)>>>(
       rows, D, x, ldx, gamma, beta, eps, y, ldy, mean, rstd);
   return check_launch("layernorm_fwd_kernel");
@@ -426,6 +427,7 @@ extern "C" int mvml_layernorm_bwd(int64_t rows, int D, const float* x, int64_t l
   MVML_REQUIRE(rows >= 0 && D > 0 && D <= 64 * kFuseMaxVpl && ldx >= D && ldgy >= D && ldgx >= D,
                "layernorm_bwd: bad shape");
   if (rows == 0) return MVML_OK;
+  MVML_REQUIRE(x && gamma && mean && rstd && g_y && g_x && g_y_xhat, "layernorm_bwd: NULL pointer");
   layernorm_bwd_kernel<<<(unsigned)ceil_div(rows, 4), 256, 0, as_stream(stream)>>>(
       rows, D, x, ldx, gamma, mean, rstd, g_y, ldgy, g_x, ldgx, g_y_xhat);
   return check_launch("layernorm_bwd_kernel");
@@ -437,6 +439,7 @@ extern "C" int mvml_token_attn_fwd(int64_t B, int H, int dk, const float* qkv, i
   MVML_REQUIRE(B >= 0 && H > 0 && fuse_dk_ok(dk) && ld >= 3 * (int64_t)H * dk,
                "token_attn_fwd: " MVML_DK_SET " and ld >= 3*H*dk");
   if (B == 0) return MVML_OK;
+  MVML_REQUIRE(qkv && att && P, "token_attn_fwd: NULL pointer");
   return by_width(dk, [&](auto mask, auto kv) {
     token_attn_fwd_kernel<mask.value, kv.value>
         <<<(unsigned)ceil_div(B * H, 4), 256, 0, as_stream(stream)>>>(B, H, dk, qkv, ld, scale, att, P);
@@ -452,6 +455,7 @@ extern "C" int mvml_token_attn_bwd(int64_t B, int H, int dk, const float* qkv, i
                    ldg >= 3 * (int64_t)H * dk,
                "token_attn_bwd: bad shape (" MVML_DK_SET ")");
   if (B == 0) return MVML_OK;
+  MVML_REQUIRE(qkv && P && g_att && g_qkv, "token_attn_bwd: NULL pointer");
   return by_width(dk, [&](auto mask, auto kv) {
     token_attn_bwd_kernel<mask.value, kv.value><<<(unsigned)ceil_div(B * H, 4), 256, 0, as_stream(stream)>>>(
         B, H, dk, qkv, ld, scale, P, g_att, g_qkv, ldg);
@@ -494,6 +498,7 @@ extern "C" int mvml_bce_logits(int64_t n, const float* z, const float* y, float*
   clear_error();
   MVML_REQUIRE(n >= 0, "bce_logits: bad size");
   if (n == 0) return MVML_OK;
+  MVML_REQUIRE(z && y && loss_terms && g_z, "bce_logits: NULL pointer");
   bce_logits_kernel<<<(unsigned)ceil_div(n, 256), 256, 0, as_stream(stream)>>>(n, z, y, loss_terms, g_z);
   return check_launch("bce_logits_kernel");
 }

@@ -231,6 +231,7 @@ extern "C" int mvml_graphnorm_fwd(int64_t G, int D, const int64_t* group_offsets
   clear_error();
   MVML_REQUIRE(G >= 0 && D > 0 && G < (int64_t(1) << 31), "graphnorm_fwd: bad shape");
   if (G == 0) return MVML_OK;
+  MVML_REQUIRE(group_offsets && x && weight && bias && mean_scale && y, "graphnorm_fwd: NULL pointer");
   hipStream_t st = as_stream(stream);
   dim3 grid((unsigned)G, (unsigned)ceil_div(D, 256));
   graphnorm_fwd_kernel<<<grid, 256, 0, st>>>(D, group_offsets, x, weight, bias, mean_scale, eps, y);
@@ -249,6 +250,8 @@ extern "C" int mvml_graphnorm_bwd(int64_t G, int D, const int64_t* group_offsets
   clear_error();
   MVML_REQUIRE(G >= 0 && D > 0 && G < (int64_t(1) << 31), "graphnorm_bwd: bad shape");
   if (G == 0) return MVML_OK;
+  MVML_REQUIRE(group_offsets && x && weight && mean_scale && g_y && g_x,
+               "graphnorm_bwd: NULL pointer (only g_weight, g_bias, g_mean_scale may be NULL)");
   if (!workspace || workspace_bytes < mvml_graphnorm_bwd_workspace_size(G, D)) {
     set_error("graphnorm_bwd: workspace too small");
     return MVML_ERR_WORKSPACE;
@@ -270,6 +273,7 @@ extern "C" int mvml_relu_bwd(int64_t n, const float* y, const float* g_y, float*
   clear_error();
   MVML_REQUIRE(n >= 0, "relu_bwd: bad size");
   if (n == 0) return MVML_OK;
+  MVML_REQUIRE(y && g_y && g_x, "relu_bwd: NULL pointer");
   hipStream_t st = as_stream(stream);
   const unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(n, 256), 16384);
   relu_bwd_kernel<<<blocks, 256, 0, st>>>(n, y, g_y, g_x, scale);

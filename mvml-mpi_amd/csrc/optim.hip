@@ -89,6 +89,7 @@ extern "C" int mvml_grad_gather(int64_t nchunks, const int32_t* chunk_param, con
   MVML_REQUIRE(nchunks >= 0 && nchunks < (int64_t(1) << 31) && P >= 0 && numel >= 0 && flat,
                "grad_gather: bad arguments");
   if (nchunks == 0) return MVML_OK;
+  MVML_REQUIRE(chunk_param && chunk_beg && chunk_end && param_off && src, "grad_gather: NULL pointer");
   grad_gather_kernel<<<(unsigned)nchunks, kOptThreads, 0, as_stream(stream)>>>(
       chunk_param, chunk_beg, chunk_end, param_off, src, P, flat, numel);
   return check_launch("grad_gather_kernel");
@@ -105,6 +106,8 @@ extern "C" int mvml_adam_flat(int64_t nchunks, const int32_t* chunk_param, const
   MVML_REQUIRE(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0 && lr >= 0.0,
                "adam_flat: bad hyper-parameters");
   if (nchunks == 0 || P == 0) return MVML_OK;
+  MVML_REQUIRE(chunk_param && chunk_beg && chunk_end && param && grad && exp_avg && exp_avg_sq,
+               "adam_flat: NULL pointer");
   hipStream_t st = as_stream(stream);
   adam_flat_kernel<<<(unsigned)nchunks, kOptThreads, 0, st>>>(chunk_param, chunk_beg, chunk_end, flags, steps,
                                                               param, grad, exp_avg, exp_avg_sq, lr, beta1,

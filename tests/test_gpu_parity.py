@@ -430,8 +430,8 @@ def test_graphnorm_parity():
 def test_graphnorm_param_reduce_many_groups(G, D, big):
     """The parameter gradients' reduction over G group partials (16 stripes per column, a fixed
     tree) at group counts around its stripe / unroll boundaries and a column count that is not a
-    multiple of 16, against float64.  big: groups of 63-130 rows, on both sides of the kernels'
-    64-row register path (longer groups re-read their rows)."""
+    multiple of 16, against float64.  big: groups of 63-130 rows (the kernels walk a group's rows
+    in sequence per column, three passes each, whatever its length)."""
     from mvml_gat.nn import GraphNorm
     gen = torch.Generator().manual_seed(G + D)
     sizes = torch.randint(63, 131, (G,), generator=gen) if big else torch.randint(1, 6, (G,), generator=gen)
