@@ -1104,6 +1104,111 @@ int mvml_multilabel_metrics(int64_t B, int C, const float* z, int64_t ldz, const
                             int64_t ldy, double* sums, int64_t* class_counts, void* workspace,
                             size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * GIN with bond embeddings (dgllife 0.3.0 gnn/gin.py: GINLayer.forward's
+ * update_all(u_add_e, sum) over summed categorical bond embeddings, GIN.forward's summed atom
+ * embeddings; restated, parity with dgllife unpinned; csrc/gin_agg.hip).
+ *
+ * Tables: T (1 <= T <= 4) embedding tables of n_0 .. n_{T-1} rows are addressed as ONE
+ * concatenated table of R = sum n_t rows, table t starting at row off_t = n_0 + .. + n_{t-1}.
+ * Edge tables: R <= 256.  Node tables: n_t <= 128 each.
+ *
+ * mvml_gin_edge_codes: one int32 per in-CSR slot s, byte t = off_t + cat_t[in_eid[s]] for t < T
+ * (bytes >= T are 0), from the T category arrays cat_t [num_edges] in edge-id order (cat_t for
+ * t >= T is ignored, may be NULL).  One 4-byte load per edge then serves every table in every
+ * layer.  A category outside [0, n_t) (or an in_eid outside [0, num_edges)) adds 1 to status[0]
+ * (int32, ADDED TO with integer atomics; the caller zeroes it) and is clamped into its table, so a
+ * code never names a row outside its table.  Refused with MVML_ERR_INVALID before any launch,
+ * nothing written: T outside [1, 4], an n_t < 1, R > 256, (num_edges > 0) a NULL cat_t for t < T,
+ * in_eid, codes or status.  num_edges == 0: MVML_OK, nothing written.
+ *
+ * mvml_gin_agg_fwd (replaces update_all(u_add_e, sum)): over the in-CSR,
+ *   out[v, 0:D) = sum_s ( X[in_src[s], 0:D) + e_s ),   e_s = (..(E[row_0(s)] + E[row_1(s)]) + ..)
+ * row_t(s) = byte t of codes[s] (clamped to R - 1).  Arithmetic order, every add rounded once
+ * (fp32, never contracted): e_s in table order; then x + e_s; then onto the running sum, s
+ * ascending over [in_rowptr[v], in_rowptr[v+1]), started from 0.  A row's bits therefore depend on
+ * neither the kernel instance (MVML_OPT_GIN_SUBWAVE), the table path (MVML_OPT_GIN_LDS) nor the batch it sits in.  A row
+ * without in-edges gives 0.  E [R][lde] is the concatenated table.  D a positive multiple of 4,
+ * <= 1024; X, out and E 16-byte aligned, ldx, ldo, lde multiples of 4 and >= D; out must not alias
+ * X or E.  Columns [D, ld) of X and E are never read and of out never written.  out_amax /
+ * out_row_amax (may be NULL) as in mvml_gcn_agg.  Anything else (also T outside [1, 4], R outside
+ * [T, 256], a NULL in_rowptr, in_src or codes): MVML_ERR_INVALID before any launch, nothing
+ * written.  A gather: no float atomics, bitwise repeatable.
+ * Its input gradient dX[u] = sum over out-edges (u -> w) of g[w] is mvml_gcn_agg over
+ * (out_rowptr, out_dst) with NULL scales, bias and act 0.
+ *
+ * mvml_gin_edge_emb_grad: dE[r, 0:D) = sum_v cnt_r(v) * G[v, 0:D), cnt_r(v) the number of
+ * in-slots of v whose code names row r, dE DENSE [R][D].  Two deterministic stages:
+ * P = mvml_gin_partial_rows(num_nodes) partial tables (a function of num_nodes alone: ceil(N / 128)
+ * clamped to [1, 2048]), partial p over the atoms [p ceil(N / P), (p + 1) ceil(N / P)) in
+ * ascending order from 0, each step acc = fma((float)cnt_r(v), G[v], acc) (atoms with cnt 0 are
+ * skipped); then mvml_colsum_f32 over the [P][R * D] matrix.  workspace:
+ * mvml_gin_emb_grad_workspace_size(num_nodes, R, D) bytes (MVML_ERR_WORKSPACE below that).
+ * num_nodes == 0 writes zeros.  dE must not alias G; D, R, T, G's alignment as the forward.
+ *
+ * mvml_embed_sum_fwd (sum_t node_embeddings[t](idx_t)): out[n, 0:D) = (..(Tab[r_0(n)] + Tab[r_1(n)])
+ * + ..), r_t(n) = off_t + idx_t[n] with idx_t clamped into [0, n_t) and every index outside it
+ * counted into status[0] (ADDED TO; may be NULL: not counted).  Tab [R][ldt] concatenated, each
+ * n_t in [1, 128].  out must not alias Tab.
+ * mvml_embed_sum_bwd: dTab[r] = sum over the atoms n with r_t(n) == r for some t of G[n] (counted
+ * once per table that names r), dTab DENSE [R][D], by the two-stage scheme and workspace of
+ * mvml_gin_edge_emb_grad, so a row most atoms name (carbon) is summed by every atom range's wave,
+ * never by one.
+ *
+ * mvml_relu_f32: y[i] = x[i] > 0 ? x[i] : +0 for i < n (NaN gives 0), x == y allowed; x and y
+ * 16-byte aligned.  The ReLU after GINLayer's BatchNorm1d; its backward is mvml_relu_bwd.
+ * ------------------------------------------------------------------------------------- */
+#define MVML_OPT_GIN_LDS 14 /* MVML_GIN_LDS: 1 (default) mvml_gin_agg_fwd stages the edge tables in
+                               LDS once per workgroup where R * D * 4 <= 49152 bytes, 0 = every wave
+                               reads its table rows from L2; the two give the same bits */
+#define MVML_OPT_GIN_SUBWAVE 15 /* MVML_GIN_SUBWAVE: mvml_gin_agg_fwd at D <= 64 with four rows per
+                                   wave, 16 lanes each (1, default), or one row per wave as at every
+                                   other width (0); the two give the same bits */
+int mvml_gin_edge_codes(int64_t num_edges, int T, const int32_t* cat0, const int32_t* cat1,
+                        const int32_t* cat2, const int32_t* cat3, int n0, int n1, int n2, int n3,
+                        const int32_t* in_eid, int32_t* codes, int32_t* status, void* stream);
+int mvml_gin_agg_fwd(int64_t num_nodes, const int32_t* in_rowptr, const int32_t* in_src,
+                     const int32_t* codes, const float* X, int64_t ldx, int D, const float* E,
+                     int64_t lde, int R, int T, float* out, int64_t ldo, uint32_t* out_amax,
+                     uint32_t* out_row_amax, void* stream);
+int64_t mvml_gin_partial_rows(int64_t num_nodes);
+size_t mvml_gin_emb_grad_workspace_size(int64_t num_nodes, int R, int D);
+int mvml_gin_edge_emb_grad(int64_t num_nodes, const int32_t* in_rowptr, const int32_t* codes,
+                           const float* G, int64_t ldg, int D, int R, int T, float* dE,
+                           void* workspace, size_t workspace_bytes, void* stream);
+int mvml_embed_sum_fwd(int64_t num_nodes, int T, const int32_t* idx0, const int32_t* idx1,
+                       const int32_t* idx2, const int32_t* idx3, int n0, int n1, int n2, int n3,
+                       const float* tab, int64_t ldt, int D, float* out, int64_t ldo, int32_t* status,
+                       void* stream);
+int mvml_embed_sum_bwd(int64_t num_nodes, int T, const int32_t* idx0, const int32_t* idx1,
+                       const int32_t* idx2, const int32_t* idx3, int n0, int n1, int n2, int n3,
+                       const float* G, int64_t ldg, int D, float* dtab, void* workspace,
+                       size_t workspace_bytes, void* stream);
+int mvml_relu_f32(int64_t n, const float* x, float* y, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Per-molecule pooling (dgl 0.9.1 SumPooling / AvgPooling / MaxPooling, GINPredictor's readouts;
+ * restated, parity with dgl unpinned; csrc/segment_pool.hip).  One wavefront per molecule g over
+ * its atoms n in [node_offsets[g], node_offsets[g+1]) (int64[B+1], mvml_build_csr), ascending:
+ *   mode 0 sum:  out[g] = sum_n X[n], from 0, each add rounded once
+ *   mode 1 mean: that sum divided once by the atom count
+ *   mode 2 max:  out[g][c] = max_n X[n][c], argmax[g][c] = the LOWEST atom index attaining it (a
+ *                strict > walking the atoms in order: mvml_wsum_max_fwd's rule); int32 [B][lda]
+ * A molecule without atoms gives 0 (and argmax -1) and takes no gradient.  argmax is read and
+ * written in mode 2 only (may be NULL otherwise).  Backward, every gX row of a non-empty molecule
+ * written exactly once: gX[n] = G[g] (sum), G[g] / count (mean), [argmax[g][c] == n] G[g][c] (max).
+ * D a positive multiple of 4, <= 2048; X, out, G, gX, argmax 16-byte aligned with row pitches that
+ * are multiples of 4 and >= D; out must not alias X, gX must not alias G; N < 2^31.  Anything else:
+ * MVML_ERR_INVALID before any launch, nothing written.  B == 0 (backward: or N == 0): MVML_OK,
+ * nothing written.  No atomics: bitwise repeatable.
+ * ------------------------------------------------------------------------------------- */
+int mvml_segment_pool_fwd(int64_t B, int64_t N, int D, int mode, const int64_t* node_offsets,
+                          const float* X, int64_t ldx, float* out, int64_t ldo, int32_t* argmax,
+                          int64_t lda, void* stream);
+int mvml_segment_pool_bwd(int64_t B, int64_t N, int D, int mode, const int64_t* node_offsets,
+                          const float* G, int64_t ldg, const int32_t* argmax, int64_t lda, float* gX,
+                          int64_t ldgx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

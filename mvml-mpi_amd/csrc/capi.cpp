@@ -30,7 +30,7 @@ int check_launch(const char* what) {
 }
 
 // Kernel-path options (include/mvml_gat.h, MVML_OPT_*): environment defaults read once at load.
-constexpr int kOptCount = 14;
+constexpr int kOptCount = 16;
 static std::atomic<int> g_opt[kOptCount];
 static int env_int(const char* name, int dflt) {
   const char* e = getenv(name);
@@ -51,6 +51,8 @@ static const bool g_opt_init = [] {
   g_opt[MVML_OPT_SMALLK] = env_int("MVML_SMALLK", 1);
   g_opt[MVML_OPT_GCN_SUBWAVE] = env_int("MVML_GCN_SUBWAVE", 1);
   g_opt[MVML_OPT_SAGE_SUBWAVE] = env_int("MVML_SAGE_SUBWAVE", 1);
+  g_opt[MVML_OPT_GIN_LDS] = env_int("MVML_GIN_LDS", 1);
+  g_opt[MVML_OPT_GIN_SUBWAVE] = env_int("MVML_GIN_SUBWAVE", 1);
   return true;
 }();
 

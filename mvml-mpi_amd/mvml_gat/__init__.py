@@ -21,10 +21,11 @@ from .nn import GAT, GATConv, GATLayer, GATv2, GATv2Conv, GATv2Layer, GNNModule,
 from .nn import GATPredictor, GATv2Predictor, MLPPredictor
 from .nn import GCN, GCNLayer, GCNPredictor, GraphConv
 from .nn import GraphSAGE, GraphSAGEPredictor, SAGEConv
+from .nn import GIN, GINLayer, GINPredictor
 from .optim import FlatAdam
 from .mvp import MVP
 from .metrics import MultiLabelMeter, evaluate, evaluate_class_wise
 
-__all__ = ["MultiLabelMeter", "evaluate", "evaluate_class_wise","GNNModule", "MVFusion", "FPNModule", "RNNModule", "tokens_struct", "collate_smiles", "bce_with_logits", "GAT", "GATLayer", "GATConv", "GATv2", "GATv2Layer", "GATv2Conv", "Set2Set", "WeightAndSum", "WeightedSumAndMax", "GATPredictor", "GATv2Predictor", "MLPPredictor", "GraphConv", "GCNLayer", "GCN", "GCNPredictor", "SAGEConv", "GraphSAGE", "GraphSAGEPredictor", "GraphNorm", "BatchedMolGraph",
+__all__ = ["MultiLabelMeter", "evaluate", "evaluate_class_wise","GNNModule", "MVFusion", "FPNModule", "RNNModule", "tokens_struct", "collate_smiles", "bce_with_logits", "GAT", "GATLayer", "GATConv", "GATv2", "GATv2Layer", "GATv2Conv", "Set2Set", "WeightAndSum", "WeightedSumAndMax", "GATPredictor", "GATv2Predictor", "MLPPredictor", "GraphConv", "GCNLayer", "GCN", "GCNPredictor", "SAGEConv", "GraphSAGE", "GraphSAGEPredictor", "GINLayer", "GIN", "GINPredictor", "GraphNorm", "BatchedMolGraph",
            "MolGraph", "batch", "graph", "bigraph_from_bonds", "from_arrays", "lib", "MvmlError", "FlatAdam", "MVP"]
 __version__ = "0.1.0"

@@ -21,13 +21,14 @@ from .functional import fold_padded
 class MolGraph:
     """One molecule as a directed graph with local int32 ids (what mol_to_bigraph returns)."""
 
-    def __init__(self, num_nodes, src, dst, ndata=None):
+    def __init__(self, num_nodes, src, dst, ndata=None, edata=None):
         self._num_nodes = int(num_nodes)
         self.src = np.ascontiguousarray(src, dtype=np.int32)
         self.dst = np.ascontiguousarray(dst, dtype=np.int32)
         if self.src.shape != self.dst.shape:
             raise ValueError("src and dst must have the same length")
         self.ndata = dict(ndata or {})
+        self.edata = dict(edata or {})  # per-edge tensors in edge-id order (the bond categories of GIN)
 
     def num_nodes(self):
         return self._num_nodes
@@ -81,6 +82,14 @@ def pad_columns(v, device, mult=4):
     return out
 
 
+def _edge_data(v, device):
+    """An edge data tensor on the GPU: integer ones (the categorical bond features of GIN) as
+    int32, the index type of the kernels; anything else as it is."""
+    if not v.dtype.is_floating_point and v.dtype != torch.bool:
+        return v.to(device=device, dtype=torch.int32, non_blocking=True)
+    return v.to(device, non_blocking=True)
+
+
 class BatchedMolGraph:
     """A batch of molecule graphs (dgl.batch result) with device-built CSR indices.
 
@@ -89,10 +98,12 @@ class BatchedMolGraph:
     ``edge_offsets`` (int64[B+1]), ``node_graph`` (int32[N]), ``in_rowptr``/``in_src``/
     ``in_eid`` (in-CSR), ``out_rowptr``/``out_dst``/``out_inslot`` (out-CSR) and
     ``group_offsets`` (int64[G+1], GraphNorm groups in molecules) are device tensors.
+    ``edata`` holds per-edge tensors in edge-id order (the categorical bond features of GIN);
+    ``.to(cuda_device)`` moves them, integer ones as int32.
     """
 
     def __init__(self, batch_num_nodes, batch_num_edges, src_local, dst_local, ndata=None,
-                 group_size=None):
+                 group_size=None, edata=None):
         self._bnn = np.ascontiguousarray(batch_num_nodes, dtype=np.int64)
         self._bne = np.ascontiguousarray(batch_num_edges, dtype=np.int64)
         self.src_local = np.ascontiguousarray(src_local, dtype=np.int32)
@@ -102,6 +113,7 @@ class BatchedMolGraph:
         if int(self._bne.sum()) != self.src_local.shape[0] or self.src_local.shape != self.dst_local.shape:
             raise ValueError("edge lists do not match batch_num_edges")
         self.ndata = dict(ndata or {})
+        self.edata = dict(edata or {})  # per-edge tensors in (global) edge-id order
         self.device = torch.device("cpu")
         self.group_size = group_size
         self._dev = None
@@ -173,11 +185,13 @@ class BatchedMolGraph:
         if device.type != "cuda":
             self.device = device
             self.ndata = {k: v.to(device) for k, v in self.ndata.items()}
+            self.edata = {k: v.to(device) for k, v in self.edata.items()}
             return self
         with torch.cuda.device(device):
             self._build_device(device)
         self.device = device
         self.ndata = {k: pad_columns(v, device) for k, v in self.ndata.items()}
+        self.edata = {k: _edge_data(v, device) for k, v in self.edata.items()}
         return self
 
     def _build_device(self, device):
@@ -235,6 +249,7 @@ class BatchedMolGraph:
         B, N, E = self.batch_size, self.num_nodes(), self.num_edges()
         d.pop("gcn_scales", None)  # GraphConv's degree factors (functional.gcn_scales) go with the indices
         d.pop("sage_gcn_scale", None)  # ... and SAGEConv's 1 / (deg + 1) (functional.sage_gcn_scale)
+        d.pop("gin_codes", None)  # ... and GIN's per-slot bond codes, in in-CSR order (functional.gin_edge_codes)
         L = _lib.lib()
         wp, wn = _lib.ws_ptr_size(L.mvml_build_csr_workspace_size(B, N, E), self.device)
         P = _lib.ptr
@@ -254,8 +269,8 @@ class BatchedMolGraph:
 
 
 def batch(graphs, group_size=None):
-    """dgl.batch (dataset.py:54): concatenate graphs; node features under ndata['h'] are
-    concatenated too."""
+    """dgl.batch (dataset.py:54): concatenate graphs; the node data every graph has (ndata['h'])
+    are concatenated too, and so are the edge data (edata), in edge order."""
     graphs = list(graphs)
     bnn = np.array([g.num_nodes() for g in graphs], dtype=np.int64)
     bne = np.array([g.num_edges() for g in graphs], dtype=np.int64)
@@ -265,12 +280,18 @@ def batch(graphs, group_size=None):
     keys = set.intersection(*[set(g.ndata) for g in graphs]) if graphs else set()
     for k in keys:
         ndata[k] = torch.cat([torch.as_tensor(g.ndata[k]) for g in graphs], 0)
-    return BatchedMolGraph(bnn, bne, src, dst, ndata, group_size=group_size)
+    edata = {}
+    ekeys = set.intersection(*[set(g.edata) for g in graphs]) if graphs else set()
+    for k in ekeys:  # in edge order, as dgl.batch concatenates edata
+        edata[k] = torch.cat([torch.as_tensor(g.edata[k]) for g in graphs], 0)
+    return BatchedMolGraph(bnn, bne, src, dst, ndata, group_size=group_size, edata=edata)
 
 
 def from_arrays(batch_num_nodes, batch_num_edges, src_local, dst_local, node_feats=None,
-                group_size=None):
-    """Build a batch directly from concatenated local edge lists (the synthetic generators)."""
+                group_size=None, edata=None):
+    """Build a batch directly from concatenated local edge lists (the synthetic generators);
+    edata: per-edge tensors in the order of the edge lists."""
     ndata = {} if node_feats is None else {"h": torch.as_tensor(node_feats)}
+    edata = None if edata is None else {k: torch.as_tensor(v) for k, v in edata.items()}
     return BatchedMolGraph(batch_num_nodes, batch_num_edges, src_local, dst_local, ndata,
-                           group_size=group_size)
+                           group_size=group_size, edata=edata)

@@ -31,6 +31,20 @@ Known differences from the reference:
   so a different canonical order only changes floating-point summation order);
 * the rest of the agreement with RDKit is **unpinned** (RDKit cannot be run here); the restatement is
   pinned by hand-derived known answers in tests/test_featurize.py.
+
+Categorical features for GIN (dgllife 0.3.0 PretrainAtomFeaturizer / PretrainBondFeaturizer and
+``smiles_to_bigraph`` with them: ``pretrain_atom_features``, ``pretrain_bond_features``,
+``smiles_to_pretrain_bigraph``; parity with dgllife / RDKit is unpinned).  The parser keeps, beside
+what the 74 features need, the direction symbol of every bond (``Mol.bond_dir``), the ``@`` count of
+every bracket atom (``Mol.chiral``) and the order in which each atom's bonds were written
+(``Mol.written``); none of the three is read by the 74-d path.  Known differences there:
+* RDKit's stereo clean-up is not restated: a ``@`` / ``@@`` tag stays on an atom that is no
+  stereocentre (fewer than three neighbours, two identical substituents), and a ``/`` or ``\\``
+  stays on a bond that is not next to a double bond;
+* a chiral atom's hydrogen inside the bracket (``[C@H]``, ``[C@@H]``) is not given a place in the
+  written neighbour order, so RDKit's special cases for a chiral first atom with an implicit H
+  and for an implicit H between the preceding atom and the ring closures are not restated;
+  explicit ``[H]`` atoms that are removed drop out of the written order without a parity change.
 """
 import numpy as np
 
@@ -78,6 +92,10 @@ class Mol:
     def __init__(self):
         self.sym, self.arom, self.bracket, self.hcount, self.charge = [], [], [], [], []
         self.bonds = []          # (a, b, order) order in {1, 2, 3, AROM}
+        # for the categorical (GIN) features only; the 74-d path reads none of the three:
+        self.bond_dir = []       # per bond: '/', '\\' or None, as written from the earlier atom a
+        self.chiral = []         # per atom: 0, 1 ('@') or 2 ('@@')
+        self.written = []        # per atom: its bonds' indices in the order its neighbours were written
         self.implicit_h = []
         self.radicals = []
         self.hyb = []
@@ -109,7 +127,8 @@ class Mol:
 # ----------------------------------------------------------------------------------------------
 # parsing (OpenSMILES subset used by KEGG + common extras)
 # ----------------------------------------------------------------------------------------------
-def _parse_bracket(s, i):
+def _parse_bracket(s, i, chiral=None):
+    """chiral: a list that receives the atom's '@' count (0, 1 or 2)."""
     j = s.index(']', i)
     body = s[i + 1:j]
     k = 0
@@ -128,8 +147,11 @@ def _parse_bracket(s, i):
         sym, k = body[k], k + 1
     else:
         raise SmilesError(f"unknown element in [{body}]")
-    while k < len(body) and body[k] == '@':          # chirality (no effect on the features)
+    k0 = k
+    while k < len(body) and body[k] == '@':          # chirality (no effect on the 74 features)
         k += 1
+    if chiral is not None:
+        chiral.append(min(k - k0, 2))
     h = 0
     if k < len(body) and body[k] == 'H':
         k += 1
@@ -163,6 +185,10 @@ def parse_smiles(s):
     prev, branch, rings = None, [], {}
     bond_sym = None
     i = 0
+
+    def direction(sym):
+        return sym if sym in ('/', '\\') else None
+
     while i < len(s):
         c = s[i]
         if c == '(':
@@ -189,13 +215,18 @@ def parse_smiles(s):
             if num in rings:
                 a, bs = rings.pop(num)
                 sym = bond_sym or bs
+                k = len(m.bonds)
                 m.bonds.append((a, prev, _bond_order(sym, m.arom[a], m.arom[prev])))
+                m.bond_dir.append(direction(sym))
+                m.written[a][m.written[a].index(('ring', num))] = k  # the place of its opening digit
+                m.written[prev].append(k)
             else:
                 rings[num] = (prev, bond_sym)
+                m.written[prev].append(('ring', num))
             bond_sym = None
             continue
         if c == '[':
-            sym, arom, h, chg, i = _parse_bracket(s, i)
+            sym, arom, h, chg, i = _parse_bracket(s, i, m.chiral)
             bracket = True
         elif s[i:i + 2] in ('Cl', 'Br'):
             sym, arom, h, chg, bracket = s[i:i + 2], False, 0, 0, False
@@ -214,8 +245,15 @@ def parse_smiles(s):
         m.bracket.append(bracket)
         m.hcount.append(h)
         m.charge.append(chg)
+        if len(m.chiral) < len(m.sym):
+            m.chiral.append(0)
+        m.written.append([])
         if prev is not None:
+            k = len(m.bonds)
             m.bonds.append((prev, idx, _bond_order(bond_sym, m.arom[prev], arom)))
+            m.bond_dir.append(direction(bond_sym))
+            m.written[prev].append(k)
+            m.written[idx].append(k)
         prev, bond_sym = idx, None
     if rings or branch:
         raise SmilesError(f"unclosed ring or branch in {s}")
@@ -640,6 +678,11 @@ def _remove_hs(m):
     for name in ('sym', 'arom', 'bracket', 'hcount', 'charge'):
         setattr(out, name, [getattr(m, name)[i] for i in keep])
     out.bonds = [(remap[a], remap[b], o) for (a, b, o) in m.bonds if a in remap and b in remap]
+    kept = [k for k, (a, b, _) in enumerate(m.bonds) if a in remap and b in remap]
+    bmap = {o: n for n, o in enumerate(kept)}
+    out.bond_dir = [m.bond_dir[k] for k in kept]
+    out.chiral = [m.chiral[i] for i in keep]
+    out.written = [[bmap[k] for k in m.written[i] if k in bmap] for i in keep]
     out._build_adj()
     return out
 
@@ -742,6 +785,81 @@ def smiles_to_bigraph(smiles, add_self_loop=True, canonical_atom_order=True):
         feats = feats[new_order]
         bonds = inv[bonds].astype(np.int32).reshape(-1, 2)
     return bigraph_from_bonds(m.num_atoms, bonds, feats, add_self_loop=add_self_loop)
+
+
+# ----------------------------------------------------------------------------------------------
+# categorical features for GIN (dgllife 0.3.0 PretrainAtomFeaturizer / PretrainBondFeaturizer)
+# ----------------------------------------------------------------------------------------------
+CHI_UNSPECIFIED, CHI_CW, CHI_CCW, CHI_OTHER = range(4)   # dgllife's chirality_type order
+BOND_TYPES = {1: 0, 2: 1, 3: 2, AROM: 3}                 # SINGLE, DOUBLE, TRIPLE, AROMATIC
+SELF_LOOP_BOND_TYPE = 4
+BOND_DIRS = {None: 0, '/': 1, '\\': 2}                   # NONE, ENDUPRIGHT, ENDDOWNRIGHT
+PRETRAIN_NODE_TABLES = [120, 3]   # the gin_supervised_* models' embedding tables (119 elements + 1; 3 tags used)
+PRETRAIN_EDGE_TABLES = [6, 3]
+
+
+def _odd_permutation(seq):
+    """True if sorting seq takes an odd number of transpositions (its inversion count is odd)."""
+    return sum(1 for a in range(len(seq)) for b in range(a + 1, len(seq)) if seq[a] > seq[b]) % 2 == 1
+
+
+def pretrain_atom_features(m):
+    """dgllife PretrainAtomFeaturizer: {'atomic_number': Z - 1, 'chirality_type': 0 unspecified,
+    1 CW, 2 CCW, 3 other}, int64 [n] each.  SMILES '@' lists the neighbours anticlockwise (CCW)
+    and '@@' clockwise (CW) in WRITTEN order; RDKit's tag refers to the atom's bonds in creation
+    order (a ring-closure bond is created at its closing digit), so the tag is inverted once when
+    the permutation from the written order to the creation order is odd."""
+    n = m.num_atoms
+    z = np.array([m.z(i) - 1 for i in range(n)], dtype=np.int64)
+    chi = np.zeros(n, dtype=np.int64)
+    for i in range(n):
+        if m.chiral[i]:
+            ccw = m.chiral[i] == 1
+            if _odd_permutation(m.written[i]):
+                ccw = not ccw
+            chi[i] = CHI_CCW if ccw else CHI_CW
+    return {"atomic_number": z, "chirality_type": chi}
+
+
+def pretrain_bond_features(m, self_loop=True):
+    """dgllife PretrainBondFeaturizer in bigraph_from_bonds' edge order (both directions of bond
+    k at 2k and 2k + 1, then one self-loop per atom): {'bond_type': single / double / triple /
+    aromatic -> 0 .. 3, a self-loop 4; 'bond_direction_type': 0 none, 1 for '/', 2 for '\\' as
+    written from the earlier atom, the same on both directions of a bond, 0 on self-loops},
+    int64 each."""
+    nb, ns = len(m.bonds), (m.num_atoms if self_loop else 0)
+    bt = np.full(2 * nb + ns, SELF_LOOP_BOND_TYPE, dtype=np.int64)
+    bd = np.zeros(2 * nb + ns, dtype=np.int64)
+    for k, (_, _, order) in enumerate(m.bonds):
+        if order not in BOND_TYPES:
+            raise SmilesError(f"bond order {order} has no pretrain bond type")
+        bt[2 * k] = bt[2 * k + 1] = BOND_TYPES[order]
+        bd[2 * k] = bd[2 * k + 1] = BOND_DIRS[m.bond_dir[k]]
+    return {"bond_type": bt, "bond_direction_type": bd}
+
+
+def smiles_to_pretrain_bigraph(smiles, add_self_loop=True, canonical_atom_order=False):
+    """smiles_to_bigraph(s, add_self_loop, PretrainAtomFeaturizer(), PretrainBondFeaturizer(),
+    canonical_atom_order) of dgllife: a MolGraph with ndata 'atomic_number', 'chirality_type' and
+    edata 'bond_type', 'bond_direction_type' (int64 torch tensors), the categorical inputs of GIN.
+    canonical_atom_order renumbers the atoms as smiles_to_bigraph does; the bonds, and with them
+    the edge features, keep their order."""
+    import torch
+
+    from .batching import bigraph_from_bonds
+    m = mol_from_smiles(smiles)
+    nf, ef = pretrain_atom_features(m), pretrain_bond_features(m, self_loop=add_self_loop)
+    bonds = np.array([(a, b) for (a, b, _) in m.bonds], dtype=np.int32).reshape(-1, 2)
+    if canonical_atom_order and m.num_atoms:
+        new_order = np.asarray(canonical_ranks(m), dtype=np.int64)
+        inv = np.empty_like(new_order)
+        inv[new_order] = np.arange(len(new_order))
+        nf = {k: v[new_order] for k, v in nf.items()}
+        bonds = inv[bonds].astype(np.int32).reshape(-1, 2)
+    g = bigraph_from_bonds(m.num_atoms, bonds, add_self_loop=add_self_loop)
+    g.ndata = {k: torch.as_tensor(v) for k, v in nf.items()}
+    g.edata = {k: torch.as_tensor(v) for k, v in ef.items()}
+    return g
 
 
 class MolDataSet:

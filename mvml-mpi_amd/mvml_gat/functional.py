@@ -86,7 +86,9 @@ def copy2d(dst, src):
 # post-ReLU output to ["relu_out"], the fusion its Conv2d+ReLU output to ["conv_out"] and
 # WeightedSumAndMaxFunction its forward's argmax to ["readout_argmax"]; SAGEConvFunction appends its
 # post-ReLU output to ["sage_out"], fc_pool's to ["sage_pool"] and the neighbour maximum's owner
-# slots to ["sage_arg"].  None in normal use.
+# slots to ["sage_arg"]; GINLayerFunction appends its MLP's post-ReLU hidden rows to ["gin_hidden"]
+# and a ReLU layer's output (before its Dropout) to ["gin_out"], SegmentPoolFunction the max
+# readout's argmax to ["pool_argmax"].  None in normal use.
 DEBUG_CAPTURE = None
 
 
@@ -1883,3 +1885,385 @@ class SAGEConvFunction(torch.autograd.Function):
                     gX = gcn_agg(gA, Fin, Fin, g, (None, s), transpose=True)
                     sage_self_add(gA, s, gX)
         return gX, gWp, gbp, gWs, gWn, gb, None, None, None
+
+
+# ---- GIN with bond embeddings (dgllife 0.3.0 gnn/gin.py; csrc/gin_agg.hip, csrc/segment_pool.hip) ----
+GIN_MAX_TABLES = 4       # embedding tables per side (mvml_gin_edge_codes, mvml_embed_sum_fwd)
+GIN_MAX_EDGE_ROWS = 256  # rows over all edge tables: one byte per table in a slot's code
+EMBED_MAX_ROWS = 128     # rows of one node table
+POOL_MODES = {"sum": 0, "mean": 1, "max": 2}
+
+
+def gin_agg_fwd_bytes(N, E, D, R):
+    """Algorithmic HBM bytes of one mvml_gin_agg_fwd: read X and write out once, the row pointers,
+    the neighbour ids, one code per slot and the R table rows (re-gathers of rows not counted)."""
+    return 4 * (2 * N * D + N + 1 + 2 * E + R * D)
+
+
+def gin_edge_emb_grad_bytes(N, E, D, R):
+    """Algorithmic bytes of one mvml_gin_edge_emb_grad: read G once, the row pointers and the codes;
+    write and re-read the mvml_gin_partial_rows(N) partial tables, write dE."""
+    P = _lib.lib().mvml_gin_partial_rows(N)
+    return 4 * (N * D + N + 1 + E + 2 * P * R * D + R * D)
+
+
+def embed_sum_fwd_bytes(N, T, D, R):
+    """Algorithmic bytes of one mvml_embed_sum_fwd: T indices per atom, the R table rows, out."""
+    return 4 * (N * T + R * D + N * D)
+
+
+def embed_sum_bwd_bytes(N, T, D, R):
+    """Algorithmic bytes of one mvml_embed_sum_bwd: G once, T indices per atom, the partial tables
+    written and re-read, dTab."""
+    P = _lib.lib().mvml_gin_partial_rows(N)
+    return 4 * (N * D + N * T + 2 * P * R * D + R * D)
+
+
+def segment_pool_bytes(B, N, D, mode):
+    """Algorithmic bytes of one mvml_segment_pool_fwd or _bwd: the [N, D] rows once, the [B, D]
+    rows once (twice with max's argmax), the offsets."""
+    return 4 * (N * D + (2 if POOL_MODES[mode] == 2 else 1) * B * D) + 8 * (B + 1)
+
+
+def _index_tensors(cats, n, dev, what):
+    """The T category tensors of one side as int32 device vectors of length n."""
+    cats = list(cats)
+    if not 1 <= len(cats) <= GIN_MAX_TABLES:
+        raise ValueError(f"{what}: 1 to {GIN_MAX_TABLES} categorical feature tensors, got {len(cats)}")
+    out = []
+    for c in cats:
+        if not c.is_cuda:
+            raise RuntimeError(f"{what} must be CUDA (HIP) tensors: the mvml_gat path has no CPU fallback")
+        if c.dim() != 1 or c.shape[0] != n or c.dtype.is_floating_point:
+            raise ValueError(f"{what}: integer vectors of length {n} expected, got {tuple(c.shape)} {c.dtype}")
+        out.append(_c(c if c.dtype == torch.int32 else c.to(torch.int32)))
+    return out
+
+
+def _table_args(cats, sizes):
+    """(T, four pointers, four sizes) of an entry point that takes up to four tables."""
+    T = len(sizes)
+    ps = [ptr(c) for c in cats] + [None] * (GIN_MAX_TABLES - T)
+    ns = [int(s) for s in sizes] + [0] * (GIN_MAX_TABLES - T)
+    return (T, *ps, *ns)
+
+
+def concat_tables(tables):
+    """The embedding tables [n_t, D] as one [R, D] tensor (mvml_copy_cols per table), and R."""
+    D = tables[0].shape[1]
+    R = sum(t.shape[0] for t in tables)
+    tab = torch.empty((R, D), dtype=torch.float32, device=tables[0].device)
+    o = 0
+    for t in tables:
+        copy2d(tab[o:o + t.shape[0]], _c(t))
+        o += t.shape[0]
+    return tab, R
+
+
+def _split_rows(dtab, tables):
+    """The per-table row blocks of a dense [R, D] gradient (contiguous views)."""
+    out, o = [], 0
+    for t in tables:
+        out.append(dtab[o:o + t.shape[0]])
+        o += t.shape[0]
+    return out
+
+
+def gin_edge_codes(g, edge_feats, sizes):
+    """One int32 per in-CSR slot of the device batch g holding, in byte t, the row of the slot's
+    edge in the concatenated edge tables (mvml_gin_edge_codes).  Computed once per (batch, feature
+    tensors, table sizes) and kept on the batch as gcn_scales' factors are;
+    BatchedMolGraph.recollate() drops it.  Categories outside their table raise IndexError, as
+    nn.Embedding would (one host read per batch, when the codes are first made)."""
+    sizes = tuple(int(s) for s in sizes)
+    E = g.num_edges()
+    feats = list(edge_feats)
+    if len(feats) != len(sizes):
+        raise ValueError(f"{len(sizes)} edge tables but {len(feats)} categorical edge feature tensors")
+    # keyed by the tensors given (not by their int32 copies, which are made on a miss only)
+    key = (sizes, tuple(c.data_ptr() for c in feats), tuple(c._version for c in feats))
+    cache = g._dev.setdefault("gin_codes", {})
+    if key not in cache:
+        cats = _index_tensors(feats, E, g.device, "categorical_edge_feats")
+        codes = torch.empty(max(E, 1), dtype=torch.int32, device=g.device)
+        status = zeros(1, dtype=torch.int32, device=g.device)
+        call("mvml_gin_edge_codes", E, *_table_args(cats, sizes), ptr(g.in_eid), ptr(codes), ptr(status),
+             _stream(g.device))
+        bad = int(status.item())
+        if bad:
+            raise IndexError(f"{bad} categorical edge features lie outside their embedding tables {sizes}")
+        cache[key] = (codes, feats)  # (the given tensors are kept: their addresses are the key)
+    return cache[key][0]
+
+
+def gin_agg(X, D, g, codes, tab, R, T, rows=False):
+    """mvml_gin_agg_fwd of the dense [N, D] rows of X over g's in-CSR with the concatenated edge
+    tables tab [R, D]: a new dense [N, D] tensor, its per-row maxima recorded on it when `rows`."""
+    N, E = g.num_nodes(), g.num_edges()
+    dev = X.device
+    out = torch.empty((N, D), dtype=torch.float32, device=dev)
+    rmx = torch.empty(max(N, 1), dtype=torch.int32, device=dev) if rows else None
+    _lib.call_tag[0] = {"layer": f"D{D}", "bytes": gin_agg_fwd_bytes(N, E, D, R)}
+    call("mvml_gin_agg_fwd", N, ptr(g.in_rowptr), ptr(g.in_src), ptr(codes), ptr(X), X.stride(0), D, ptr(tab), D,
+         R, T, ptr(out), D, None, ptr(rmx), _stream(dev))
+    if rows:
+        fold_rows(out, rmx)
+    return out
+
+
+def _emb_grad_ws(N, R, D, dev):
+    return _lib.ws_ptr_size(_lib.lib().mvml_gin_emb_grad_workspace_size(N, R, D), dev)
+
+
+def gin_edge_emb_grad(G, D, g, codes, R, T):
+    """mvml_gin_edge_emb_grad: the dense [R, D] gradient of the concatenated edge tables from G,
+    the gradient at gin_agg's output."""
+    N, E = g.num_nodes(), g.num_edges()
+    dE = torch.empty((R, D), dtype=torch.float32, device=G.device)
+    wp, wn = _emb_grad_ws(N, R, D, G.device)
+    _lib.call_tag[0] = {"layer": f"D{D}", "bytes": gin_edge_emb_grad_bytes(N, E, D, R)}
+    call("mvml_gin_edge_emb_grad", N, ptr(g.in_rowptr), ptr(codes), ptr(G), G.stride(0), D, R, T, ptr(dE), wp, wn,
+         _stream(G.device))
+    return dE
+
+
+class _StageCtx:
+    """A stand-in ctx for running another Function's forward / backward as a stage of a fused one."""
+
+    def __init__(self, needs=(True,) * 9):
+        self.needs_input_grad = needs
+        self.saved_tensors = ()
+
+    def save_for_backward(self, *ts):
+        self.saved_tensors = ts
+
+
+class GINLayerFunction(torch.autograd.Function):
+    """dgllife 0.3.0 GINLayer.forward (restated; parity with dgllife is unpinned) as ONE autograd
+    node: the slot codes of the bond categories (gin_edge_codes, cached on the batch) -> the fused
+    sum over in-edges of (node_feats[u] + e_uv) with e_uv the sum of the edge's embedding rows
+    (mvml_gin_agg_fwd) -> mlp = Linear(D, 2D) + ReLU -> Linear(2D, D) on the fp32-accurate GEMM ->
+    BatchNorm1d (bn: the parameter container, or None) -> ReLU (act; mvml_relu_f32 in place) and
+    the Dropout(p) that follows a ReLU layer (in place, relu_dropout_).  Backward: mvml_relu_bwd,
+    the BatchNorm backward, the two Linears' backwards, then from the gradient at the sum's output
+    both the edge tables' gradient (mvml_gin_edge_emb_grad) and the input's (mvml_gcn_agg over the
+    out-CSR).  Returns gradients for X, both Linears, BatchNorm and every edge table."""
+
+    @staticmethod
+    def forward(ctx, X, w1, b1, w2, b2, bn_w, bn_b, g, edge_feats, bn, act, p, *tables):
+        _check_cuda_f32(X, "node_feats")
+        for t in (w1, b1, w2, b2, *tables):
+            _check_cuda_f32(t, "GINLayer parameters")
+        X = _rows_f32(X)
+        N, D = X.shape
+        sizes = [t.shape[0] for t in tables]
+        codes = gin_edge_codes(g, edge_feats, sizes)
+        tab, R = concat_tables(tables)
+        T = len(tables)
+        rows = GEMM_ALGO == "f16x2" and ROW_SCALES
+        A = gin_agg(X, D, g, codes, tab, R, T, rows=rows)
+        _, w1, h1, lm1 = linear_forward(A, w1, b1, act=1)
+        if DEBUG_CAPTURE is not None:  # the ReLU sides the product took (parity tests)
+            DEBUG_CAPTURE.setdefault("gin_hidden", []).append(h1.detach().clone())
+        _, w2, out, lm2 = linear_forward(h1, w2, b2)
+        bctx = None
+        if bn is not None:
+            if bn.momentum is None:
+                raise ValueError("BatchNorm1d: momentum=None (cumulative average) is not implemented on the HIP path")
+            training = bn.training or bn.running_mean is None
+            bctx = _StageCtx((True, bn_w is not None, bn_b is not None))
+            out = BatchNorm1dFunction.forward(bctx, out, bn_w, bn_b, bn.running_mean, bn.running_var,
+                                              bn.num_batches_tracked if training else None, training, bn.momentum,
+                                              bn.eps)
+        ctx.scale = 1.0
+        if act:
+            call("mvml_relu_f32", out.numel(), ptr(out), ptr(out), _stream(out.device))
+            if DEBUG_CAPTURE is not None:
+                DEBUG_CAPTURE.setdefault("gin_out", []).append(out.detach().clone())
+            ctx.scale = relu_dropout_(out, p)
+        ctx.save_for_backward(A, w1, h1, w2, out if act else None)
+        ctx.state = (g, codes, R, T, lm1, lm2, bctx, tables)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        A, w1, h1, w2, out = ctx.saved_tensors
+        g, codes, R, T, lm1, lm2, bctx, tables = ctx.state
+        N, D = A.shape
+        dev = A.device
+        gy = _c(g_out)
+        if out is not None:
+            g_pre = torch.empty_like(gy)
+            call("mvml_relu_bwd", gy.numel(), ptr(out), ptr(gy), ptr(g_pre), float(ctx.scale), _stream(dev))
+            gy = g_pre
+        g_bnw = g_bnb = None
+        if bctx is not None:
+            gy, g_bnw, g_bnb = BatchNorm1dFunction.backward(bctx, gy)[:3]
+        gh1, gw2, gb2 = linear_backward(h1, w2, gy, lm2)
+        g_hid = torch.empty_like(gh1)
+        call("mvml_relu_bwd", gh1.numel(), ptr(h1), ptr(gh1), ptr(g_hid), 1.0, _stream(dev))
+        gA, gw1, gb1 = linear_backward(A, w1, g_hid, lm1)
+        dE = gin_edge_emb_grad(gA, D, g, codes, R, T)
+        gX = gcn_agg(gA, D, D, g, (None, None), transpose=True) if ctx.needs_input_grad[0] else None
+        return (gX, gw1, gb1, gw2, gb2, g_bnw, g_bnb, None, None, None, None, None, *_split_rows(dE, tables))
+
+
+_EMBED_STATUS = {}
+
+
+def embed_status(dev):
+    """The int32 device counter of atom categories that lay outside their embedding table (clamped
+    into it by mvml_embed_sum_fwd) since the process started; read it with .item() when wanted —
+    the forward never synchronises for it."""
+    t = _EMBED_STATUS.get(str(dev))
+    if t is None:
+        t = _EMBED_STATUS[str(dev)] = zeros(1, dtype=torch.int32, device=dev)
+    return t
+
+
+class EmbedSumFunction(torch.autograd.Function):
+    """sum_t node_embeddings[t](idx_t) of dgllife's GIN.forward: one pass over the atoms
+    (mvml_embed_sum_fwd), the tables' gradient by the two-stage sum of mvml_embed_sum_bwd.
+    node_feats: the T integer vectors [N]; tables: the T weights [n_t, D]."""
+
+    @staticmethod
+    def forward(ctx, node_feats, *tables):
+        for t in tables:
+            _check_cuda_f32(t, "node_embeddings")
+        dev = tables[0].device
+        N = node_feats[0].shape[0]
+        idx = _index_tensors(node_feats, N, dev, "categorical_node_feats")
+        if len(idx) != len(tables):
+            raise ValueError(f"{len(tables)} node tables but {len(idx)} categorical node feature tensors")
+        tab, R = concat_tables(tables)
+        D = tab.shape[1]
+        out = torch.empty((N, D), dtype=torch.float32, device=dev)
+        sizes = [t.shape[0] for t in tables]
+        _lib.call_tag[0] = {"layer": f"D{D}", "bytes": embed_sum_fwd_bytes(N, len(idx), D, R)}
+        call("mvml_embed_sum_fwd", N, *_table_args(idx, sizes), ptr(tab), D, D, ptr(out), D, ptr(embed_status(dev)),
+             _stream(dev))
+        ctx.state = (idx, sizes, R, D, tables)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        idx, sizes, R, D, tables = ctx.state
+        G = _rows_f32(g_out)
+        N = G.shape[0]
+        dev = G.device
+        dtab = torch.empty((R, D), dtype=torch.float32, device=dev)
+        wp, wn = _emb_grad_ws(N, R, D, dev)
+        _lib.call_tag[0] = {"layer": f"D{D}", "bytes": embed_sum_bwd_bytes(N, len(idx), D, R)}
+        call("mvml_embed_sum_bwd", N, *_table_args(idx, sizes), ptr(G), G.stride(0), D, ptr(dtab), wp, wn,
+             _stream(dev))
+        return (None, *_split_rows(dtab, tables))
+
+
+class SegmentPoolFunction(torch.autograd.Function):
+    """dgl's SumPooling / AvgPooling / MaxPooling over the molecules of the device batch g
+    (mvml_segment_pool_fwd / _bwd): mode "sum", "mean" or "max"; returns (B, D)."""
+
+    @staticmethod
+    def forward(ctx, X, g, mode):
+        _check_cuda_f32(X, "feats")
+        if mode not in POOL_MODES:
+            raise ValueError(f"readout must be one of {sorted(POOL_MODES)}, got {mode!r}")
+        X = _rows_f32(X)
+        N, D = X.shape
+        B = g.batch_size
+        dev = X.device
+        out = torch.empty((B, D), dtype=torch.float32, device=dev)
+        argmax = torch.empty((B, D), dtype=torch.int32, device=dev) if mode == "max" else None
+        _lib.call_tag[0] = {"layer": f"D{D}", "bytes": segment_pool_bytes(B, N, D, mode)}
+        call("mvml_segment_pool_fwd", B, N, D, POOL_MODES[mode], ptr(g.node_offsets), ptr(X), X.stride(0), ptr(out), D,
+             ptr(argmax), D, _stream(dev))
+        if DEBUG_CAPTURE is not None and argmax is not None:  # the atoms the product took at ties
+            DEBUG_CAPTURE.setdefault("pool_argmax", []).append(argmax.detach().clone())
+        ctx.save_for_backward(argmax)
+        ctx.state = (g, mode, N, D)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        (argmax,) = ctx.saved_tensors
+        g, mode, N, D = ctx.state
+        G = _rows_f32(g_out)
+        B = g.batch_size
+        # (rows of atoms outside every molecule cannot exist: node_offsets covers [0, N))
+        gX = torch.empty((N, D), dtype=torch.float32, device=G.device)
+        _lib.call_tag[0] = {"layer": f"D{D}", "bytes": segment_pool_bytes(B, N, D, mode)}
+        call("mvml_segment_pool_bwd", B, N, D, POOL_MODES[mode], ptr(g.node_offsets), ptr(G), G.stride(0), ptr(argmax),
+             D, ptr(gX), D, _stream(G.device))
+        return gX, None, None
+
+
+class ForkFunction(torch.autograd.Function):
+    """x for two consumers (GIN's jumping knowledge: h_l feeds layer l + 1 and the JK): the two
+    gradients that meet at x are added by mvml_add_cols_f32 here, not by the autograd engine."""
+
+    @staticmethod
+    def forward(ctx, x):
+        return x.view_as(x), x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, ga, gb):
+        if ga is None or gb is None:  # one consumer took no gradient
+            return gb if ga is None else ga
+        ga, gb = _rows_f32(ga), _rows_f32(gb)
+        s = copy2d(torch.empty(ga.shape, dtype=torch.float32, device=ga.device), ga)
+        M, D = s.shape
+        if M:
+            call("mvml_add_cols_f32", M, D, ptr(gb), gb.stride(0), ptr(s), D, _stream(s.device))
+        return s
+
+
+class JKConcatFunction(torch.autograd.Function):
+    """torch.cat([h_0, ..., h_L], dim=1) by mvml_copy_cols into column blocks; the backward copies
+    each block out again."""
+
+    @staticmethod
+    def forward(ctx, *hs):
+        N = hs[0].shape[0]
+        ctx.widths = [h.shape[1] for h in hs]
+        out = torch.empty((N, sum(ctx.widths)), dtype=torch.float32, device=hs[0].device)
+        o = 0
+        for h in hs:
+            _check_cuda_f32(h, "h")
+            if N:
+                copy2d(out[:, o:o + h.shape[1]], _rows_f32(h))
+            o += h.shape[1]
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        g = _rows_f32(g)
+        N = g.shape[0]
+        out, o = [], 0
+        for w in ctx.widths:
+            t = torch.empty((N, w), dtype=torch.float32, device=g.device)
+            out.append(copy2d(t, g[:, o:o + w]) if N else t)
+            o += w
+        return tuple(out)
+
+
+class JKSumFunction(torch.autograd.Function):
+    """h_0 + ... + h_L, added in that order by mvml_add_cols_f32 onto a copy of h_0; every input's
+    gradient is the output's."""
+
+    @staticmethod
+    def forward(ctx, *hs):
+        for h in hs:
+            _check_cuda_f32(h, "h")
+        ctx.n = len(hs)
+        h0 = _rows_f32(hs[0])
+        out = copy2d(torch.empty(h0.shape, dtype=torch.float32, device=h0.device), h0)
+        M, D = out.shape
+        for h in hs[1:]:
+            h = _rows_f32(h)
+            if M:
+                call("mvml_add_cols_f32", M, D, ptr(h), h.stride(0), ptr(out), D, _stream(out.device))
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        return (g,) * ctx.n

@@ -11,7 +11,9 @@ Drop-in replacements, on the MI355X HIP path, for
   * dgl 0.9.1 ``GraphConv`` and dgllife 0.3.0 ``GCNLayer`` / ``GCN`` / ``GCNPredictor`` (the GCN
     baseline; not in model.py),
   * dgl 0.9.1 ``SAGEConv`` and dgllife 0.3.0 ``GraphSAGE`` / ``GraphSAGEPredictor`` (the GraphSAGE
-    baseline; not in model.py).
+    baseline; not in model.py),
+  * dgllife 0.3.0 ``GINLayer`` / ``GIN`` / ``GINPredictor`` (the bond-aware gin_supervised_* family
+    over categorical atom and bond features; not in model.py).
 Parameter names/shapes/registration order follow the reference so a ``net_i.pkl``
 ``model_state_dict`` (keys under ``gnn.``) loads unchanged.
 """
@@ -896,3 +898,175 @@ class GraphSAGEPredictor(nn.Module):
     def forward(self, bg, feats):
         node_feats = self.gnn(bg, feats)
         return self.predict(self.readout(bg, node_feats))
+
+
+def _check_emb_dim(who, emb_dim):
+    # the range of mvml_gin_agg_fwd / mvml_embed_sum_fwd (csrc/gin_agg.hip): refuse here, not in forward
+    if not isinstance(emb_dim, int) or emb_dim <= 0 or emb_dim % 4 or emb_dim > 1024:
+        raise ValueError(f"{who}: emb_dim must be a positive multiple of 4 <= 1024 on the HIP path (got {emb_dim})")
+
+
+def _check_tables(who, what, sizes, max_total=None, max_each=None):
+    sizes = [int(n) for n in sizes]
+    if not 1 <= len(sizes) <= Fn.GIN_MAX_TABLES:
+        raise ValueError(f"{who}: 1 to {Fn.GIN_MAX_TABLES} {what} embedding tables on the HIP path (got {len(sizes)})")
+    if min(sizes) < 1:
+        raise ValueError(f"{who}: every {what} embedding table needs at least one row (got {sizes})")
+    if max_total is not None and sum(sizes) > max_total:
+        raise ValueError(f"{who}: at most {max_total} rows over the {what} embedding tables (got {sum(sizes)})")
+    if max_each is not None and max(sizes) > max_each:
+        raise ValueError(f"{who}: at most {max_each} rows per {what} embedding table (got {sizes})")
+    return sizes
+
+
+class GINLayer(nn.Module):
+    """dgllife.model.gnn.gin.GINLayer (0.3.0; restated, parity with dgllife is unpinned).  Members
+    in dgllife's order: mlp = Sequential(Linear(D, 2D), ReLU(), Linear(2D, D)), edge_embeddings =
+    ModuleList(Embedding(n, D) for n in num_edge_emb_list) (xavier-uniform), bn = BatchNorm1d(D) when
+    batch_norm.  forward(g, node_feats, categorical_edge_feats): e = sum_t edge_embeddings[t](cat_t)
+    per edge, h[v] = sum over in-edges (u -> v) of (node_feats[u] + e_uv), then mlp, bn and
+    activation.  The torch modules are parameter containers; the arithmetic is one autograd node on
+    the HIP kernels (Fn.GINLayerFunction: csrc/gin_agg.hip, the fp32-accurate GEMM,
+    csrc/batchnorm.hip).  activation: None or ReLU (F.relu, torch.relu, nn.ReLU()).  Refused at
+    construction: emb_dim no positive multiple of 4 or above 1024, more than 4 edge tables, more
+    than 256 rows over them."""
+
+    def __init__(self, num_edge_emb_list, emb_dim, batch_norm=True, activation=None):
+        super().__init__()
+        _check_emb_dim("GINLayer", emb_dim)
+        sizes = _check_tables("GINLayer", "edge", num_edge_emb_list, max_total=Fn.GIN_MAX_EDGE_ROWS)
+        if activation is not None and not _is_relu(activation):
+            raise ValueError("GINLayer: activation must be None or ReLU (F.relu, torch.relu, nn.ReLU()) on the HIP path")
+        self.mlp = nn.Sequential(nn.Linear(emb_dim, 2 * emb_dim), nn.ReLU(), nn.Linear(2 * emb_dim, emb_dim))
+        self.edge_embeddings = nn.ModuleList()
+        for num_emb in sizes:
+            emb_module = nn.Embedding(num_emb, emb_dim)
+            nn.init.xavier_uniform_(emb_module.weight.data)
+            self.edge_embeddings.append(emb_module)
+        if batch_norm:
+            self.bn = nn.BatchNorm1d(emb_dim)
+        else:
+            self.bn = None
+        self.activation = activation
+        self._allow_zero_in_degree = True  # (a row without in-edges sums to 0, as in DGL)
+
+    def reset_parameters(self):
+        for layer in self.mlp:
+            if isinstance(layer, nn.Linear):
+                layer.reset_parameters()
+        for emb_module in self.edge_embeddings:
+            nn.init.xavier_uniform_(emb_module.weight.data)
+        if self.bn is not None:
+            self.bn.reset_parameters()
+
+    _check_graph = GATConv._check_graph
+
+    def fused(self, g, node_feats, categorical_edge_feats, p=0.0):
+        """forward with the Dropout(p) that follows a ReLU layer applied in place on its output."""
+        self._check_graph(g)
+        bn = self.bn
+        return Fn.GINLayerFunction.apply(
+            node_feats, self.mlp[0].weight, self.mlp[0].bias, self.mlp[2].weight, self.mlp[2].bias,
+            None if bn is None else bn.weight, None if bn is None else bn.bias, g, list(categorical_edge_feats), bn,
+            int(self.activation is not None), float(p) if self.activation is not None else 0.0,
+            *[e.weight for e in self.edge_embeddings])
+
+    def forward(self, g, node_feats, categorical_edge_feats):
+        return self.fused(g, node_feats, categorical_edge_feats)
+
+
+class GIN(nn.Module):
+    """dgllife.model.gnn.gin.GIN (0.3.0; restated, parity with dgllife is unpinned):
+    node_embeddings = ModuleList(Embedding(n, D)) (xavier-uniform), gnn_layers = num_layers GINLayers
+    with F.relu on all but the last.  forward(g, categorical_node_feats, categorical_edge_feats):
+    h_0 = sum_t node_embeddings[t](idx_t) (Fn.EmbedSumFunction), h_{l+1} = dropout(layer_l(g, h_l,
+    edge_feats)), then the jumping knowledge over [h_0, ..., h_L]: 'last', 'concat' (dim 1) or
+    'sum'; 'max' is not implemented.  The Dropout after a ReLU layer runs in place inside the
+    layer's node, the last layer's through Fn.dropout.  With 'concat' / 'sum' every h_l has two
+    consumers; Fn.ForkFunction adds their two gradients with a HIP kernel, so the autograd engine
+    adds nothing.  Refused at construction beside GINLayer's rules: num_layers < 2, dropout outside
+    [0, 1), more than 4 node tables or more than 128 rows in one, a concat width above 2048."""
+
+    def __init__(self, num_node_emb_list, num_edge_emb_list, num_layers=5, emb_dim=300, JK="last", dropout=0.5):
+        super().__init__()
+        if num_layers < 2:
+            raise ValueError(f"Number of GNN layers must be greater than 1, got {num_layers}")
+        _check_emb_dim("GIN", emb_dim)
+        node_sizes = _check_tables("GIN", "node", num_node_emb_list, max_each=Fn.EMBED_MAX_ROWS)
+        _check_tables("GIN", "edge", num_edge_emb_list, max_total=Fn.GIN_MAX_EDGE_ROWS)
+        if not 0.0 <= dropout < 1.0:
+            raise ValueError("GIN: dropout probability must be in [0, 1) on the HIP path")
+        if JK == "max":
+            raise NotImplementedError("GIN: JK='max' is not on the HIP path")
+        if JK not in ("last", "concat", "sum"):
+            raise ValueError(f"Expect argument JK to be one of 'concat', 'last', 'max' or 'sum', got {JK}")
+        if JK == "concat" and (num_layers + 1) * emb_dim > 2048:
+            raise ValueError(f"GIN: JK='concat' width (num_layers + 1) * emb_dim must be <= 2048 on the HIP path "
+                             f"(got {(num_layers + 1) * emb_dim})")
+        self.num_layers = num_layers
+        self.JK = JK
+        self.dropout = nn.Dropout(dropout)
+        self.node_embeddings = nn.ModuleList()
+        for num_emb in node_sizes:
+            emb_module = nn.Embedding(num_emb, emb_dim)
+            nn.init.xavier_uniform_(emb_module.weight.data)
+            self.node_embeddings.append(emb_module)
+        self.gnn_layers = nn.ModuleList()
+        for layer in range(num_layers):
+            if layer == num_layers - 1:
+                self.gnn_layers.append(GINLayer(num_edge_emb_list, emb_dim))
+            else:
+                self.gnn_layers.append(GINLayer(num_edge_emb_list, emb_dim, activation=F.relu))
+
+    def reset_parameters(self):
+        for emb_module in self.node_embeddings:
+            nn.init.xavier_uniform_(emb_module.weight.data)
+        for layer in self.gnn_layers:
+            layer.reset_parameters()
+
+    def forward(self, g, categorical_node_feats, categorical_edge_feats):
+        self.gnn_layers[0]._check_graph(g)
+        p = Fn.dropout_p(self.dropout)
+        fork = self.JK != "last"
+        h = Fn.EmbedSumFunction.apply(list(categorical_node_feats), *[e.weight for e in self.node_embeddings])
+        taps = []
+        for layer in self.gnn_layers:
+            if fork:
+                h, tap = Fn.ForkFunction.apply(h)
+                taps.append(tap)
+            h = layer.fused(g, h, categorical_edge_feats, p)
+            if layer.activation is None:
+                h = Fn.dropout(h, p)
+        if self.JK == "last":
+            return h
+        taps.append(h)
+        return (Fn.JKConcatFunction if self.JK == "concat" else Fn.JKSumFunction).apply(*taps)
+
+
+class GINPredictor(nn.Module):
+    """dgllife.model.model_zoo.gin_predictor.GINPredictor (0.3.0; restated, parity with dgllife is
+    unpinned): gnn = GIN(...) -> readout 'sum' / 'mean' / 'max' (dgl's Sum / Avg / MaxPooling per
+    molecule, Fn.SegmentPoolFunction) -> predict = Linear((num_layers + 1) * D if JK == 'concat' else
+    D, n_tasks).  The 'attention' and 'set2set' readouts are not implemented (dgllife's own
+    'set2set' branch cannot be constructed).  forward(g, categorical_node_feats,
+    categorical_edge_feats) returns (B, n_tasks)."""
+
+    def __init__(self, num_node_emb_list, num_edge_emb_list, num_layers=5, emb_dim=300, JK="last", dropout=0.5,
+                 readout="mean", n_tasks=1):
+        super().__init__()
+        if num_layers < 2:
+            raise ValueError(f"Number of GNN layers must be greater than 1, got {num_layers}")
+        if readout in ("attention", "set2set"):
+            raise NotImplementedError(f"GINPredictor: readout={readout!r} is not on the HIP path")
+        if readout not in Fn.POOL_MODES:
+            raise ValueError(f"Expect readout to be 'sum', 'mean', 'max', 'attention' or 'set2set', got {readout}")
+        self.gnn = GIN(num_node_emb_list=num_node_emb_list, num_edge_emb_list=num_edge_emb_list,
+                       num_layers=num_layers, emb_dim=emb_dim, JK=JK, dropout=dropout)
+        self.readout = readout
+        self.predict = nn.Linear((num_layers + 1) * emb_dim if JK == "concat" else emb_dim, n_tasks)
+
+    def forward(self, g, categorical_node_feats, categorical_edge_feats):
+        node_feats = self.gnn(g, categorical_node_feats, categorical_edge_feats)
+        graph_feats = Fn.SegmentPoolFunction.apply(node_feats, g, self.readout)
+        from .fusion import LinearFunction
+        return LinearFunction.apply(graph_feats, self.predict.weight, self.predict.bias)
