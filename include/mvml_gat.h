@@ -1209,6 +1209,95 @@ int mvml_segment_pool_bwd(int64_t B, int64_t N, int D, int mode, const int64_t* 
                           const float* G, int64_t ldg, const int32_t* argmax, int64_t lda, float* gX,
                           int64_t ldgx, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * AttentiveFP (dgllife 0.3.0 gnn/attentivefp.py, readout/attentivefp_readout.py; restated, parity
+ * with dgllife unpinned): the three pieces the other models' kernels cannot serve.  All fp32.
+ * leaky = LeakyReLU(0.01).  csrc/afp_agg.hip, csrc/gru.hip, csrc/attn_pool.hip; DESIGN.md
+ * "AttentiveFP".
+ *
+ * mvml_afp_edge_rows: rows[s, 0:Dp) = [ e[in_eid[s], 0:De) | 0 ... ], Dp = De rounded up to 4: the
+ * bond rows in in-CSR slot order, once per batch.  1 <= De <= 32; rows 16-byte aligned.
+ *
+ * mvml_afp_context_fwd (GetContext's edge part, nothing [E, G] in memory): per edge s = (u -> v),
+ *   he_s = leaky(P[u] + b1 + sum_k e_s[k] W1eT[k])          (k ascending, one fma each)
+ *   l_s  = leaky(t[v] + w2e . he_s),   a = softmax of l over v's in-slots
+ *   s_out[v] = sum_s a_s he_s            (slot order, online softmax; 0 without in-edges)
+ * W1eT is [De][G] dense (the bond columns of project_edge1's weight, transposed), b1 and w2e [G],
+ * t [N], bond_rows from mvml_afp_edge_rows ([E][Dp]), attn_out [E] in slot order.  One wave per
+ * atom (G <= 64: four atoms per wave); W1eT staged in LDS where De * G * 4 <= 49152 bytes, read
+ * from L2 otherwise (the same bits).  G a positive multiple of 4 <= 1024, 1 <= De <= 32, P and
+ * s_out 16-byte aligned with pitches that are multiples of 4 and >= G; anything else:
+ * MVML_ERR_INVALID before any launch, nothing written.  in_src, bond_rows and attn_out are touched
+ * per in-edge only and may be NULL for a batch without edges (the backward: num_edges == 0).
+ *
+ * mvml_afp_context_bwd: from g_s = dL/d s_out (and the forward's s_out, attn): gP [N][ldgp] (every
+ * row written), g_t [N], g_w2e [G] and g_w1e_b1 [(De + 1)][G] = [dL/dW1eT | dL/db1].  No float
+ * atomics; bitwise repeatable.  Stage 1 by destination atom (softmax backward d l_e = a_e (c_e -
+ * cbar), c_e = g_s . (he_e - s[v]) recentred by cbar = sum a c / sum a of the stored weights; d_pre per slot,
+ * g_t, partial g_w2e per atom range), stage 2 by source atom over the out-CSR (gP, partial
+ * g_W1eT / g_b1 per atom range), mvml_afp_partial_rows(N) ranges each, reduced by mvml_colsum_f32.
+ * Bond features get no gradient.  workspace: mvml_afp_context_bwd_workspace_size bytes.
+ *
+ * mvml_afp_bias_elu: X[v] = elu(X[v] + (in_rowptr == NULL || deg_in(v) > 0 ? bias : 0)) in place
+ * (bias may be NULL).  _bwd: gX[v] = G[v] * elu'(out[v]) (from the output: out > 0 ? 1 : out + 1),
+ * zero for a masked atom.  mvml_leaky_f32 / mvml_leaky_bwd_f32: y = leaky(x, slope) on pitched
+ * rows, and gx = g * (y > 0 ? 1 : slope).  cols multiples of 4, 16-byte aligned rows.
+ *
+ * mvml_gru_cell_fwd (torch GRUCell after the two gate products gi = x Wih^T, gh = h Whh^T, both
+ * [M][3D] dense, gate order r, z, n):  r = sig(gi_r + bih_r + gh_r + bhh_r), z likewise,
+ * n = tanh(gi_n + bih_n + r (gh_n + bhh_n)), h' = (1 - z) n + z h, out = relu ? max(h', 0) : h'.
+ * save [M][4D] = [r | z | n | gh_n + bhh_n].  _bwd: g_gi, g_gh [M][3D] and g_h [M][D] = z g (the
+ * direct term) from g_out (and out, for the ReLU).  D a positive multiple of 4 <= 1024, any M.
+ *
+ * mvml_attn_pool_fwd (AttentiveFPReadout's softmax-weighted sum): per graph b over its atoms,
+ *   z_v = leaky(w_node . X[v] + u[b], slope), a = softmax of z, r_out[b] = sum_v a_v X[v]
+ * one wave per graph, each atom row read once, online softmax in atom order; attn_out [N].
+ * _bwd: gX[v] (+)= a_v g_r[b] + dz_v w_node (accumulate != 0 adds), g_u [B], g_wn [D] through
+ * mvml_attn_pool_partial_rows(B) partial rows and mvml_colsum_f32.  D a positive multiple of 4 <=
+ * 1024.  No atomics.
+ * ------------------------------------------------------------------------------------- */
+int mvml_afp_edge_rows(int64_t num_edges, int De, const int32_t* in_eid, const float* e, int64_t lde,
+                       float* rows, void* stream);
+int mvml_afp_context_fwd(int64_t num_nodes, const int32_t* in_rowptr, const int32_t* in_src,
+                         const float* P, int64_t ldp, int G, const float* bond_rows, int De,
+                         const float* W1eT, const float* b1, const float* w2e, const float* t,
+                         float* s_out, int64_t lds, float* attn_out, void* stream);
+int64_t mvml_afp_partial_rows(int64_t num_nodes);
+size_t mvml_afp_context_bwd_workspace_size(int64_t num_nodes, int64_t num_edges, int G, int De);
+int mvml_afp_context_bwd(int64_t num_nodes, int64_t num_edges, const int32_t* in_rowptr,
+                         const int32_t* in_src, const int32_t* out_rowptr, const int32_t* out_dst,
+                         const int32_t* out_inslot, const float* P, int64_t ldp, int G,
+                         const float* bond_rows, int De, const float* W1eT, const float* b1,
+                         const float* w2e, const float* t, const float* s_out, int64_t lds,
+                         const float* attn, const float* g_s, int64_t ldgs, float* gP, int64_t ldgp,
+                         float* g_t, float* g_w2e, float* g_w1e_b1, void* workspace,
+                         size_t workspace_bytes, void* stream);
+int mvml_afp_bias_elu(int64_t num_nodes, int G, const int32_t* in_rowptr, float* X, int64_t ldx,
+                      const float* bias, void* stream);
+int mvml_afp_bias_elu_bwd(int64_t num_nodes, int G, const int32_t* in_rowptr, const float* out,
+                          int64_t ldo, const float* g, int64_t ldg, float* gX, int64_t ldgx,
+                          void* stream);
+int mvml_leaky_f32(int64_t rows, int cols, const float* x, int64_t ldx, float* y, int64_t ldy,
+                   float slope, void* stream);
+int mvml_leaky_bwd_f32(int64_t rows, int cols, const float* y, int64_t ldy, const float* g,
+                       int64_t ldg, float* gx, int64_t ldgx, float slope, void* stream);
+int mvml_gru_cell_fwd(int64_t M, int D, const float* gi, const float* gh, const float* b_ih,
+                      const float* b_hh, const float* h, int64_t ldh, int relu, float* out,
+                      int64_t ldo, float* save, void* stream);
+int mvml_gru_cell_bwd(int64_t M, int D, const float* save, const float* h, int64_t ldh,
+                      const float* out, int64_t ldo, const float* g_out, int64_t ldg, int relu,
+                      float* g_gi, float* g_gh, float* g_h, int64_t ldgh, void* stream);
+int mvml_attn_pool_fwd(int64_t B, int64_t N, int D, const int64_t* node_offsets, const float* X,
+                       int64_t ldx, const float* w_node, const float* u, float slope, float* r_out,
+                       int64_t ldr, float* attn_out, void* stream);
+int64_t mvml_attn_pool_partial_rows(int64_t B);
+size_t mvml_attn_pool_bwd_workspace_size(int64_t B, int64_t N, int D);
+int mvml_attn_pool_bwd(int64_t B, int64_t N, int D, const int64_t* node_offsets, const float* X,
+                       int64_t ldx, const float* w_node, const float* u, float slope,
+                       const float* r_out, int64_t ldr, const float* attn, const float* g_r,
+                       int64_t ldgr, int accumulate, float* gX, int64_t ldgx, float* g_u,
+                       float* g_wn, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -250,6 +250,7 @@ class BatchedMolGraph:
         d.pop("gcn_scales", None)  # GraphConv's degree factors (functional.gcn_scales) go with the indices
         d.pop("sage_gcn_scale", None)  # ... and SAGEConv's 1 / (deg + 1) (functional.sage_gcn_scale)
         d.pop("gin_codes", None)  # ... and GIN's per-slot bond codes, in in-CSR order (functional.gin_edge_codes)
+        d.pop("afp_rows", None)  # ... and AttentiveFP's bond rows in in-CSR order (functional.afp_edge_rows)
         L = _lib.lib()
         wp, wn = _lib.ws_ptr_size(L.mvml_build_csr_workspace_size(B, N, E), self.device)
         P = _lib.ptr

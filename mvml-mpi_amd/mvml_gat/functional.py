@@ -2267,3 +2267,342 @@ class JKSumFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         return (g,) * ctx.n
+
+
+# ---- AttentiveFP (csrc/afp_agg.hip, csrc/gru.hip, csrc/attn_pool.hip; DESIGN.md "AttentiveFP") ----
+AFP_SLOPE = 0.01         # torch's LeakyReLU default, AttentiveFP's everywhere
+AFP_MAX_EDGE_FEATS = 32  # bond features per edge (mvml_afp_context_fwd)
+AFP_MAX_WIDTH = 1024     # graph_feat_size
+
+
+def afp_context_fwd_bytes(N, E, G, De):
+    """Algorithmic HBM bytes of one mvml_afp_context_fwd: P read and s written once, the row
+    pointers, the neighbour ids, the padded bond rows, t, the attention (re-gathers not counted)."""
+    return 4 * (2 * N * G + N + 1 + E + E * _round4(De) + N + E + (De + 2) * G)
+
+
+def afp_context_bwd_bytes(N, E, G, De):
+    """Algorithmic bytes of one mvml_afp_context_bwd: stage 1 reads P, s, g_s, the bond rows and
+    the attention, parks two scalars per slot, re-reads them and writes d_pre and g_t; stage 2 reads P, g_s, the bond rows, the attention and
+    d_pre and writes gP; both write and re-read their partial rows."""
+    Pn = _lib.lib().mvml_afp_partial_rows(N)
+    idx = 2 * (N + 1) + 3 * E
+    return 4 * (5 * N * G + N * G + 2 * E * _round4(De) + 8 * E + 2 * N + idx + 2 * Pn * (De + 2) * G)
+
+
+def gru_cell_bytes(M, D, backward):
+    """Algorithmic bytes of mvml_gru_cell_fwd (gi, gh, h in; out, save out) or _bwd."""
+    return 4 * M * D * ((3 + 3 + 1 + 1 + 4) if not backward else (4 + 1 + 1 + 1 + 3 + 3 + 1))
+
+
+def attn_pool_bytes(B, N, D, backward):
+    """Algorithmic bytes of mvml_attn_pool_fwd (X once, r, attn) or _bwd (X once, gX, r, g_r, attn)."""
+    return 4 * ((N * D + B * D + N + B) if not backward else (2 * N * D + 2 * B * D + N + 2 * B))
+
+
+def _off(t, floats):
+    """The device pointer `floats` elements past t's first."""
+    return ctypes.c_void_p(t.data_ptr() + 4 * floats)
+
+
+def _dense(view):
+    """A contiguous copy of a 2-D (or 1-D) float32 view with unit column stride (mvml_copy_cols)."""
+    return copy2d(torch.empty(view.shape, dtype=torch.float32, device=view.device), view)
+
+
+def afp_edge_rows(g, edge_feats):
+    """The [E, round_up(De, 4)] bond rows of the device batch g in in-CSR slot order, zero-padded
+    (mvml_afp_edge_rows).  Made once per (batch, feature tensor) and kept on the batch as GIN's
+    codes are; BatchedMolGraph.recollate() drops it."""
+    _check_cuda_f32(edge_feats, "edge_feats")
+    E = g.num_edges()
+    if edge_feats.dim() != 2 or edge_feats.shape[0] != E or not 1 <= edge_feats.shape[1] <= AFP_MAX_EDGE_FEATS:
+        raise ValueError(f"edge_feats: a float [E = {E}, 1..{AFP_MAX_EDGE_FEATS}] tensor in edge-id order expected, "
+                         f"got {tuple(edge_feats.shape)}")
+    key = (edge_feats.data_ptr(), edge_feats._version, tuple(edge_feats.shape), tuple(edge_feats.stride()))
+    cache = g._dev.setdefault("afp_rows", {})
+    if key not in cache:
+        e = _c(edge_feats)
+        De = e.shape[1]
+        rows = torch.empty((max(E, 1), _round4(De)), dtype=torch.float32, device=g.device)
+        call("mvml_afp_edge_rows", E, De, ptr(g.in_eid), ptr(e), De, ptr(rows), _stream(g.device))
+        cache[key] = (rows, edge_feats)  # (the given tensor is kept: its address is the key)
+    return cache[key][0]
+
+
+def _gru_forward(x, h, w_ih, w_hh, b_ih, b_hh, relu):
+    """relu?(GRUCell(x, h)): the two gate products on the GEMM, the gates in mvml_gru_cell_fwd.
+    Returns (out, state); state is what _gru_backward takes beside `out` (kept apart: where out is
+    an autograd node's output it goes through save_for_backward, not into the node's own state)."""
+    x, w_ih, gi, lmi = linear_forward(x, w_ih, None)
+    h, w_hh, gh, lmh = linear_forward(h, w_hh, None)
+    M, D = h.shape
+    dev = h.device
+    out = torch.empty((M, D), dtype=torch.float32, device=dev)
+    save = torch.empty((M, 4 * D), dtype=torch.float32, device=dev)
+    _lib.call_tag[0] = {"layer": f"D{D}", "bytes": gru_cell_bytes(M, D, False)}
+    call("mvml_gru_cell_fwd", M, D, ptr(gi), ptr(gh), ptr(_c(b_ih)), ptr(_c(b_hh)), ptr(h), D, int(relu), ptr(out), D,
+         ptr(save), _stream(dev))
+    return out, (x, h, w_ih, w_hh, lmi, lmh, save, int(relu))
+
+
+def _gru_backward(state, out, g_out, need_gx=True):
+    """(g_x, g_h, g_w_ih, g_w_hh, g_b_ih, g_b_hh) of _gru_forward; g_h holds the direct z g term
+    plus the hidden product's share (accumulated by that product, beta = 1).  out: the forward's
+    output, read for the ReLU's sides only (None without a ReLU)."""
+    x, h, w_ih, w_hh, lmi, lmh, save, relu = state
+    M, D = h.shape
+    dev = h.device
+    g_out = _rows_f32(g_out)
+    g_gi = torch.empty((M, 3 * D), dtype=torch.float32, device=dev)
+    g_gh = torch.empty((M, 3 * D), dtype=torch.float32, device=dev)
+    g_h = torch.empty((M, D), dtype=torch.float32, device=dev)
+    _lib.call_tag[0] = {"layer": f"D{D}", "bytes": gru_cell_bytes(M, D, True)}
+    call("mvml_gru_cell_bwd", M, D, ptr(save), ptr(h), D, ptr(out), D, ptr(g_out), g_out.stride(0), relu, ptr(g_gi),
+         ptr(g_gh), ptr(g_h), D, _stream(dev))
+    g_x, g_wih, g_bih = linear_backward(x, w_ih, g_gi, lmi, need_gx=need_gx)
+    g_h, g_whh, g_bhh = linear_backward(h, w_hh, g_gh, lmh, gx_acc=g_h)
+    return g_x, g_h, g_wih, g_whh, g_bih, g_bhh
+
+
+def _elu_(x, g=None, bias=None):
+    """x = elu(x + bias) in place; g: the batch whose atoms without in-edges take no bias."""
+    M, D = x.shape
+    call("mvml_afp_bias_elu", M, D, ptr(g.in_rowptr) if g is not None else None, ptr(x), D,
+         None if bias is None else ptr(_c(bias)), _stream(x.device))
+    return x
+
+
+def _elu_backward(out, g_out, g=None):
+    """The gradient before _elu_ (zero rows for the atoms it masked)."""
+    M, D = out.shape
+    g_out = _rows_f32(g_out)
+    gx = torch.empty((M, D), dtype=torch.float32, device=out.device)
+    call("mvml_afp_bias_elu_bwd", M, D, ptr(g.in_rowptr) if g is not None else None, ptr(out), D, ptr(g_out),
+         g_out.stride(0), ptr(gx), D, _stream(out.device))
+    return gx
+
+
+class AFPContextFunction(torch.autograd.Function):
+    """dgllife 0.3.0 GetContext.forward (restated; parity with dgllife is unpinned) as ONE autograd
+    node.  One GEMM over the atom features gives [x Wn^T + bn | P = x W1n^T]; hv_new = leaky of the
+    first half; t = w2n . hv_new + b2 per atom; mvml_afp_context_fwd runs the bond-aware edge
+    softmax and its weighted sum s without any [E, G] tensor; c = elu(We s + be [deg > 0]) is a
+    node-level GEMM and mvml_afp_bias_elu; h = relu(GRUCell(c, hv_new)).  The Fn + De and 2G wide
+    weights are split by columns here, per call.  Bond features get no gradient."""
+
+    @staticmethod
+    def forward(ctx, X, edge_feats, g, Wn, bn, W1, b1, W2, b2, We, be, w_ih, w_hh, b_ih, b_hh):
+        _check_cuda_f32(X, "node_feats")
+        for p in (Wn, bn, W1, b1, W2, b2, We, be, w_ih, w_hh, b_ih, b_hh):
+            _check_cuda_f32(p, "GetContext parameters")
+        X, Xp = _padded_input(X)
+        N, Fn = X.shape
+        Fp = Xp.shape[1]
+        G = Wn.shape[0]
+        De = W1.shape[1] - Fn
+        dev = X.device
+        st = _stream(dev)
+        E = g.num_edges()
+        rows = afp_edge_rows(g, edge_feats)
+        if edge_feats.shape[1] != De:
+            raise ValueError(f"GetContext: {De} bond features expected, got {edge_feats.shape[1]}")
+        Wcat = zeros((2 * G, Fp), device=dev)
+        copy2d(Wcat[:G, :Fn], Wn)
+        copy2d(Wcat[G:, :Fn], W1[:, :Fn])
+        bcat = zeros(2 * G, device=dev)
+        copy2d(bcat[:G], bn)
+        _, _, Y, lmY = linear_forward(Xp, Wcat, bcat)
+        hv = torch.empty((N, G), dtype=torch.float32, device=dev)
+        call("mvml_leaky_f32", N, G, ptr(Y), 2 * G, ptr(hv), G, AFP_SLOPE, st)
+        W2 = _c(W2)
+        w2n = W2[:, :G]
+        _, w2n, t, lmt = linear_forward(hv, w2n, b2)
+        W1eT = torch.empty((De, G), dtype=torch.float32, device=dev)
+        W1 = _c(W1)
+        call("mvml_transpose", G, De, _off(W1, Fn), Fn + De, ptr(W1eT), G, st)
+        b1 = _c(b1)
+        s = torch.empty((N, G), dtype=torch.float32, device=dev)
+        attn = torch.empty(max(E, 1), dtype=torch.float32, device=dev)
+        _lib.call_tag[0] = {"layer": f"G{G}xDe{De}", "bytes": afp_context_fwd_bytes(N, E, G, De)}
+        call("mvml_afp_context_fwd", N, ptr(g.in_rowptr), ptr(g.in_src), _off(Y, G), 2 * G, G, ptr(rows), De, ptr(W1eT),
+             ptr(b1), _off(W2, G), ptr(t), ptr(s), G, ptr(attn), st)
+        _, We, c, lmc = linear_forward(s, We, None)
+        _elu_(c, g, be)
+        h, gst = _gru_forward(c, hv, w_ih, w_hh, b_ih, b_hh, True)
+        ctx.state = (g, rows, Xp, Wcat, lmY, Y, hv, w2n, lmt, t, W1eT, b1, W2, s, attn, We, lmc, c, gst, Fn, De)
+        ctx.save_for_backward(h)
+        return h
+
+    @staticmethod
+    def backward(ctx, g_out):
+        g, rows, Xp, Wcat, lmY, Y, hv, w2n, lmt, t, W1eT, b1, W2, s, attn, We, lmc, c, gst, Fn, De = ctx.state
+        N, G = hv.shape
+        E = g.num_edges()
+        dev = hv.device
+        st = _stream(dev)
+        g_c, g_hv, g_wih, g_whh, g_bih, g_bhh = _gru_backward(gst, ctx.saved_tensors[0], g_out)
+        g_cpre = _elu_backward(c, g_c, g)
+        g_s, g_We, _ = linear_backward(s, We, g_cpre, lmc, need_gb=False)
+        g_be = torch.empty(G, dtype=torch.float32, device=dev)
+        colsum(g_cpre, N, G, G, g_be)  # (the masked atoms' rows are zero)
+        gY = torch.empty((N, 2 * G), dtype=torch.float32, device=dev)
+        g_t = torch.empty((N, 1), dtype=torch.float32, device=dev)
+        g_W2 = torch.empty((1, 2 * G), dtype=torch.float32, device=dev)
+        g_w1b = torch.empty((De + 1, G), dtype=torch.float32, device=dev)
+        wp, wn = _lib.ws_ptr_size(_lib.lib().mvml_afp_context_bwd_workspace_size(N, E, G, De), dev)
+        _lib.call_tag[0] = {"layer": f"G{G}xDe{De}", "bytes": afp_context_bwd_bytes(N, E, G, De)}
+        call("mvml_afp_context_bwd", N, E, ptr(g.in_rowptr), ptr(g.in_src), ptr(g.out_rowptr), ptr(g.out_dst),
+             ptr(g.out_inslot), _off(Y, G), 2 * G, G, ptr(rows), De, ptr(W1eT), ptr(b1), _off(W2, G), ptr(t), ptr(s), G,
+             ptr(attn), ptr(g_s), G, _off(gY, G), 2 * G, ptr(g_t), _off(g_W2, G), ptr(g_w1b), wp, wn, st)
+        g_hv, g_w2n, g_b2 = linear_backward(hv, w2n, g_t, lmt, gx_acc=g_hv)
+        copy2d(g_W2[:, :G], g_w2n)
+        call("mvml_leaky_bwd_f32", N, G, ptr(hv), G, ptr(g_hv), G, ptr(gY), 2 * G, AFP_SLOPE, st)
+        gXp, gWcat, gbcat = linear_backward(Xp, Wcat, gY, lmY, need_gx=ctx.needs_input_grad[0])
+        g_W1 = torch.empty((G, Fn + De), dtype=torch.float32, device=dev)
+        copy2d(g_W1[:, :Fn], gWcat[G:, :Fn])
+        call("mvml_transpose", De, G, ptr(g_w1b), G, _off(g_W1, Fn), Fn + De, st)
+        gX = _dense(gXp[:, :Fn]) if gXp is not None else None
+        return (gX, None, None, _dense(gWcat[:G, :Fn]), _dense(gbcat[:G]), g_W1, _dense(g_w1b[De]), g_W2, g_b2, g_We,
+                g_be, g_wih, g_whh, g_bih, g_bhh)
+
+
+class AFPGNNLayerFunction(torch.autograd.Function):
+    """dgllife 0.3.0 GNNLayer.forward (restated) as ONE autograd node: logits leaky(w_d . h_v +
+    w_s . h_u + b) are a one-head GAT's el / er pair, so one GEMM gives [Z = h Wp^T + bp | el | er]
+    and the existing mvml_gat_agg_fwd_res (H = 1, flatten + ELU, no residual, no bias, slope 0.01)
+    gives elu(sum_e a_e Z[u]); then h' = relu(GRUCell(that, h)) and BatchNorm1d (bn: the parameter
+    container) on the project's kernel."""
+
+    @staticmethod
+    def forward(ctx, h, g, w_edge, b_edge, Wp, bp, w_ih, w_hh, b_ih, b_hh, bn_w, bn_b, bn):
+        _check_cuda_f32(h, "node_feats")
+        h = _c(h)
+        N, G = h.shape
+        dev = h.device
+        st = _stream(dev)
+        E = g.num_edges()
+        C = G + 4  # [Z | el | er | 2 pad]
+        Wz = zeros((C, G), device=dev)
+        copy2d(Wz[:G], _c(Wp))
+        w_edge = _c(w_edge)
+        copy2d(Wz[G:G + 1], w_edge[:, G:])      # el: the source term
+        copy2d(Wz[G + 1:G + 2], w_edge[:, :G])  # er: the destination term (+ the bias)
+        bz = zeros(C, device=dev)
+        copy2d(bz[:G], bp)
+        copy2d(bz[G + 1:G + 2], b_edge)
+        _, _, Y, lmY = linear_forward(h, Wz, bz)
+        elr = torch.empty((N, 2), dtype=torch.float32, device=dev)
+        call("mvml_copy_cols", N, 2, _off(Y, G), C, ptr(elr), 2, st)
+        c = torch.empty((N, G), dtype=torch.float32, device=dev)
+        attn = torch.empty((max(E, 1), 1), dtype=torch.float32, device=dev)
+        _lib.call_tag[0] = {"layer": f"H1xF{G}", "bytes": agg_fwd_bytes(N, E, 1, G, G, 0)}
+        call("mvml_gat_agg_fwd_res", N, ptr(g.node_groups), g.num_node_groups, ptr(g.in_rowptr), ptr(g.in_src), ptr(Y),
+             C, 1, G, ptr(elr), None, 0, None, AFP_SLOPE, MODE_FLATTEN_ELU, ptr(c), ptr(attn), None, None, st)
+        out, gst = _gru_forward(c, h, w_ih, w_hh, b_ih, b_hh, True)
+        bctx = _StageCtx((True, True, True))
+        training = bn.training or bn.running_mean is None
+        if bn.momentum is None:
+            raise ValueError("BatchNorm1d: momentum=None (cumulative average) is not implemented on the HIP path")
+        y = BatchNorm1dFunction.forward(bctx, out, bn_w, bn_b, bn.running_mean, bn.running_var,
+                                        bn.num_batches_tracked if training else None, training, bn.momentum, bn.eps)
+        ctx.state = (g, h, Wz, lmY, Y, elr, c, attn, gst, out, bctx)
+        return y
+
+    @staticmethod
+    def backward(ctx, g_y):
+        g, h, Wz, lmY, Y, elr, c, attn, gst, out, bctx = ctx.state
+        N, G = h.shape
+        C = G + 4
+        dev = h.device
+        st = _stream(dev)
+        g_out, g_bnw, g_bnb = BatchNorm1dFunction.backward(bctx, _c(g_y))[:3]
+        g_c, g_h, g_wih, g_whh, g_bih, g_bhh = _gru_backward(gst, out, g_out)
+        gY = zeros((N, C), device=dev)  # (the two pad columns stay 0)
+        # (a batch without bonds still passes a workspace: the entry wants a pointer)
+        wp, wn = _lib.ws_ptr_size(_lib.lib().mvml_gat_agg_bwd_workspace_size(max(g.num_edges(), 1), 1), dev)
+        _lib.call_tag[0] = {"layer": f"H1xF{G}", "bytes": agg_bwd_bytes(N, g.num_edges(), 1, G, G, 0)}
+        call("mvml_gat_agg_bwd_res", N, ptr(g.node_groups), g.num_node_groups, ptr(g.in_rowptr), ptr(g.in_src),
+             ptr(g.out_rowptr), ptr(g.out_dst), ptr(g.out_inslot), ptr(Y), C, ptr(elr), ptr(attn), ptr(c), ptr(g_c), 1, G,
+             AFP_SLOPE, MODE_FLATTEN_ELU, ptr(gY), C, G, None, 0, None, None, wp, wn, st)
+        g_h, gWz, gbz = linear_backward(h, Wz, gY, lmY, gx_acc=g_h)
+        g_wedge = torch.empty((1, 2 * G), dtype=torch.float32, device=dev)
+        copy2d(g_wedge[:, G:], gWz[G:G + 1])
+        copy2d(g_wedge[:, :G], gWz[G + 1:G + 2])
+        return (g_h, None, g_wedge, _dense(gbz[G + 1:G + 2]), _dense(gWz[:G]), _dense(gbz[:G]), g_wih, g_whh, g_bih,
+                g_bhh, g_bnw, g_bnb, None)
+
+
+class AFPReadoutFunction(torch.autograd.Function):
+    """dgllife 0.3.0 AttentiveFPReadout.forward (restated) as ONE autograd node: gf = the per-graph
+    sum of the atom rows (mvml_segment_pool_fwd), then per timestep u = wg . relu(gf) + bz (a GEMM),
+    the softmax-weighted sum r of the atom rows (mvml_attn_pool_fwd), elu(Wp r + bp) at GRAPH level
+    (every graph has an atom and the weights sum to 1) and gf = GRUCell(that, gf).  params: per
+    timestep (compute_logits weight [1, 2D] and bias, project_nodes weight and bias, the GRUCell's
+    four).  All timesteps' atom gradients and the initial sum's add into one gX."""
+
+    @staticmethod
+    def forward(ctx, X, g, T, *params):
+        _check_cuda_f32(X, "node_feats")
+        X = _rows_f32(X)
+        N, D = X.shape
+        B = g.batch_size
+        dev = X.device
+        st = _stream(dev)
+        gf = torch.empty((B, D), dtype=torch.float32, device=dev)
+        call("mvml_segment_pool_fwd", B, N, D, POOL_MODES["sum"], ptr(g.node_offsets), ptr(X), X.stride(0), ptr(gf), D,
+             None, D, st)
+        steps = []
+        for k in range(T):
+            wl, bl, Wp, bp, w_ih, w_hh, b_ih, b_hh = params[8 * k:8 * k + 8]
+            wl = _c(wl)
+            rg = torch.empty_like(gf)
+            call("mvml_relu_f32", gf.numel(), ptr(gf), ptr(rg), st)
+            _, wg, u, lmu = linear_forward(rg, wl[:, :D], bl)
+            r = torch.empty((B, D), dtype=torch.float32, device=dev)
+            attn = torch.empty(max(N, 1), dtype=torch.float32, device=dev)
+            _lib.call_tag[0] = {"layer": f"D{D}", "bytes": attn_pool_bytes(B, N, D, False)}
+            call("mvml_attn_pool_fwd", B, N, D, ptr(g.node_offsets), ptr(X), X.stride(0), _off(wl, D), ptr(u), AFP_SLOPE,
+                 ptr(r), D, ptr(attn), st)
+            _, Wp, c, lmc = linear_forward(r, Wp, bp)
+            _elu_(c)
+            gf, gst = _gru_forward(c, gf, w_ih, w_hh, b_ih, b_hh, False)
+            steps.append((wl, rg, wg, u, lmu, r, attn, Wp, c, lmc, gst))
+        ctx.state = (g, X, steps)
+        return gf
+
+    @staticmethod
+    def backward(ctx, g_gf):
+        g, X, steps = ctx.state
+        N, D = X.shape
+        B = g.batch_size
+        dev = X.device
+        st = _stream(dev)
+        gX = torch.empty((N, D), dtype=torch.float32, device=dev)
+        wp, wn = _lib.ws_ptr_size(_lib.lib().mvml_attn_pool_bwd_workspace_size(B, N, D), dev)
+        grads = []
+        for k in reversed(range(len(steps))):
+            wl, rg, wg, u, lmu, r, attn, Wp, c, lmc, gst = steps[k]
+            g_c, g_gf, g_wih, g_whh, g_bih, g_bhh = _gru_backward(gst, None, g_gf)
+            g_cpre = _elu_backward(c, g_c)
+            g_r, g_Wp, g_bp = linear_backward(r, Wp, g_cpre, lmc)
+            g_u = torch.empty((B, 1), dtype=torch.float32, device=dev)
+            g_wl = torch.empty((1, 2 * D), dtype=torch.float32, device=dev)
+            _lib.call_tag[0] = {"layer": f"D{D}", "bytes": attn_pool_bytes(B, N, D, True)}
+            call("mvml_attn_pool_bwd", B, N, D, ptr(g.node_offsets), ptr(X), X.stride(0), _off(wl, D), ptr(u), AFP_SLOPE,
+                 ptr(r), D, ptr(attn), ptr(g_r), D, int(k != len(steps) - 1), ptr(gX), D, ptr(g_u), _off(g_wl, D), wp, wn,
+                 st)
+            g_rg, g_wg, g_bl = linear_backward(rg, wg, g_u, lmu)
+            copy2d(g_wl[:, :D], g_wg)
+            g_relu = torch.empty_like(g_rg)
+            call("mvml_relu_bwd", g_rg.numel(), ptr(rg), ptr(g_rg), ptr(g_relu), 1.0, st)
+            call("mvml_add_cols_f32", B, D, ptr(g_relu), D, ptr(g_gf), D, st)
+            grads[:0] = [g_wl, g_bl, g_Wp, g_bp, g_wih, g_whh, g_bih, g_bhh]
+        g_sum = torch.empty((N, D), dtype=torch.float32, device=dev)
+        call("mvml_segment_pool_bwd", B, N, D, POOL_MODES["sum"], ptr(g.node_offsets), ptr(g_gf), D, None, D, ptr(g_sum), D,
+             st)
+        if steps:
+            call("mvml_add_cols_f32", N, D, ptr(g_sum), D, ptr(gX), D, st)
+        else:
+            gX = g_sum
+        return (gX, None, None, *grads)

@@ -13,7 +13,9 @@ Drop-in replacements, on the MI355X HIP path, for
   * dgl 0.9.1 ``SAGEConv`` and dgllife 0.3.0 ``GraphSAGE`` / ``GraphSAGEPredictor`` (the GraphSAGE
     baseline; not in model.py),
   * dgllife 0.3.0 ``GINLayer`` / ``GIN`` / ``GINPredictor`` (the bond-aware gin_supervised_* family
-    over categorical atom and bond features; not in model.py).
+    over categorical atom and bond features; not in model.py),
+  * dgllife 0.3.0 ``AttentiveFPGNN`` / ``AttentiveFPReadout`` / ``AttentiveFPPredictor`` (continuous
+    bond-feature vectors; not in model.py).
 Parameter names/shapes/registration order follow the reference so a ``net_i.pkl``
 ``model_state_dict`` (keys under ``gnn.``) loads unchanged.
 """
@@ -1070,3 +1072,149 @@ class GINPredictor(nn.Module):
         graph_feats = Fn.SegmentPoolFunction.apply(node_feats, g, self.readout)
         from .fusion import LinearFunction
         return LinearFunction.apply(graph_feats, self.predict.weight, self.predict.bias)
+
+
+def _check_afp(who, graph_feat_size, edge_feat_size, dropout):
+    # the ranges of mvml_afp_context_fwd / mvml_gru_cell_fwd / mvml_attn_pool_fwd: refuse here, not in forward
+    G = graph_feat_size
+    if not isinstance(G, int) or G <= 0 or G % 4 or G > Fn.AFP_MAX_WIDTH:
+        raise ValueError(f"{who}: graph_feat_size must be a positive multiple of 4 <= {Fn.AFP_MAX_WIDTH} on the HIP "
+                         f"path (got {G})")
+    if edge_feat_size is not None and not 1 <= edge_feat_size <= Fn.AFP_MAX_EDGE_FEATS:
+        raise ValueError(f"{who}: 1 to {Fn.AFP_MAX_EDGE_FEATS} bond features on the HIP path (got {edge_feat_size})")
+    if dropout != 0:
+        raise ValueError(f"{who}: dropout > 0 is not on the HIP path: two of AttentiveFP's dropouts act on per-edge "
+                         f"[E, graph_feat_size] rows, which the fused context kernel never materialises (got {dropout})")
+
+
+class _AttentiveGRU(nn.Module):
+    """AttentiveGRU1 / AttentiveGRU2's members: the Linear under `name` at index 1 of a Sequential
+    (index 0 is dgllife's Dropout), and gru = GRUCell."""
+
+    def __init__(self, name, in_size, hidden):
+        super().__init__()
+        setattr(self, name, nn.Sequential(nn.Dropout(0.), nn.Linear(in_size, hidden)))
+        self.gru = nn.GRUCell(hidden, hidden)
+
+    def gru_params(self):
+        return self.gru.weight_ih, self.gru.weight_hh, self.gru.bias_ih, self.gru.bias_hh
+
+
+class GetContext(nn.Module):
+    """dgllife.model.gnn.attentivefp.GetContext (0.3.0; restated, parity with dgllife is unpinned):
+    a parameter container with dgllife's members; forward(g, node_feats, edge_feats) runs
+    Fn.AFPContextFunction."""
+
+    def __init__(self, node_feat_size, edge_feat_size, graph_feat_size, dropout=0.):
+        super().__init__()
+        _check_afp("GetContext", graph_feat_size, edge_feat_size, dropout)
+        G = graph_feat_size
+        self.project_node = nn.Sequential(nn.Linear(node_feat_size, G), nn.LeakyReLU())
+        self.project_edge1 = nn.Sequential(nn.Linear(node_feat_size + edge_feat_size, G), nn.LeakyReLU())
+        self.project_edge2 = nn.Sequential(nn.Dropout(0.), nn.Linear(2 * G, 1), nn.LeakyReLU())
+        self.attentive_gru = _AttentiveGRU("edge_transform", G, G)
+        self._allow_zero_in_degree = True  # (an atom without in-edges has a zero context, as in DGL)
+
+    _check_graph = GATConv._check_graph
+
+    def forward(self, g, node_feats, edge_feats):
+        a = self.attentive_gru
+        return Fn.AFPContextFunction.apply(
+            node_feats, edge_feats, g, self.project_node[0].weight, self.project_node[0].bias,
+            self.project_edge1[0].weight, self.project_edge1[0].bias, self.project_edge2[1].weight,
+            self.project_edge2[1].bias, a.edge_transform[1].weight, a.edge_transform[1].bias, *a.gru_params())
+
+
+class AFPGNNLayer(nn.Module):
+    """dgllife.model.gnn.attentivefp.GNNLayer (0.3.0; restated) plus the BatchNorm1d that ends it:
+    forward(g, node_feats) runs Fn.AFPGNNLayerFunction."""
+
+    def __init__(self, node_feat_size, graph_feat_size, dropout=0.):
+        super().__init__()
+        _check_afp("GNNLayer", graph_feat_size, None, dropout)
+        if node_feat_size != graph_feat_size:
+            raise ValueError("GNNLayer: node_feat_size must equal graph_feat_size (its GRUCell's hidden state is the input)")
+        G = graph_feat_size
+        self.project_edge = nn.Sequential(nn.Dropout(0.), nn.Linear(2 * G, 1), nn.LeakyReLU())
+        self.attentive_gru = _AttentiveGRU("project_node", G, G)
+        self.bn_layer = nn.BatchNorm1d(G)
+
+    def forward(self, g, node_feats):
+        a, bn = self.attentive_gru, self.bn_layer
+        return Fn.AFPGNNLayerFunction.apply(node_feats, g, self.project_edge[1].weight, self.project_edge[1].bias,
+                                            a.project_node[1].weight, a.project_node[1].bias, *a.gru_params(),
+                                            bn.weight, bn.bias, bn)
+
+
+class AttentiveFPGNN(nn.Module):
+    """dgllife.model.gnn.attentivefp.AttentiveFPGNN (0.3.0; restated, parity with dgllife is
+    unpinned): init_context = GetContext, gnn_layers = num_layers - 1 GNNLayers, each ending in
+    BatchNorm1d(graph_feat_size).  forward(g, node_feats, edge_feats) -> (N, graph_feat_size);
+    edge_feats is a float [E, edge_feat_size] tensor in edge-id order.  Refused at construction:
+    graph_feat_size no positive multiple of 4 or above 1024, edge_feat_size outside [1, 32],
+    dropout > 0."""
+
+    def __init__(self, node_feat_size, edge_feat_size, num_layers=2, graph_feat_size=200, dropout=0.):
+        super().__init__()
+        if num_layers < 1:
+            raise ValueError(f"AttentiveFPGNN: num_layers must be at least 1, got {num_layers}")
+        self.init_context = GetContext(node_feat_size, edge_feat_size, graph_feat_size, dropout)
+        self.gnn_layers = nn.ModuleList(AFPGNNLayer(graph_feat_size, graph_feat_size, dropout)
+                                        for _ in range(num_layers - 1))
+
+    def forward(self, g, node_feats, edge_feats):
+        self.init_context._check_graph(g)
+        h = self.init_context(g, node_feats, edge_feats)
+        for layer in self.gnn_layers:
+            h = layer(g, h)
+        return h
+
+
+class _GlobalPool(nn.Module):
+    """dgllife's GlobalPool members (one readout timestep)."""
+
+    def __init__(self, feat_size):
+        super().__init__()
+        self.compute_logits = nn.Sequential(nn.Linear(2 * feat_size, 1), nn.LeakyReLU())
+        self.project_nodes = nn.Sequential(nn.Dropout(0.), nn.Linear(feat_size, feat_size))
+        self.gru = nn.GRUCell(feat_size, feat_size)
+
+    def params(self):
+        return (self.compute_logits[0].weight, self.compute_logits[0].bias, self.project_nodes[1].weight,
+                self.project_nodes[1].bias, self.gru.weight_ih, self.gru.weight_hh, self.gru.bias_ih, self.gru.bias_hh)
+
+
+class AttentiveFPReadout(nn.Module):
+    """dgllife.model.readout.attentivefp_readout.AttentiveFPReadout (0.3.0; restated, parity with
+    dgllife is unpinned): readouts = num_timesteps GlobalPools.  forward(g, node_feats) -> (B,
+    feat_size) through Fn.AFPReadoutFunction (get_node_weight is not implemented)."""
+
+    def __init__(self, feat_size, num_timesteps=2, dropout=0.):
+        super().__init__()
+        _check_afp("AttentiveFPReadout", feat_size, None, dropout)
+        self.readouts = nn.ModuleList(_GlobalPool(feat_size) for _ in range(num_timesteps))
+
+    def forward(self, g, node_feats):
+        ps = [p for r in self.readouts for p in r.params()]
+        return Fn.AFPReadoutFunction.apply(node_feats, g, len(self.readouts), *ps)
+
+
+class AttentiveFPPredictor(nn.Module):
+    """dgllife.model.model_zoo.attentivefp_predictor.AttentiveFPPredictor (0.3.0; restated, parity
+    with dgllife is unpinned): gnn = AttentiveFPGNN -> readout = AttentiveFPReadout -> predict =
+    Sequential(Dropout, Linear(graph_feat_size, n_tasks)).  forward(g, node_feats, edge_feats)
+    returns (B, n_tasks)."""
+
+    def __init__(self, node_feat_size, edge_feat_size, num_layers=2, num_timesteps=2, graph_feat_size=200, n_tasks=1,
+                 dropout=0.):
+        super().__init__()
+        self.gnn = AttentiveFPGNN(node_feat_size=node_feat_size, edge_feat_size=edge_feat_size, num_layers=num_layers,
+                                  graph_feat_size=graph_feat_size, dropout=dropout)
+        self.readout = AttentiveFPReadout(feat_size=graph_feat_size, num_timesteps=num_timesteps, dropout=dropout)
+        self.predict = nn.Sequential(nn.Dropout(0.), nn.Linear(graph_feat_size, n_tasks))
+
+    def forward(self, g, node_feats, edge_feats):
+        node_feats = self.gnn(g, node_feats, edge_feats)
+        g_feats = self.readout(g, node_feats)
+        from .fusion import LinearFunction
+        return LinearFunction.apply(g_feats, self.predict[1].weight, self.predict[1].bias)
