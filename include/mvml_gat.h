@@ -1298,6 +1298,53 @@ int mvml_attn_pool_bwd(int64_t B, int64_t N, int D, const int64_t* node_offsets,
                        int64_t ldgr, int accumulate, float* gX, int64_t ldgx, float* g_u,
                        float* g_wn, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * MPNN's edge-network convolution (dgl 0.9.1 NNConv, sum aggregator; dgllife 0.3.0 MPNNGNN;
+ * restated, parity with dgllife unpinned; csrc/nnconv.hip, DESIGN.md "MPNN").  All fp32.
+ *   W_e = view(z_e W2^T + b2, [D, D]),  m_e = h_u W_e,  out_v = sum_{e: u -> v} m_e + bias
+ * z [E][ldz] = ReLU(Linear1(bond rows)) in in-CSR SLOT order (mvml_afp_edge_rows then the GEMM), W2
+ * [D * D][H] dense (Linear2's weight).  The entries below cover the z W2^T part, re-associated as
+ * m_e = sum_i h_u[i] (z_e W2_i) with W2_i the [H, D] slice that makes row i of W_e, so nothing of
+ * shape [E, D * D] is ever in memory; the b2 part, (sum_{u -> v} h_u) view(b2), is node-level
+ * (mvml_gcn_agg and a GEMM).  D and H multiples of 16, 16 <= D <= 128, 16 <= H <= 256; anything else:
+ * MVML_ERR_INVALID before any launch, nothing written.  num_edges == 0: MVML_OK (the forward writes
+ * bias rows, the backward zero rows; the weight gradient zeros unless it accumulates).  Row
+ * pointers 16-byte aligned, pitches multiples of 4 and at least the row width.  No float atomics:
+ * bitwise repeatable, and an edge's message does not depend on the batch around it.
+ *
+ * mvml_nnconv_split_w2: max |W2| and the two scaled split-fp16 images of W2 in MFMA fragment order
+ *   (forward and data-gradient direction), mvml_nnconv_image_bytes(D, H) bytes (0: bad shape); once
+ *   per weight value, shared by every call that uses it.
+ * mvml_nnconv_slot_dst: slot_dst[s] = the destination atom of in-CSR slot s; once per batch.
+ * mvml_nnconv_fwd: out[v] = bias + sum over v's in-slots (slot order) of m_s (bias may be NULL); an atom
+ *   without in-edges gets exactly bias.  Split-fp16 MFMA, three products, each z row scaled by itself.
+ * mvml_nnconv_bwd_data: from g_out = dL/d out [N][ldg]:  dz[s] (+)= sum_i h_u[i] (g_out[v] W2_i^T)
+ *   (accumulate != 0 adds onto dz) and dH[u] = sum over u's out-edges of [ <z_s, g_out[v] W2_i^T> ]_i
+ *   (every row written; the b2 part's share is not included).
+ * mvml_nnconv_bwd_weight: dW2[(i, o), k] (+)= sum_s z[s][k] h_u[i] g_out[v][o]; fp32 MFMA over
+ *   edge ranges, the partials summed in fixed order.
+ * ------------------------------------------------------------------------------------- */
+size_t mvml_nnconv_image_bytes(int D, int H);
+int mvml_nnconv_split_w2(int D, int H, const float* W2, void* image, void* stream);
+int mvml_nnconv_slot_dst(int64_t num_nodes, const int32_t* in_rowptr, int32_t* slot_dst, void* stream);
+size_t mvml_nnconv_fwd_workspace_size(int64_t num_edges, int D);
+int mvml_nnconv_fwd(int64_t num_nodes, int64_t num_edges, const int32_t* in_rowptr,
+                    const int32_t* in_src, const float* h, int64_t ldh, int D, const float* z,
+                    int64_t ldz, int H, const void* image, const float* bias, float* out,
+                    int64_t ldo, void* workspace, size_t workspace_bytes, void* stream);
+size_t mvml_nnconv_bwd_data_workspace_size(int64_t num_edges, int D, int H);
+int mvml_nnconv_bwd_data(int64_t num_nodes, int64_t num_edges, const int32_t* in_src,
+                         const int32_t* slot_dst, const int32_t* out_rowptr,
+                         const int32_t* out_inslot, const float* h, int64_t ldh, int D,
+                         const float* z, int64_t ldz, int H, const void* image, const float* g_out,
+                         int64_t ldg, int accumulate, float* dz, int64_t lddz, float* dH,
+                         int64_t lddh, void* workspace, size_t workspace_bytes, void* stream);
+size_t mvml_nnconv_bwd_weight_workspace_size(int64_t num_edges, int D, int H);
+int mvml_nnconv_bwd_weight(int64_t num_edges, const int32_t* in_src, const int32_t* slot_dst,
+                           const float* h, int64_t ldh, int D, const float* z, int64_t ldz, int H,
+                           const float* g_out, int64_t ldg, int accumulate, float* dW2,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -251,6 +251,7 @@ class BatchedMolGraph:
         d.pop("sage_gcn_scale", None)  # ... and SAGEConv's 1 / (deg + 1) (functional.sage_gcn_scale)
         d.pop("gin_codes", None)  # ... and GIN's per-slot bond codes, in in-CSR order (functional.gin_edge_codes)
         d.pop("afp_rows", None)  # ... and AttentiveFP's bond rows in in-CSR order (functional.afp_edge_rows)
+        d.pop("nnconv_slot_dst", None)  # ... and MPNN's slot -> destination atom list (functional.nnconv_slot_dst)
         L = _lib.lib()
         wp, wn = _lib.ws_ptr_size(L.mvml_build_csr_workspace_size(B, N, E), self.device)
         P = _lib.ptr

@@ -2606,3 +2606,203 @@ class AFPReadoutFunction(torch.autograd.Function):
         else:
             gX = g_sum
         return (gX, None, None, *grads)
+
+
+# ---- MPNN: NNConv on csrc/nnconv.hip ("MPNN") ------------------------------------------
+NNCONV_MAX_D = 128  # node_out_feats (mvml_nnconv_fwd)
+NNCONV_MAX_H = 256  # edge_hidden_feats
+
+
+def nnconv_check(who, D, H):
+    """The widths mvml_nnconv_* take: multiples of 16, D in [16, 128], H in [16, 256]."""
+    for what, v, hi in (("node_out_feats", D, NNCONV_MAX_D), ("edge_hidden_feats", H, NNCONV_MAX_H)):
+        if not isinstance(v, int) or v < 16 or v % 16 or v > hi:
+            raise ValueError(f"{who}: {what} must be a multiple of 16 in [16, {hi}] on the HIP path (got {v})")
+
+
+def nnconv_flops(E, D, H):
+    """2 H D^2 per edge: the flops of one of the three NNConv products (the MFMA work of the
+    split-fp16 kernels is three times that, before their K padding)."""
+    return 2 * E * H * D * D
+
+
+def nnconv_slot_dst(g):
+    """int32 [E]: the destination atom of every in-CSR slot (mvml_nnconv_slot_dst), made once per
+    batch and kept on it; BatchedMolGraph.recollate() drops it."""
+    d = g._dev
+    if "nnconv_slot_dst" not in d:
+        t = torch.empty(max(g.num_edges(), 1), dtype=torch.int32, device=g.device)
+        call("mvml_nnconv_slot_dst", g.num_nodes(), ptr(g.in_rowptr), ptr(t), _stream(g.device))
+        d["nnconv_slot_dst"] = t
+    return d["nnconv_slot_dst"]
+
+
+def nnconv_image(W2, D, H):
+    """max |W2| and W2's two split-fp16 images in MFMA fragment order (mvml_nnconv_split_w2)."""
+    nbytes = _lib.lib().mvml_nnconv_image_bytes(D, H)
+    if nbytes == 0 or tuple(W2.shape) != (D * D, H):
+        raise ValueError(f"NNConv: edge_func must end in a Linear({H}, {D * D}) with widths that are multiples of 16, "
+                         f"D <= {NNCONV_MAX_D}, H <= {NNCONV_MAX_H} (weight {tuple(W2.shape)})")
+    img = torch.empty(nbytes, dtype=torch.uint8, device=W2.device)
+    call("mvml_nnconv_split_w2", D, H, ptr(W2), ptr(img), _stream(W2.device))
+    return img
+
+
+class NNConvShared:
+    """What the message-passing steps of one MPNNGNN forward share: W2's image (split once) and, in
+    the backward, ONE dz, dW2, db2 and dbias that every step's kernels add onto (their accumulate
+    flag), handed to autograd by the step whose backward runs last."""
+
+    def __init__(self, image, steps):
+        self.image, self.steps, self.done = image, steps, 0
+
+    def alloc(self, E, D, H, dev):
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.dz = torch.empty((max(E, 1), H), **f32)
+        self.dW2 = torch.empty((D * D, H), **f32)
+        self.db2 = torch.empty(D * D, **f32)
+        self.dbias = torch.empty(D, **f32)
+
+
+def nnconv_forward(g, h, z, b2, bias, image, act):
+    """(out, S): out = act(NNConv(h)) [N, D] dense, S = the per-destination sums of the source rows
+    (the b2 part's operand).  h [N, D] and z [E, H] row-pitched, b2 [D * D] and bias [D] dense."""
+    N, D = h.shape
+    E, H = g.num_edges(), z.shape[1]
+    dev = h.device
+    out = torch.empty((N, D), dtype=torch.float32, device=dev)
+    wp, wn = _lib.ws_ptr_size(_lib.lib().mvml_nnconv_fwd_workspace_size(E, D), dev)
+    _lib.call_tag[0] = {"layer": f"D{D}xH{H}", "flops": nnconv_flops(E, D, H)}
+    call("mvml_nnconv_fwd", N, E, ptr(g.in_rowptr), ptr(g.in_src), ptr(h), h.stride(0), D, ptr(z), z.stride(0), H,
+         ptr(image), ptr(bias), ptr(out), D, wp, wn, _stream(dev))
+    # (mvml_gcn_agg wants its neighbour list: a batch without any bond has none, and S = 0)
+    S = gcn_agg(h, h.stride(0), D, g, (None, None)) if E else zeros((N, D), device=dev)
+    gemm(S, b2, N, D, D, 0, 1, D, D, out, D, beta=1.0, act=int(act))  # out = act(out + S view(b2))
+    return out, S
+
+
+def nnconv_backward(g, h, z, b2, image, S, out, g_out, act, acc, accumulate):
+    """dL/dh [N, D] of nnconv_forward from g_out = dL/d out; dz, dW2, db2 and dbias go into (or,
+    accumulate, onto) acc's buffers."""
+    N, D = h.shape
+    E, H = g.num_edges(), z.shape[1]
+    dev = h.device
+    st = _stream(dev)
+    g_out = _c(g_out)
+    if act:
+        g_pre = torch.empty_like(out)
+        call("mvml_relu_bwd", out.numel(), ptr(out), ptr(g_out), ptr(g_pre), 1.0, st)
+    else:
+        g_pre = g_out
+    L = _lib.lib()
+    sd = nnconv_slot_dst(g)
+    dH = torch.empty((N, D), dtype=torch.float32, device=dev)
+    wp, wn = _lib.ws_ptr_size(L.mvml_nnconv_bwd_data_workspace_size(E, D, H), dev)
+    _lib.call_tag[0] = {"layer": f"D{D}xH{H}", "flops": 2 * nnconv_flops(E, D, H)}
+    call("mvml_nnconv_bwd_data", N, E, ptr(g.in_src), ptr(sd), ptr(g.out_rowptr), ptr(g.out_inslot), ptr(h), h.stride(0),
+         D, ptr(z), z.stride(0), H, ptr(image), ptr(g_pre), D, int(accumulate), ptr(acc.dz), H, ptr(dH), D, wp, wn, st)
+    wp, wn = _lib.ws_ptr_size(L.mvml_nnconv_bwd_weight_workspace_size(E, D, H), dev)
+    _lib.call_tag[0] = {"layer": f"D{D}xH{H}", "flops": nnconv_flops(E, D, H)}
+    call("mvml_nnconv_bwd_weight", E, ptr(g.in_src), ptr(sd), ptr(h), h.stride(0), D, ptr(z), z.stride(0), H, ptr(g_pre), D,
+         int(accumulate), ptr(acc.dW2), wp, wn, st)
+    # the b2 part, out += S view(b2): dB2 = S^T g, dS = g B2^T, dh += the sum of dS over the out-edges
+    beta = 1.0 if accumulate else 0.0
+    gemm(S, g_pre, D, D, N, 1, 1, D, D, acc.db2, D, beta=beta)
+    if E:
+        dS = torch.empty((N, D), dtype=torch.float32, device=dev)
+        gemm(g_pre, b2, N, D, D, 0, 0, D, D, dS, D)
+        dHb = gcn_agg(dS, D, D, g, (None, None), transpose=True)
+        call("mvml_add_cols_f32", N, D, ptr(dHb), D, ptr(dH), D, st)
+    colsum(g_pre, N, D, D, acc.dbias, beta=beta)
+    return dH
+
+
+class NNConvFunction(torch.autograd.Function):
+    """act(NNConv(h)) of one message-passing step as ONE autograd node (dgl 0.9.1 NNConv.forward, sum
+    aggregator; restated): mvml_nnconv_fwd for the z W2^T part of the per-edge weights, mvml_gcn_agg
+    and a GEMM for the b2 part, bias and the ReLU in their epilogues.  z [E, H] is the edge network's
+    hidden layer in in-CSR slot order (EdgeNetworkFunction), W2 / b2 its last Linear.  shared: the
+    NNConvShared of the forward this step belongs to (None: a step of its own)."""
+
+    @staticmethod
+    def forward(ctx, h, z, W2, b2, bias, g, act, shared):
+        _check_cuda_f32(h, "node_feats")
+        _check_cuda_f32(z, "edge hidden rows")
+        h, z, W2, b2 = _rows_f32(h), _rows_f32(z), _c(W2), _c(b2)
+        N, D = h.shape
+        H = z.shape[1]
+        if z.shape[0] != g.num_edges() or tuple(b2.shape) != (D * D,):
+            raise ValueError(f"NNConv: z must be [E = {g.num_edges()}, H] and edge_func's last bias [{D * D}] "
+                             f"(got {tuple(z.shape)}, {tuple(b2.shape)})")
+        image = shared.image if shared is not None else nnconv_image(W2, D, H)
+        bias = None if bias is None else _c(bias)
+        out, S = nnconv_forward(g, h, z, b2, bias, image, act)
+        ctx.state = (g, h, z, b2, bias is not None, image, S, int(act), shared)
+        ctx.save_for_backward(out)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        g, h, z, b2, has_bias, image, S, act, shared = ctx.state
+        acc = shared if shared is not None else NNConvShared(image, 1)
+        N, D = h.shape
+        E, H = g.num_edges(), z.shape[1]
+        first = acc.done == 0
+        if first:
+            acc.alloc(E, D, H, h.device)
+        dH = nnconv_backward(g, h, z, b2, image, S, ctx.saved_tensors[0], g_out, act, acc, not first)
+        acc.done += 1
+        if acc.done < acc.steps:  # a later backward hands the sums over
+            return dH, None, None, None, None, None, None, None
+        return dH, acc.dz[:E], acc.dW2, acc.db2, acc.dbias if has_bias else None, None, None, None
+
+
+class EdgeNetworkFunction(torch.autograd.Function):
+    """z = ReLU(Linear1(bond rows)) [E, H] in in-CSR slot order: the bond rows permuted and padded
+    to 4 columns once per batch (mvml_afp_edge_rows), then the Linear + ReLU GEMM.  Bond features
+    get no gradient."""
+
+    @staticmethod
+    def forward(ctx, edge_feats, g, W1, b1):
+        rows = afp_edge_rows(g, edge_feats)
+        E = g.num_edges()
+        H, De = W1.shape
+        if edge_feats.shape[1] != De:
+            raise ValueError(f"MPNN: {De} bond features expected, got {edge_feats.shape[1]}")
+        ctx.De = De
+        if E == 0:  # a batch without any bond: no rows, zero gradients
+            ctx.state = (H, g.device)
+            return torch.empty((0, H), dtype=torch.float32, device=g.device)
+        Wp = zeros((H, rows.shape[1]), device=g.device)
+        copy2d(Wp[:, :De], _c(W1))
+        rows, Wp, z, lm = linear_forward(rows, Wp, b1, act=1)
+        ctx.state = (rows, Wp, lm)
+        ctx.save_for_backward(z)
+        return z
+
+    @staticmethod
+    def backward(ctx, g_z):
+        if len(ctx.state) == 2:
+            H, dev = ctx.state
+            return None, None, zeros((H, ctx.De), device=dev), zeros(H, device=dev)
+        rows, Wp, lm = ctx.state
+        z, = ctx.saved_tensors
+        g_z = _c(g_z)
+        g_pre = torch.empty_like(z)
+        call("mvml_relu_bwd", z.numel(), ptr(z), ptr(g_z), ptr(g_pre), 1.0, _stream(z.device))
+        _, gWp, gb = linear_backward(rows, Wp, g_pre, lm, need_gx=False)
+        return None, None, _dense(gWp[:, :ctx.De]), gb
+
+
+class GRUCellFunction(torch.autograd.Function):
+    """torch GRUCell(x, h) as one autograd node: two gate GEMMs and mvml_gru_cell_fwd / _bwd."""
+
+    @staticmethod
+    def forward(ctx, x, h, w_ih, w_hh, b_ih, b_hh):
+        _check_cuda_f32(x, "x")
+        out, ctx.state = _gru_forward(x, _c(h), w_ih, w_hh, b_ih, b_hh, False)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        return _gru_backward(ctx.state, None, g_out)

@@ -1218,3 +1218,130 @@ class AttentiveFPPredictor(nn.Module):
         g_feats = self.readout(g, node_feats)
         from .fusion import LinearFunction
         return LinearFunction.apply(g_feats, self.predict[1].weight, self.predict[1].bias)
+
+
+class NNConv(nn.Module):
+    """dgl.nn.pytorch.conv.NNConv (0.9.1; restated, parity with dgl is unpinned) with the sum
+    aggregator on the fused edge-network kernels (csrc/nnconv.hip): edge_func must be
+    Sequential(Linear(edge_in_feats, H), ReLU, Linear(H, in_feats * out_feats)), whose per-edge
+    [in_feats, out_feats] matrices are never in memory.  forward(graph, feat, efeat) -> (N,
+    out_feats); efeat is a float [E, edge_in_feats] tensor in edge-id order.  Refused at
+    construction: in_feats != out_feats (and bipartite inputs with them), widths that are not
+    multiples of 16 or above 128 (H: 256), another aggregator, residual=True."""
+
+    def __init__(self, in_feats, out_feats, edge_func, aggregator_type="sum", residual=False, bias=True):
+        super().__init__()
+        if isinstance(in_feats, (tuple, list)) or in_feats != out_feats:
+            raise ValueError(f"NNConv: in_feats must equal out_feats on the HIP path, bipartite inputs are not "
+                             f"implemented (got {in_feats}, {out_feats})")
+        if aggregator_type != "sum":
+            raise ValueError(f'NNConv: only aggregator_type="sum" is on the HIP path (got "{aggregator_type}")')
+        if residual:
+            raise ValueError("NNConv: residual=True is not on the HIP path")
+        ok = (isinstance(edge_func, nn.Sequential) and len(edge_func) == 3 and isinstance(edge_func[0], nn.Linear)
+              and isinstance(edge_func[1], nn.ReLU) and isinstance(edge_func[2], nn.Linear)
+              and edge_func[0].bias is not None and edge_func[2].bias is not None
+              and edge_func[2].in_features == edge_func[0].out_features
+              and edge_func[2].out_features == in_feats * out_feats)
+        if not ok:
+            raise ValueError("NNConv: edge_func must be Sequential(Linear(edge_in_feats, H), ReLU(), "
+                             "Linear(H, in_feats * out_feats)) with biases on the HIP path")
+        Fn.nnconv_check("NNConv", out_feats, edge_func[0].out_features)
+        if not 1 <= edge_func[0].in_features <= Fn.AFP_MAX_EDGE_FEATS:
+            raise ValueError(f"NNConv: 1 to {Fn.AFP_MAX_EDGE_FEATS} bond features on the HIP path (got "
+                             f"{edge_func[0].in_features})")
+        self._in_src_feats = self._in_dst_feats = in_feats
+        self._out_feats = out_feats
+        self.edge_func = edge_func
+        self.bias = nn.Parameter(torch.empty(out_feats)) if bias else None
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        if self.bias is not None:
+            nn.init.zeros_(self.bias)
+
+    def edge_rows(self, graph, efeat):
+        """ReLU(edge_func[0](efeat)) in in-CSR slot order: the same for every step of a forward."""
+        return Fn.EdgeNetworkFunction.apply(efeat, graph, self.edge_func[0].weight, self.edge_func[0].bias)
+
+    def shared(self, steps):
+        """The NNConvShared of `steps` applications of this layer in one forward."""
+        w2 = self.edge_func[2].weight
+        return Fn.NNConvShared(Fn.nnconv_image(w2.detach().contiguous(), self._out_feats, w2.shape[1]), steps)
+
+    def fused(self, graph, feat, z, act=False, shared=None):
+        return Fn.NNConvFunction.apply(feat, z, self.edge_func[2].weight, self.edge_func[2].bias, self.bias, graph,
+                                       act, shared)
+
+    def forward(self, graph, feat, efeat):
+        return self.fused(graph, feat, self.edge_rows(graph, efeat))
+
+
+class MPNNGNN(nn.Module):
+    """dgllife.model.gnn.mpnn.MPNNGNN (0.3.0; restated, parity with dgllife is unpinned):
+    project_node_feats = Sequential(Linear, ReLU), then num_step_message_passing times
+    h = GRU(relu(gnn_layer(g, h, e)), h) with ONE NNConv and ONE single-layer GRU shared by all
+    steps.  forward(g, node_feats, edge_feats) -> (N, node_out_feats); edge_feats is a float [E,
+    edge_in_feats] tensor in edge-id order.  Refused at construction: node_out_feats no multiple of
+    16 in [16, 128], edge_hidden_feats none in [16, 256], more than 32 bond features."""
+
+    def __init__(self, node_in_feats, edge_in_feats, node_out_feats=64, edge_hidden_feats=128,
+                 num_step_message_passing=6):
+        super().__init__()
+        Fn.nnconv_check("MPNNGNN", node_out_feats, edge_hidden_feats)
+        D = node_out_feats
+        self.project_node_feats = nn.Sequential(nn.Linear(node_in_feats, D), nn.ReLU())
+        self.num_step_message_passing = num_step_message_passing
+        edge_network = nn.Sequential(nn.Linear(edge_in_feats, edge_hidden_feats), nn.ReLU(),
+                                     nn.Linear(edge_hidden_feats, D * D))
+        self.gnn_layer = NNConv(in_feats=D, out_feats=D, edge_func=edge_network, aggregator_type="sum")
+        self.gru = nn.GRU(D, D)
+
+    def reset_parameters(self):
+        self.project_node_feats[0].reset_parameters()
+        self.gnn_layer.reset_parameters()
+        for layer in self.gnn_layer.edge_func:
+            if isinstance(layer, nn.Linear):
+                layer.reset_parameters()
+        self.gru.reset_parameters()
+
+    _check_graph = GATConv._check_graph
+    _allow_zero_in_degree = True  # (an atom without in-edges gets NNConv's bias, as in DGL)
+
+    def forward(self, g, node_feats, edge_feats):
+        self._check_graph(g)
+        p = self.project_node_feats[0]
+        h = Fn.LinearReLUFunction.apply(node_feats, p.weight, p.bias)
+        steps = self.num_step_message_passing
+        if steps == 0:
+            return h
+        conv, gru = self.gnn_layer, self.gru
+        z = conv.edge_rows(g, edge_feats)
+        shared = conv.shared(steps)
+        for _ in range(steps):
+            h_conv, h_gru = Fn.ForkFunction.apply(h)
+            m = conv.fused(g, h_conv, z, act=True, shared=shared)
+            h = Fn.GRUCellFunction.apply(m, h_gru, gru.weight_ih_l0, gru.weight_hh_l0, gru.bias_ih_l0, gru.bias_hh_l0)
+        return h
+
+
+class MPNNPredictor(nn.Module):
+    """dgllife.model.model_zoo.mpnn_predictor.MPNNPredictor (0.3.0; restated, parity with dgllife
+    is unpinned): gnn = MPNNGNN -> readout = Set2Set -> predict = Sequential(Linear(2 D, D), ReLU,
+    Linear(D, n_tasks)).  forward(g, node_feats, edge_feats) returns (B, n_tasks)."""
+
+    def __init__(self, node_in_feats, edge_in_feats, node_out_feats=64, edge_hidden_feats=128, n_tasks=1,
+                 num_step_message_passing=6, num_step_set2set=6, num_layer_set2set=3):
+        super().__init__()
+        self.gnn = MPNNGNN(node_in_feats=node_in_feats, node_out_feats=node_out_feats, edge_in_feats=edge_in_feats,
+                           edge_hidden_feats=edge_hidden_feats, num_step_message_passing=num_step_message_passing)
+        self.readout = Set2Set(input_dim=node_out_feats, n_iters=num_step_set2set, n_layers=num_layer_set2set)
+        self.predict = nn.Sequential(nn.Linear(2 * node_out_feats, node_out_feats), nn.ReLU(),
+                                     nn.Linear(node_out_feats, n_tasks))
+
+    def forward(self, g, node_feats, edge_feats):
+        node_feats = self.gnn(g, node_feats, edge_feats)
+        graph_feats = self.readout(g, node_feats)
+        from .fusion import LinearFunction
+        hidden = Fn.LinearReLUFunction.apply(graph_feats, self.predict[0].weight, self.predict[0].bias)
+        return LinearFunction.apply(hidden, self.predict[2].weight, self.predict[2].bias)
