@@ -1345,6 +1345,64 @@ int mvml_nnconv_bwd_weight(int64_t num_edges, const int32_t* in_src, const int32
                            const float* g_out, int64_t ldg, int accumulate, float* dW2,
                            void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * D-MPNN, the directed bond-message network (Chemprop v1 MPNEncoder, bond messages, directed,
+ * ReLU; restated, parity with Chemprop unpinned; csrc/dmpnn.hip, DESIGN.md "D-MPNN").  All fp32.
+ *   input_s = W_i [x_u ; e_s] (+ b_i),  M^0_s = relu(input_s)                     for s = (u -> v)
+ *   M^t_s   = relu(input_s + W_h (sum_{k -> u} M^{t-1}_k - M^{t-1}_{rev(s)}) (+ b_h))
+ * Every per-bond matrix ([E][ld]) is in in-CSR SLOT order, as z is for NNConv: the states of the
+ * bonds entering an atom are one contiguous block of rows.
+ * THE REVERSE MAP: for s = (u -> v), the k-th edge u -> v in edge-id order, rev(s) is the k-th edge
+ * v -> u in edge-id order.  A self-loop is its own reverse.  An edge without such a partner has none
+ * (-1) and nothing is subtracted for it.
+ * D a positive multiple of 4, at most 1024; 1 <= De <= 32; anything else: MVML_ERR_INVALID before any
+ * launch, nothing written.  num_edges == 0: MVML_OK, nothing written.  Row pointers 16-byte aligned,
+ * pitches multiples of 4 and at least D; outputs must not alias inputs.  No float atomics: bitwise
+ * repeatable, and a molecule's rows do not depend on the batch around it.
+ *
+ * mvml_dmpnn_rev_slots: rev_slot[s] (int32, slot numbers, -1: none) by the rule above from the
+ *   in-CSR; once per batch.
+ * mvml_dmpnn_init_fwd: input[s] = (P[in_src[s]] + b_i) + sum_k rows[s][k] W_ieT[k] (k ascending, one fma
+ *   each) and M0[s] = relu(input[s]).  P [N][ldp] = x W_ia^T from the GEMM (W_i's atom columns), W_ieT
+ *   [De][D] dense (W_i's bond columns transposed), rows the padded bond rows of mvml_afp_edge_rows
+ *   (pitch De rounded up to 4), b_i [D] or NULL.  W_ieT is staged in LDS where it fits 48 KiB and read
+ *   from L2 otherwise: the same bits.
+ * mvml_dmpnn_update: with R [E][ldr] = M^{t-1} W_h^T from the GEMM, per atom v: Q = the sum of R over
+ *   v's in-slots (slot order from 0, each add rounded once); for every out-edge t of v (its slot f =
+ *   out_inslot[t]):  out[f] = relu((input[f] + b_h) + (Q - R[rev_slot[f]])), (Q) where rev is -1.  b_h
+ *   [D] or NULL.
+ * mvml_dmpnn_update_bwd: the adjoint, from out and g_out = dL/d out:  dpre[f] = g_out[f] * (out[f] > 0)
+ *   (g_out's bits or +0; every row written once: the gradient of input and, summed by
+ *   mvml_colsum_f32, of b_h) and dR[f] = (the sum of dpre over the out-edges of f's destination atom,
+ *   out-CSR order) - dpre[rev_slot[f]].
+ * mvml_dmpnn_atom_sum: a[v] = the sum of the rows M[idx[i]], i in [rowptr[v], rowptr[v + 1]), in list
+ *   order from 0 (idx NULL: the rows i themselves; an empty list gives +0), every atom row written.
+ *   With in_rowptr and no idx it is the atom sum a_v of the model; with out_rowptr and out_inslot
+ *   the adjoint of the gather P[in_src[s]].  mvml_dmpnn_atom_sum_bwd: dM[s] = g_a[the destination
+ *   atom of slot s], a row broadcast.  Both are instances of the update kernel with one list empty
+ *   (mvml_gcn_agg with an index list sums the same bits, but its alias check takes X and out to
+ *   have equally many rows, which an [E] and an [N] matrix have not).
+ * ------------------------------------------------------------------------------------- */
+int mvml_dmpnn_rev_slots(int64_t num_nodes, int64_t num_edges, const int32_t* in_rowptr,
+                         const int32_t* in_src, int32_t* rev_slot, void* stream);
+int mvml_dmpnn_init_fwd(int64_t num_nodes, int64_t num_edges, const int32_t* in_src, const float* P,
+                        int64_t ldp, int D, const float* rows, int De, const float* W_ieT,
+                        const float* b_i, float* input, int64_t ldi, float* M0, int64_t ldm,
+                        void* stream);
+int mvml_dmpnn_update(int64_t num_nodes, int64_t num_edges, const int32_t* in_rowptr,
+                      const int32_t* out_rowptr, const int32_t* out_inslot, const int32_t* rev_slot,
+                      const float* R, int64_t ldr, const float* input, int64_t ldi, const float* b_h,
+                      int D, float* out, int64_t ldo, void* stream);
+int mvml_dmpnn_update_bwd(int64_t num_nodes, int64_t num_edges, const int32_t* in_rowptr,
+                          const int32_t* out_rowptr, const int32_t* out_inslot,
+                          const int32_t* rev_slot, const float* out, int64_t ldo, const float* g_out,
+                          int64_t ldg, int D, float* dR, int64_t lddr, float* dpre, int64_t lddp,
+                          void* stream);
+int mvml_dmpnn_atom_sum(int64_t num_nodes, int64_t num_edges, const int32_t* rowptr, const int32_t* idx,
+                        const float* M, int64_t ldm, int D, float* a, int64_t lda, void* stream);
+int mvml_dmpnn_atom_sum_bwd(int64_t num_nodes, int64_t num_edges, const int32_t* in_rowptr,
+                            const float* g_a, int64_t ldg, int D, float* dM, int64_t lddm, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

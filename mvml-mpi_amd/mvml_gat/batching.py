@@ -252,6 +252,7 @@ class BatchedMolGraph:
         d.pop("gin_codes", None)  # ... and GIN's per-slot bond codes, in in-CSR order (functional.gin_edge_codes)
         d.pop("afp_rows", None)  # ... and AttentiveFP's bond rows in in-CSR order (functional.afp_edge_rows)
         d.pop("nnconv_slot_dst", None)  # ... and MPNN's slot -> destination atom list (functional.nnconv_slot_dst)
+        d.pop("dmpnn_rev_slots", None)  # ... and D-MPNN's reverse-bond slot map (functional.dmpnn_rev_slots)
         L = _lib.lib()
         wp, wn = _lib.ws_ptr_size(L.mvml_build_csr_workspace_size(B, N, E), self.device)
         P = _lib.ptr

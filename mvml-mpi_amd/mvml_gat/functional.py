@@ -2806,3 +2806,243 @@ class GRUCellFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_out):
         return _gru_backward(ctx.state, None, g_out)
+
+
+# ---- D-MPNN: directed bond messages on csrc/dmpnn.hip ("D-MPNN") ------------------------
+DMPNN_MAX_WIDTH = 1024  # hidden_size (mvml_dmpnn_update)
+
+
+def dmpnn_check(who, D, De, depth):
+    """What mvml_dmpnn_* take: D a positive multiple of 4 up to 1024, 1..32 bond features, depth >= 1."""
+    if not isinstance(D, int) or D <= 0 or D % 4 or D > DMPNN_MAX_WIDTH:
+        raise ValueError(f"{who}: hidden_size must be a positive multiple of 4, at most {DMPNN_MAX_WIDTH}, on the HIP "
+                         f"path (got {D})")
+    if not isinstance(De, int) or not 1 <= De <= AFP_MAX_EDGE_FEATS:
+        raise ValueError(f"{who}: 1 to {AFP_MAX_EDGE_FEATS} bond features on the HIP path (got {De})")
+    if not isinstance(depth, int) or depth < 1:
+        raise ValueError(f"{who}: depth must be at least 1 (got {depth})")
+
+
+def dmpnn_init_bytes(N, E, D, De):
+    """Algorithmic HBM bytes of one mvml_dmpnn_init_fwd: P, the bond rows, the sources and W_ieT read
+    once, input and M0 written (re-gathers of P rows not counted)."""
+    return 4 * (N * D + E * _round4(De) + E + (De + 1) * D + 2 * E * D)
+
+
+def dmpnn_update_bytes(N, E, D, backward=False):
+    """Algorithmic HBM bytes of one mvml_dmpnn_update (R and input read, out written) or of its
+    adjoint (out and g_out read, dR and dpre written), with both row pointers, out_inslot and the
+    reverse map; the re-read of the reverse rows is not counted."""
+    return 4 * ((4 if backward else 3) * E * D + 2 * (N + 1) + 2 * E + (0 if backward else D))
+
+
+def dmpnn_atom_sum_bytes(N, E, D):
+    """Algorithmic HBM bytes of mvml_dmpnn_atom_sum or its adjoint: the E slot rows and the N atom rows."""
+    return 4 * ((N + E) * D + N + 1)
+
+
+def dmpnn_rev_slots(g):
+    """int32 [E]: the in-CSR slot of every slot's reverse bond, -1 for none (mvml_dmpnn_rev_slots),
+    made once per batch and kept on it; BatchedMolGraph.recollate() drops it."""
+    d = g._dev
+    if "dmpnn_rev_slots" not in d:
+        t = torch.empty(max(g.num_edges(), 1), dtype=torch.int32, device=g.device)
+        call("mvml_dmpnn_rev_slots", g.num_nodes(), g.num_edges(), ptr(g.in_rowptr), ptr(g.in_src), ptr(t),
+             _stream(g.device))
+        d["dmpnn_rev_slots"] = t
+    return d["dmpnn_rev_slots"]
+
+
+def dmpnn_update(g, R, inp, b_h):
+    """The next bond state [E, D] from R = M W_h^T and input (mvml_dmpnn_update); all in slot order."""
+    E, D = R.shape
+    out = torch.empty((E, D), dtype=torch.float32, device=R.device)
+    _lib.call_tag[0] = {"layer": f"D{D}", "bytes": dmpnn_update_bytes(g.num_nodes(), E, D)}
+    call("mvml_dmpnn_update", g.num_nodes(), E, ptr(g.in_rowptr), ptr(g.out_rowptr), ptr(g.out_inslot),
+         ptr(dmpnn_rev_slots(g)), ptr(R), R.stride(0), ptr(inp), inp.stride(0), ptr(b_h), D, ptr(out), D, _stream(R.device))
+    return out
+
+
+def dmpnn_update_bwd(g, out, g_out):
+    """(dR, dpre) of dmpnn_update from its output and g_out = dL/d out (mvml_dmpnn_update_bwd)."""
+    E, D = out.shape
+    dR, dpre = torch.empty_like(out), torch.empty_like(out)
+    _lib.call_tag[0] = {"layer": f"D{D}", "bytes": dmpnn_update_bytes(g.num_nodes(), E, D, True)}
+    call("mvml_dmpnn_update_bwd", g.num_nodes(), E, ptr(g.in_rowptr), ptr(g.out_rowptr), ptr(g.out_inslot),
+         ptr(dmpnn_rev_slots(g)), ptr(out), out.stride(0), ptr(g_out), g_out.stride(0), D, ptr(dR), D, ptr(dpre), D,
+         _stream(out.device))
+    return dR, dpre
+
+
+def dmpnn_atom_sum(g, M, transpose=False):
+    """[N, D]: per atom the sum of its in-slot rows of M, or (transpose) of the slot rows of its
+    out-edges, the adjoint of gathering an atom row per slot by in_src (mvml_dmpnn_atom_sum)."""
+    N, E, D = g.num_nodes(), g.num_edges(), M.shape[1]
+    a = torch.empty((N, D), dtype=torch.float32, device=M.device)
+    rowptr, idx = (g.out_rowptr, g.out_inslot) if transpose else (g.in_rowptr, None)
+    _lib.call_tag[0] = {"layer": f"D{D}", "bytes": dmpnn_atom_sum_bytes(N, E, D)}
+    call("mvml_dmpnn_atom_sum", N, E, ptr(rowptr), ptr(idx), ptr(M), M.stride(0) if E else D, D, ptr(a), D,
+         _stream(M.device))
+    return a
+
+
+def _dmpnn_split(W, Fa, Fp):
+    """(W[:, :Fa] zero-padded to Fp columns, W[:, Fa:] dense) of a weight over [atom features ; rest]."""
+    Wa = zeros((W.shape[0], Fp), device=W.device)
+    copy2d(Wa[:, :Fa], W[:, :Fa])
+    return Wa, _dense(W[:, Fa:])
+
+
+def _dmpnn_join(ga, gb):
+    """The gradient of such a weight from those of its two column blocks."""
+    Fa = ga.shape[1]
+    gW = torch.empty((ga.shape[0], Fa + gb.shape[1]), dtype=torch.float32, device=ga.device)
+    copy2d(gW[:, :Fa], ga)
+    copy2d(gW[:, Fa:], gb)
+    return gW
+
+
+class DMPNNInitFunction(torch.autograd.Function):
+    """(input, M0) [E, D] in in-CSR slot order: input_s = W_i [x_u ; e_s] (+ b_i) for s = (u -> v), M0 =
+    relu(input).  Re-associated, no [E, Fa + De] concat: P = x W_ia^T is one GEMM over the atom rows,
+    mvml_dmpnn_init_fwd gathers it and adds the bond part.  The backward needs no kernel of its own:
+    gP by mvml_dmpnn_atom_sum over the out-edges, the bond columns' gradient rows^T g_input on the
+    GEMM.  Bond features get no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, edge_feats, g, W_i, b_i):
+        _check_cuda_f32(x, "node_feats")
+        ctx.set_materialize_grads(False)
+        X, Xp = _padded_input(x)
+        N, Fa = X.shape
+        D, De = W_i.shape[0], W_i.shape[1] - Fa
+        E, dev = g.num_edges(), X.device
+        rows = afp_edge_rows(g, edge_feats)
+        if edge_feats.shape[1] != De:
+            raise ValueError(f"D-MPNN: {De} bond features expected, got {edge_feats.shape[1]}")
+        inp = torch.empty((E, D), dtype=torch.float32, device=dev)
+        M0 = torch.empty((E, D), dtype=torch.float32, device=dev)
+        ctx.dims, ctx.dev = (W_i.shape, b_i is not None, Fa), dev
+        if E == 0:  # a batch without any bond: no rows, zero gradients
+            ctx.state = None
+            return inp, M0
+        W_i = _c(W_i)
+        Wa, We = _dmpnn_split(W_i, Fa, Xp.shape[1])
+        Xp, Wa, P, lm = linear_forward(Xp, Wa, None)
+        WieT = torch.empty((De, D), dtype=torch.float32, device=dev)
+        call("mvml_transpose", D, De, ptr(We), De, ptr(WieT), D, _stream(dev))
+        _lib.call_tag[0] = {"layer": f"D{D}xDe{De}", "bytes": dmpnn_init_bytes(N, E, D, De)}
+        call("mvml_dmpnn_init_fwd", N, E, ptr(g.in_src), ptr(P), D, D, ptr(rows), De, ptr(WieT),
+             ptr(None if b_i is None else _c(b_i)), ptr(inp), D, ptr(M0), D, _stream(dev))
+        ctx.state = (g, rows, Xp, Wa, lm)
+        ctx.save_for_backward(M0)
+        return inp, M0
+
+    @staticmethod
+    def backward(ctx, g_inp, g_M0):
+        shape, has_bias, Fa = ctx.dims
+        D, De = shape[0], shape[1] - Fa
+        if ctx.state is None or (g_inp is None and g_M0 is None):
+            dev = ctx.dev
+            return None, None, None, zeros(tuple(shape), device=dev), zeros(D, device=dev) if has_bias else None
+        g, rows, Xp, Wa, lm = ctx.state
+        (M0,) = ctx.saved_tensors
+        E, dev = M0.shape[0], M0.device
+        st = _stream(dev)
+        if g_M0 is not None:  # g_in = g_input + g_M0 * (M0 > 0)
+            g_in = torch.empty_like(M0)
+            call("mvml_relu_bwd", M0.numel(), ptr(M0), ptr(_c(g_M0)), ptr(g_in), 1.0, st)
+            if g_inp is not None:
+                g_inp = _rows_f32(g_inp)
+                call("mvml_add_cols_f32", E, D, ptr(g_inp), g_inp.stride(0), ptr(g_in), D, st)
+        else:
+            g_in = _c(g_inp)
+        gP = dmpnn_atom_sum(g, g_in, transpose=True)
+        gXp, gWa, _ = linear_backward(Xp, Wa, gP, lm, need_gb=False, need_gx=ctx.needs_input_grad[0])
+        Dp = rows.shape[1]
+        gWe = torch.empty((D, Dp), dtype=torch.float32, device=dev)
+        gemm(g_in, rows, D, Dp, E, 1, 1, D, Dp, gWe, Dp)  # g_in^T rows: the bond columns
+        gb = None
+        if has_bias:
+            gb = torch.empty(D, dtype=torch.float32, device=dev)
+            colsum(g_in, E, D, D, gb)
+        gX = _dense(gXp[:, :Fa]) if gXp is not None else None
+        return gX, None, None, _dmpnn_join(gWa[:, :Fa], gWe[:, :De]), gb
+
+
+class DMPNNStepFunction(torch.autograd.Function):
+    """One depth step, M' = relu(input + W_h (sum of the bond states entering the source atom - the
+    reverse bond's) (+ b_h)), as one autograd node: R = M W_h^T on the GEMM over the E slot rows (no
+    gather), then mvml_dmpnn_update.  Backward: the adjoint kernel gives dR and dpre (the gradient
+    of input; its column sums that of b_h), then the Linear's two products."""
+
+    @staticmethod
+    def forward(ctx, inp, M, W_h, b_h, g):
+        _check_cuda_f32(M, "bond states")
+        E, D = M.shape
+        if E != g.num_edges() or tuple(inp.shape) != (E, D) or tuple(W_h.shape) != (D, D):
+            raise ValueError(f"D-MPNN step: input and M must be [E = {g.num_edges()}, D] and W_h [D, D] "
+                             f"(got {tuple(inp.shape)}, {tuple(M.shape)}, {tuple(W_h.shape)})")
+        ctx.has_bias = b_h is not None
+        if E == 0:
+            ctx.state = None
+            ctx.D = D
+            return torch.empty_like(M)
+        M, W_h, R, lm = linear_forward(M, W_h, None)
+        out = dmpnn_update(g, R, _rows_f32(inp), None if b_h is None else _c(b_h))
+        ctx.state = (g, M, W_h, lm)
+        ctx.save_for_backward(out)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        if ctx.state is None:
+            D, dev = ctx.D, g_out.device
+            return g_out, g_out, zeros((D, D), device=dev), zeros(D, device=dev) if ctx.has_bias else None, None
+        g, M, W_h, lm = ctx.state
+        (out,) = ctx.saved_tensors
+        E, D = out.shape
+        dR, dpre = dmpnn_update_bwd(g, out, _rows_f32(g_out))
+        gM, gW, _ = linear_backward(M, W_h, dR, lm, need_gb=False)
+        gb = None
+        if ctx.has_bias:
+            gb = torch.empty(D, dtype=torch.float32, device=out.device)
+            colsum(dpre, E, D, D, gb)
+        return dpre, gM, gW, gb, None
+
+
+class DMPNNOutputFunction(torch.autograd.Function):
+    """h_v = relu(W_o [x_v ; a_v] + b_o), a_v = the sum of the bond states entering v
+    (mvml_dmpnn_atom_sum), without the [N, Fa + D] concat: two GEMMs, the second onto the first with
+    the ReLU in its epilogue."""
+
+    @staticmethod
+    def forward(ctx, x, M, g, W_o, b_o):
+        _check_cuda_f32(x, "node_feats")
+        X, Xp = _padded_input(x)
+        N, Fa = X.shape
+        W_o = _c(W_o)
+        D = W_o.shape[0]
+        Wa, Wm = _dmpnn_split(W_o, Fa, Xp.shape[1])
+        a = dmpnn_atom_sum(g, _rows_f32(M))
+        Xp, Wa, y, lmx = linear_forward(Xp, Wa, b_o)
+        a, Wm, h, lma = linear_forward(a, Wm, None, act=1, onto=y)
+        ctx.state = (g, Xp, Wa, lmx, a, Wm, lma, Fa)
+        ctx.save_for_backward(h)
+        return h
+
+    @staticmethod
+    def backward(ctx, g_h):
+        g, Xp, Wa, lmx, a, Wm, lma, Fa = ctx.state
+        (h,) = ctx.saved_tensors
+        N, D = h.shape
+        E, dev = g.num_edges(), h.device
+        g_pre = torch.empty_like(h)
+        call("mvml_relu_bwd", h.numel(), ptr(h), ptr(_c(g_h)), ptr(g_pre), 1.0, _stream(dev))
+        g_a, gWm, _ = linear_backward(a, Wm, g_pre, lma, need_gb=False)
+        gXp, gWa, gb = linear_backward(Xp, Wa, g_pre, lmx, need_gx=ctx.needs_input_grad[0])
+        gM = torch.empty((E, D), dtype=torch.float32, device=dev)
+        _lib.call_tag[0] = {"layer": f"D{D}", "bytes": dmpnn_atom_sum_bytes(N, E, D)}
+        call("mvml_dmpnn_atom_sum_bwd", N, E, ptr(g.in_rowptr), ptr(g_a), D, D, ptr(gM), D, _stream(dev))
+        gX = _dense(gXp[:, :Fa]) if gXp is not None else None
+        return gX, gM, None, _dmpnn_join(gWa[:, :Fa], gWm), gb

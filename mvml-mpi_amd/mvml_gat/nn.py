@@ -1345,3 +1345,68 @@ class MPNNPredictor(nn.Module):
         from .fusion import LinearFunction
         hidden = Fn.LinearReLUFunction.apply(graph_feats, self.predict[0].weight, self.predict[0].bias)
         return LinearFunction.apply(hidden, self.predict[2].weight, self.predict[2].bias)
+
+
+class DMPNNGNN(nn.Module):
+    """The directed message-passing encoder (Chemprop v1 MPNEncoder with its defaults: bond messages,
+    directed, ReLU; restated, parity with Chemprop is unpinned), whose hidden state lives on the
+    directed bonds (csrc/dmpnn.hip, DESIGN.md "D-MPNN").  For a bond s = (u -> v):
+        input_s = W_i [x_u ; e_s],  M^0_s = relu(input_s),
+        M^t_s = relu(input_s + W_h (sum_{k -> u} M^{t-1}_k - M^{t-1}_{rev(s)}))  for t = 1 .. depth - 1,
+        h_v = relu(W_o [x_v ; sum_{k -> v} M^{depth-1}_k])
+    with rev(s), for the k-th edge u -> v in edge-id order, the k-th edge v -> u (a self-loop its own
+    reverse; nothing subtracted where there is none).  forward(g, node_feats, edge_feats) -> (N,
+    hidden_size); edge_feats is a float [E, edge_in_feats] tensor in edge-id order.  depth = 1 runs no
+    update step.  Refused at construction: dropout > 0, a hidden_size that is no multiple of 4 or above
+    1024, edge_in_feats outside 1..32, depth < 1."""
+
+    def __init__(self, node_in_feats, edge_in_feats, hidden_size=300, depth=3, bias=False, dropout=0.0):
+        super().__init__()
+        if dropout > 0:
+            raise ValueError("DMPNNGNN: dropout > 0 is not on the HIP path: Chemprop's message dropout acts inside the "
+                             "depth loop, on every bond state, and the update kernel has no such stage")
+        Fn.dmpnn_check("DMPNNGNN", hidden_size, edge_in_feats, depth)
+        self.depth = depth
+        self.W_i = nn.Linear(node_in_feats + edge_in_feats, hidden_size, bias=bias)
+        self.W_h = nn.Linear(hidden_size, hidden_size, bias=bias)
+        self.W_o = nn.Linear(node_in_feats + hidden_size, hidden_size)
+
+    def reset_parameters(self):
+        for lin in (self.W_i, self.W_h, self.W_o):
+            lin.reset_parameters()
+
+    _check_graph = GATConv._check_graph
+    _allow_zero_in_degree = True  # (an atom without in-edges sums nothing: a_v = 0)
+
+    def forward(self, g, node_feats, edge_feats):
+        self._check_graph(g)
+        inp, M = Fn.DMPNNInitFunction.apply(node_feats, edge_feats, g, self.W_i.weight, self.W_i.bias)
+        for t in range(1, self.depth):
+            # (input feeds every step: its gradients meet in ForkFunction's kernel, not in the engine)
+            inp_t, inp = Fn.ForkFunction.apply(inp) if t + 1 < self.depth else (inp, None)
+            M = Fn.DMPNNStepFunction.apply(inp_t, M, self.W_h.weight, self.W_h.bias, g)
+        return Fn.DMPNNOutputFunction.apply(node_feats, M, g, self.W_o.weight, self.W_o.bias)
+
+
+class DMPNNPredictor(nn.Module):
+    """gnn = DMPNNGNN -> the per-molecule "mean" (Chemprop's default) or "sum" of the atom rows
+    (Fn.SegmentPoolFunction) -> predict = Sequential(Linear(D, ffn_hidden_size or D), ReLU,
+    Linear(., n_tasks)) (restated; parity with Chemprop is unpinned).  forward(g, node_feats,
+    edge_feats) returns (B, n_tasks)."""
+
+    def __init__(self, node_in_feats, edge_in_feats, hidden_size=300, depth=3, bias=False, aggregation="mean",
+                 ffn_hidden_size=None, n_tasks=1):
+        super().__init__()
+        if aggregation not in ("mean", "sum"):
+            raise ValueError(f'DMPNNPredictor: aggregation must be "mean" or "sum" (got {aggregation!r})')
+        self.gnn = DMPNNGNN(node_in_feats, edge_in_feats, hidden_size=hidden_size, depth=depth, bias=bias)
+        self.aggregation = aggregation
+        ffn = hidden_size if ffn_hidden_size is None else ffn_hidden_size
+        self.predict = nn.Sequential(nn.Linear(hidden_size, ffn), nn.ReLU(), nn.Linear(ffn, n_tasks))
+
+    def forward(self, g, node_feats, edge_feats):
+        node_feats = self.gnn(g, node_feats, edge_feats)
+        graph_feats = Fn.SegmentPoolFunction.apply(node_feats, g, self.aggregation)
+        from .fusion import LinearFunction
+        hidden = Fn.LinearReLUFunction.apply(graph_feats, self.predict[0].weight, self.predict[0].bias)
+        return LinearFunction.apply(hidden, self.predict[2].weight, self.predict[2].bias)
