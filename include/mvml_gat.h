@@ -1403,6 +1403,54 @@ int mvml_dmpnn_atom_sum(int64_t num_nodes, int64_t num_edges, const int32_t* row
 int mvml_dmpnn_atom_sum_bwd(int64_t num_nodes, int64_t num_edges, const int32_t* in_rowptr,
                             const float* g_a, int64_t ldg, int D, float* dM, int64_t lddm, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * SchNet's continuous-filter convolution (dgl 0.9.1 CFConv, dgllife 0.3.0 SchNetGNN; restated,
+ * parity with dgllife unpinned; csrc/schnet.hip, DESIGN.md "SchNet").  All fp32.  For an edge
+ * s = (u -> v) with distance d_s, centres mu [K], ssp(x) = softplus(x) - ln 2 (beta 1, threshold 20):
+ *   rbf_s[k] = exp(-gamma (d_s - mu_k)^2)                              (never in memory)
+ *   s1_s = ssp(rbf_s W_1^T + b_1),  he_s = ssp(s1_s W_2^T + b_2),  a_v = sum_{u -> v} hv[u] * he_s
+ * W_1 [H][K] and W_2 [H][H] dense.  d is one float per in-CSR SLOT at a stride of ldd floats; every
+ * per-edge matrix ([E][ld]) is in slot order.  H a multiple of 16 in [16, 128], 1 <= K <= 512,
+ * gamma > 0; anything else: MVML_ERR_INVALID before any launch, nothing written.  num_edges == 0:
+ * MVML_OK (mvml_cfconv_agg writes zero rows, mvml_schnet_dw1 zeros unless it accumulates).  Row
+ * pointers 16-byte aligned, pitches multiples of 4 and at least H.  No float atomics: bitwise
+ * repeatable, and a slot's or an atom's bits do not depend on the batch around it.
+ *
+ * mvml_schnet_split_w: max |W_1|, max |W_2| and the scaled split-fp16 images of W_1 (K padded to a
+ *   multiple of 32 with zeros), W_2 and W_2 transposed in MFMA fragment order,
+ *   mvml_schnet_image_bytes(H, K) bytes (0: bad shape); once per weight value.
+ * mvml_schnet_filter_fwd: s1 and he from d; the expansion is generated in registers as the MFMA A
+ *   operand (three split-fp16 products, fixed scale 2^14), s1 is re-split per row on the CU.
+ * mvml_schnet_filter_bwd: from dA = dL/da [N][lda] and hv [N][ldh]: dpre2[s] = (dA[slot_dst[s]] *
+ *   hv[in_src[s]]) ssp'(he[s]) and dpre1[s] = (dpre2[s] W_2) ssp'(s1[s]), ssp'(y) = 1 - exp(-y) / 2 from
+ *   the output.  Their column sums are db_2 and db_1, dpre2^T s1 is dW_2 (mvml_colsum_f32, the GEMM).
+ * mvml_schnet_dw1: dW_1[j][k] (+)= sum_s dpre1[s][j] rbf_s[k] (accumulate != 0 adds onto dW_1); fp32
+ *   MFMA over slot ranges with the expansion generated, the partials summed in fixed order.
+ * mvml_cfconv_agg: out[v] = sum over i in [rowptr[v], rowptr[v + 1]) of X[xidx[w]] * Wt[w], w = widx ?
+ *   widx[i] : i, in list order from 0, one fma per entry; an empty list gives +0; every row written.
+ *   a: (in_rowptr, NULL, in_src, hv, he).  dL/dhv: (out_rowptr, out_inslot, slot_dst, dA, he).
+ * mvml_ssp_fwd: y[i] = ssp(x[i]); mvml_ssp_bwd: g_x[i] = g_y[i] (1 - exp(-y[i]) / 2).  x == y and
+ *   g_y == g_x are allowed.
+ * ------------------------------------------------------------------------------------- */
+size_t mvml_schnet_image_bytes(int H, int K);
+int mvml_schnet_split_w(int H, int K, const float* W1, const float* W2, void* image, void* stream);
+int mvml_schnet_filter_fwd(int64_t num_edges, const float* d, int64_t ldd, const float* centers, int K,
+                           float gamma, int H, const void* image, const float* b1, const float* b2,
+                           float* s1, int64_t lds1, float* he, int64_t ldhe, void* stream);
+int mvml_schnet_filter_bwd(int64_t num_edges, const int32_t* in_src, const int32_t* slot_dst,
+                           const float* dA, int64_t lda, const float* hv, int64_t ldh, const float* s1,
+                           int64_t lds1, const float* he, int64_t ldhe, int H, int K, const void* image,
+                           float* dpre2, int64_t ld2, float* dpre1, int64_t ld1, void* stream);
+size_t mvml_schnet_dw1_workspace_size(int64_t num_edges, int H, int K);
+int mvml_schnet_dw1(int64_t num_edges, const float* d, int64_t ldd, const float* centers, int K,
+                    float gamma, const float* dpre1, int64_t ld1, int H, int accumulate, float* dW1,
+                    void* workspace, size_t workspace_bytes, void* stream);
+int mvml_cfconv_agg(int64_t num_nodes, int64_t num_edges, const int32_t* rowptr, const int32_t* widx,
+                    const int32_t* xidx, const float* X, int64_t ldx, const float* Wt, int64_t ldw,
+                    int H, float* out, int64_t ldo, void* stream);
+int mvml_ssp_fwd(int64_t n, const float* x, float* y, void* stream);
+int mvml_ssp_bwd(int64_t n, const float* y, const float* g_y, float* g_x, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

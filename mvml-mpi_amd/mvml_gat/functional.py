@@ -3046,3 +3046,269 @@ class DMPNNOutputFunction(torch.autograd.Function):
         call("mvml_dmpnn_atom_sum_bwd", N, E, ptr(g.in_rowptr), ptr(g_a), D, D, ptr(gM), D, _stream(dev))
         gX = _dense(gXp[:, :Fa]) if gXp is not None else None
         return gX, gM, None, _dmpnn_join(gWa[:, :Fa], gWm), gb
+
+
+# ---- SchNet: the fused filter network and CFConv on csrc/schnet.hip ("SchNet") ----------
+SCHNET_MAX_H = 128     # hidden_feats of a CFConv (mvml_schnet_filter_fwd)
+SCHNET_MAX_K = 512     # radial-basis centres
+SCHNET_MAX_F = 1024    # node_feats
+
+
+def schnet_num_centers(cutoff, gap):
+    """K = ceil(cutoff / gap), dgllife's RBFExpansion count; ValueError naming the argument at fault."""
+    if not cutoff > 0:
+        raise ValueError(f"SchNet: cutoff must be positive (got {cutoff})")
+    if not gap > 0:
+        raise ValueError(f"SchNet: gap must be positive (got {gap})")
+    K = int(np.ceil(cutoff / gap))
+    if not 1 <= K <= SCHNET_MAX_K:
+        raise ValueError(f"SchNet: cutoff / gap must give 1 to {SCHNET_MAX_K} centres on the HIP path (got K = {K})")
+    return K
+
+
+def schnet_check(who, F=None, H=None):
+    """The widths mvml_schnet_* take: hidden_feats a multiple of 16 in [16, 128], node_feats a
+    positive multiple of 4 up to 1024."""
+    if H is not None and (not isinstance(H, int) or H < 16 or H % 16 or H > SCHNET_MAX_H):
+        raise ValueError(f"{who}: hidden_feats must be a multiple of 16 in [16, {SCHNET_MAX_H}] on the HIP path (got {H})")
+    if F is not None and (not isinstance(F, int) or F <= 0 or F % 4 or F > SCHNET_MAX_F):
+        raise ValueError(f"{who}: node_feats must be a positive multiple of 4, at most {SCHNET_MAX_F}, on the HIP path "
+                         f"(got {F})")
+
+
+def schnet_filter_flops(E, H, K):
+    """Useful flops of one filter forward: the K x H and the H x H product per edge (the MFMA work is
+    three times that, before K's padding to a multiple of 32)."""
+    return 2 * E * H * (K + H)
+
+
+def schnet_filter_fwd_bytes(E, H, K):
+    """Algorithmic HBM bytes of one mvml_schnet_filter_fwd: one float per edge read, s1 and he written;
+    the centres, biases and the three-image weight file once."""
+    return 4 * (E + 2 * E * H + K + 2 * H) + _lib.lib().mvml_schnet_image_bytes(H, K)
+
+
+def schnet_filter_bwd_bytes(N, E, H):
+    """Algorithmic bytes of one mvml_schnet_filter_bwd: he and s1 read, dpre2 and dpre1 written, both
+    index lists, the dA and hv rows once (re-gathers not counted), W_2's transposed image."""
+    return 4 * (4 * E * H + 2 * E + 2 * N * H) + 2 * H * H * 4
+
+
+def schnet_dw1_bytes(E, H, K):
+    """Algorithmic bytes of one mvml_schnet_dw1: dpre1 once per group of 64 centres, one float per edge,
+    the partials written and re-read, dW_1."""
+    S = max(1, min(-(-E // 128), 128))
+    return 4 * (-(-K // 64) * E * H + E + 2 * S * H * K + H * K)
+
+
+def cfconv_agg_bytes(N, E, H):
+    """Algorithmic bytes of one mvml_cfconv_agg: the E filter rows and the N atom rows read once
+    (re-gathers not counted), out written, the row pointers and up to two index lists."""
+    return 4 * (E * H + 2 * N * H + N + 1 + 2 * E)
+
+
+def schnet_slot_dists(g, edge_dists):
+    """(d, stride): the distances in in-CSR slot order, column 0 of the padded rows of
+    mvml_afp_edge_rows; permuted once per (batch, tensor), kept on the batch and dropped by
+    BatchedMolGraph.recollate()."""
+    E = g.num_edges()
+    d = edge_dists
+    if d.dim() == 1:
+        d = d.view(-1, 1)
+    if d.dim() != 2 or tuple(d.shape) != (E, 1):
+        raise ValueError(f"edge_dists: a float [E = {E}] or [E, 1] tensor in edge-id order expected, got "
+                         f"{tuple(edge_dists.shape)}")
+    rows = afp_edge_rows(g, d)
+    return rows, rows.shape[1]
+
+
+def schnet_image(W1, W2, H, K):
+    """max |W_1|, max |W_2| and the split-fp16 images of W_1, W_2 and W_2^T (mvml_schnet_split_w)."""
+    nbytes = _lib.lib().mvml_schnet_image_bytes(H, K)
+    if nbytes == 0 or tuple(W1.shape) != (H, K) or tuple(W2.shape) != (H, H):
+        raise ValueError(f"CFConv: project_edge must be Linear({K}, {H}), Linear({H}, {H}) with H a multiple of 16 <= "
+                         f"{SCHNET_MAX_H} and K <= {SCHNET_MAX_K} (weights {tuple(W1.shape)}, {tuple(W2.shape)})")
+    img = torch.empty(nbytes, dtype=torch.uint8, device=W1.device)
+    call("mvml_schnet_split_w", H, K, ptr(W1), ptr(W2), ptr(img), _stream(W1.device))
+    return img
+
+
+def schnet_dw1(dists, ldd, centers, gamma, dpre1, E, H, K, out, accumulate=False):
+    """out [H, K] (+)= dpre1^T rbf(dists) with the expansion generated in the kernel (mvml_schnet_dw1)."""
+    wp, wn = _lib.ws_ptr_size(_lib.lib().mvml_schnet_dw1_workspace_size(E, H, K), out.device)
+    _lib.call_tag[0] = {"layer": f"H{H}xK{K}", "flops": 2 * E * H * K, "bytes": schnet_dw1_bytes(E, H, K)}
+    call("mvml_schnet_dw1", E, ptr(dists), ldd, ptr(centers), K, float(gamma), ptr(dpre1), H, H, int(accumulate), ptr(out),
+         wp, wn, _stream(out.device))
+    return out
+
+
+def cfconv_agg(g, X, he, transpose=False):
+    """[N, H]: a_v = sum over v's in-slots s of X[src s] * he[s], or (transpose) the gradient of the
+    gathered rows, sum over u's out-edges of X[dst s] * he[s] (mvml_cfconv_agg; he in slot order)."""
+    N, E, H = g.num_nodes(), g.num_edges(), X.shape[1]
+    out = torch.empty((N, H), dtype=torch.float32, device=X.device)
+    rowptr, widx, xidx = (g.out_rowptr, g.out_inslot, nnconv_slot_dst(g)) if transpose else (g.in_rowptr, None, g.in_src)
+    _lib.call_tag[0] = {"layer": f"H{H}", "bytes": cfconv_agg_bytes(N, E, H)}
+    call("mvml_cfconv_agg", N, E, ptr(rowptr), ptr(widx), ptr(xidx), ptr(X), X.stride(0), ptr(he), he.stride(0) if E else H,
+         H, ptr(out), H, _stream(X.device))
+    return out
+
+
+class CFConvLink:
+    """What joins a layer's CFConvAggFunction to its SchNetFilterFunction in the backward: the
+    gradient of he, dA[dst] * hv[src], is never written; the aggregation's backward leaves dA and hv
+    here and mvml_schnet_filter_bwd forms the product as it loads."""
+    dA = hv = None
+
+
+class SchNetFilterFunction(torch.autograd.Function):
+    """he = ssp(ssp(rbf(d) W_1^T + b_1) W_2^T + b_2) [E, H] in in-CSR slot order from the distances
+    (edge-id order), as ONE autograd node with the four parameters as leaves: mvml_schnet_split_w once
+    per call, then mvml_schnet_filter_fwd; the [E, K] expansion does not exist.  link: the CFConvLink
+    shared with the CFConvAggFunction that consumes he; the backward takes dA and hv from it (the
+    gradient autograd hands over for he is a placeholder without storage), runs
+    mvml_schnet_filter_bwd and mvml_schnet_dw1, dW_2 on the k-major GEMM and both bias gradients on
+    mvml_colsum_f32.  Distances and centres get no gradient."""
+
+    @staticmethod
+    def forward(ctx, edge_dists, centers, gamma, W1, b1, W2, b2, g, link):
+        _check_cuda_f32(edge_dists, "edge_dists")
+        for t in (centers, W1, b1, W2, b2):
+            _check_cuda_f32(t, "CFConv parameters")
+        H, K = W1.shape
+        E, dev = g.num_edges(), g.device
+        centers, W1, b1, W2, b2 = _c(centers), _c(W1), _c(b1), _c(W2), _c(b2)
+        if centers.numel() != K:
+            raise ValueError(f"CFConv: {K} centres expected by project_edge, the expansion has {centers.numel()}")
+        image = schnet_image(W1, W2, H, K)
+        d, ldd = schnet_slot_dists(g, edge_dists)
+        s1 = torch.empty((E, H), dtype=torch.float32, device=dev)
+        he = torch.empty((E, H), dtype=torch.float32, device=dev)
+        _lib.call_tag[0] = {"layer": f"H{H}xK{K}", "flops": schnet_filter_flops(E, H, K),
+                            "bytes": schnet_filter_fwd_bytes(E, H, K)}
+        call("mvml_schnet_filter_fwd", E, ptr(d), ldd, ptr(centers), K, float(gamma), H, ptr(image), ptr(b1), ptr(b2),
+             ptr(s1), H, ptr(he), H, _stream(dev))
+        ctx.state = (g, d, ldd, centers, float(gamma), image, link, H, K)
+        ctx.save_for_backward(s1, he)
+        return he
+
+    @staticmethod
+    def backward(ctx, _g_he):
+        g, d, ldd, centers, gamma, image, link, H, K = ctx.state
+        s1, he = ctx.saved_tensors
+        N, E, dev = g.num_nodes(), g.num_edges(), g.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        if link is None or link.dA is None:
+            raise RuntimeError("SchNetFilterFunction: he must be consumed by a CFConvAggFunction that shares its link")
+        dA, hv = link.dA, link.hv
+        link.dA = link.hv = None
+        if E == 0:  # a batch without any bond: no rows, zero gradients
+            return (None, None, None, zeros((H, K), device=dev), zeros(H, device=dev), zeros((H, H), device=dev),
+                    zeros(H, device=dev), None, None)
+        dpre2, dpre1 = torch.empty((E, H), **f32), torch.empty((E, H), **f32)
+        _lib.call_tag[0] = {"layer": f"H{H}", "flops": 2 * E * H * H, "bytes": schnet_filter_bwd_bytes(N, E, H)}
+        call("mvml_schnet_filter_bwd", E, ptr(g.in_src), ptr(nnconv_slot_dst(g)), ptr(dA), dA.stride(0), ptr(hv),
+             hv.stride(0), ptr(s1), H, ptr(he), H, H, K, ptr(image), ptr(dpre2), H, ptr(dpre1), H, _stream(dev))
+        dW2 = torch.empty((H, H), **f32)
+        gemm(dpre2, s1, H, H, E, 1, 1, H, H, dW2, H)  # dpre2^T s1
+        db2, db1 = torch.empty(H, **f32), torch.empty(H, **f32)
+        colsum(dpre2, E, H, H, db2)
+        colsum(dpre1, E, H, H, db1)
+        dW1 = schnet_dw1(d, ldd, centers, gamma, dpre1, E, H, K, torch.empty((H, K), **f32))
+        return None, None, None, dW1, db1, dW2, db2, None, None
+
+
+class CFConvAggFunction(torch.autograd.Function):
+    """a_v = sum_{u -> v} hv[u] * he_s (dgl's u_mul_e, sum) with he [E, H] in slot order
+    (mvml_cfconv_agg).  Backward: dL/dhv by the same kernel over the out-edges; dA and hv go to link
+    for SchNetFilterFunction, and he's gradient is a placeholder without storage (a zero expanded to
+    [E, H]): its rows exist only inside mvml_schnet_filter_bwd.  Without a link he gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, hv, he, g, link):
+        _check_cuda_f32(hv, "node rows")
+        _check_cuda_f32(he, "filter rows")
+        hv, he = _rows_f32(hv), _rows_f32(he)
+        if he.shape[0] != g.num_edges() or he.shape[1] != hv.shape[1] or hv.shape[0] != g.num_nodes():
+            raise ValueError(f"CFConv: hv must be [N = {g.num_nodes()}, H] and he [E = {g.num_edges()}, H] "
+                             f"(got {tuple(hv.shape)}, {tuple(he.shape)})")
+        ctx.state = (g, hv, he, link)
+        return cfconv_agg(g, hv, he)
+
+    @staticmethod
+    def backward(ctx, g_a):
+        g, hv, he, link = ctx.state
+        dA = _rows_f32(g_a)
+        d_hv = cfconv_agg(g, dA, he, transpose=True)
+        if link is None:
+            return d_hv, None, None, None
+        link.dA, link.hv = dA, hv
+        return d_hv, dA.new_zeros(()).expand(he.shape), None, None
+
+
+class LinearSSPFunction(torch.autograd.Function):
+    """ssp(x W^T + b), ssp = softplus - ln 2: the GEMM with its bias epilogue, mvml_ssp_fwd in place;
+    the backward takes ssp' from the output (mvml_ssp_bwd) and runs the Linear's three products."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        _check_cuda_f32(x, "x")
+        x, weight, y, ctx.lm = linear_forward(x, weight, bias)
+        call("mvml_ssp_fwd", y.numel(), ptr(y), ptr(y), _stream(y.device))
+        ctx.save_for_backward(x, weight, y)
+        return y
+
+    @staticmethod
+    def backward(ctx, g_y):
+        x, weight, y = ctx.saved_tensors
+        g_pre = torch.empty_like(y)
+        call("mvml_ssp_bwd", y.numel(), ptr(y), ptr(_c(g_y)), ptr(g_pre), _stream(y.device))
+        return linear_backward(x, weight, g_pre, ctx.lm, need_gx=ctx.needs_input_grad[0])
+
+
+class SSPFunction(torch.autograd.Function):
+    """ssp(x) = softplus(x) - ln 2 element-wise (mvml_ssp_fwd / mvml_ssp_bwd, the backward from the output)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        _check_cuda_f32(x, "x")
+        y = torch.empty_like(_c(x))
+        call("mvml_ssp_fwd", y.numel(), ptr(_c(x)), ptr(y), _stream(y.device))
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, g_y):
+        (y,) = ctx.saved_tensors
+        g_x = torch.empty_like(y)
+        call("mvml_ssp_bwd", y.numel(), ptr(y), ptr(_c(g_y)), ptr(g_x), _stream(y.device))
+        return g_x
+
+
+class NodeReadoutFunction(torch.autograd.Function):
+    """The per-molecule pool of (h W^T + b) [N, T] for any T >= 1 (MLPNodeReadout's out_project, T =
+    n_tasks): mvml_segment_pool_* walks float4 columns, so W and b are zero-padded to a multiple of 4
+    rows for the GEMM and the pool, and the [B, T] block is copied out (mvml_copy_cols)."""
+
+    @staticmethod
+    def forward(ctx, h, weight, bias, g, mode):
+        _check_cuda_f32(h, "node rows")
+        T, K = weight.shape
+        Tp, dev = _round4(T), h.device
+        Wp, bp = zeros((Tp, K), device=dev), zeros(Tp, device=dev)
+        copy2d(Wp[:T], _c(weight))
+        copy2d(bp[:T], _c(bias))
+        h, Wp, rows, lm = linear_forward(h, Wp, bp)
+        ctx.pool = _StageCtx()
+        pooled = SegmentPoolFunction.forward(ctx.pool, rows, g, mode)
+        ctx.state = (h, Wp, lm, T)
+        return _dense(pooled[:, :T])
+
+    @staticmethod
+    def backward(ctx, g_out):
+        h, Wp, lm, T = ctx.state
+        Gp = zeros((g_out.shape[0], Wp.shape[0]), device=h.device)
+        copy2d(Gp[:, :T], _c(g_out))
+        g_rows = SegmentPoolFunction.backward(ctx.pool, Gp)[0]
+        gx, gWp, gbp = linear_backward(h, Wp, g_rows, lm, need_gx=ctx.needs_input_grad[0])
+        return gx, _dense(gWp[:T]), _dense(gbp[:T]), None, None

@@ -1410,3 +1410,168 @@ class DMPNNPredictor(nn.Module):
         from .fusion import LinearFunction
         hidden = Fn.LinearReLUFunction.apply(graph_feats, self.predict[0].weight, self.predict[0].bias)
         return LinearFunction.apply(hidden, self.predict[2].weight, self.predict[2].bias)
+
+
+class ShiftedSoftplus(nn.Module):
+    """ssp(x) = softplus(x) - ln 2 (dgl's ShiftedSoftplus with beta 1, threshold 20) on mvml_ssp_fwd /
+    mvml_ssp_bwd; the backward takes the derivative from the output."""
+
+    def forward(self, x):
+        return Fn.SSPFunction.apply(x)
+
+
+class RBFExpansion(nn.Module):
+    """dgllife's RBFExpansion (restated): K = ceil((high - low) / gap) centres linspace(low, high, K)
+    in float32 (the non-trainable buffer `centers`) and gamma = 1 / gap.  The expansion
+    exp(-gamma (d - mu_k)^2) is never materialised on the HIP path: CFConv reads `centers` and
+    `gamma` and its kernels generate the values in registers, so forward() is refused."""
+
+    def __init__(self, low=0., high=30., gap=0.1):
+        super().__init__()
+        if low != 0.:
+            raise ValueError(f"RBFExpansion: low must be 0 on the HIP path (got {low})")
+        K = Fn.schnet_num_centers(high - low, gap)
+        self.gamma = 1 / gap
+        self.register_buffer("centers", torch.linspace(low, high, K, dtype=torch.float32))
+
+    def reset_parameters(self):
+        pass
+
+    def forward(self, edge_dists):
+        raise NotImplementedError("RBFExpansion: the [E, K] expansion is never materialised on the HIP path; pass this "
+                                  "module to CFConv(g, node_feats, edge_dists, rbf), which generates it in its kernels")
+
+
+class CFConv(nn.Module):
+    """dgl 0.9.1 CFConv as dgllife's SchNet uses it (restated, parity unpinned): project_edge =
+    Sequential(Linear(K, H), ssp, Linear(H, H), ssp) on the radial-basis expansion of the distances,
+    project_node = Linear(node_in_feats, H), a_v = sum_{u -> v} hv[u] * he, project_out =
+    Sequential(Linear(H, out_feats), ssp).  forward(g, node_feats, edge_dists, rbf): edge_dists a float
+    [E] or [E, 1] tensor in edge-id order, rbf the RBFExpansion whose centres and gamma the fused
+    filter kernels read (Fn.SchNetFilterFunction, Fn.CFConvAggFunction; csrc/schnet.hip)."""
+
+    def __init__(self, node_in_feats, edge_in_feats, hidden_feats, out_feats):
+        super().__init__()
+        Fn.schnet_check("CFConv", F=node_in_feats, H=hidden_feats)
+        Fn.schnet_check("CFConv", F=out_feats)
+        if not isinstance(edge_in_feats, int) or not 1 <= edge_in_feats <= Fn.SCHNET_MAX_K:
+            raise ValueError(f"CFConv: edge_in_feats (the centre count) must be in [1, {Fn.SCHNET_MAX_K}] on the HIP path "
+                             f"(got {edge_in_feats})")
+        self.project_edge = nn.Sequential(nn.Linear(edge_in_feats, hidden_feats), ShiftedSoftplus(),
+                                          nn.Linear(hidden_feats, hidden_feats), ShiftedSoftplus())
+        self.project_node = nn.Linear(node_in_feats, hidden_feats)
+        self.project_out = nn.Sequential(nn.Linear(hidden_feats, out_feats), ShiftedSoftplus())
+
+    def reset_parameters(self):
+        for lin in (self.project_edge[0], self.project_edge[2], self.project_node, self.project_out[0]):
+            lin.reset_parameters()
+
+    _check_graph = GATConv._check_graph
+    _allow_zero_in_degree = True  # (an atom without in-edges sums nothing: a_v = 0)
+
+    def forward(self, g, node_feats, edge_dists, rbf):
+        self._check_graph(g)
+        from .fusion import LinearFunction
+        hv = LinearFunction.apply(node_feats, self.project_node.weight, self.project_node.bias)
+        link = Fn.CFConvLink()
+        e0, e2 = self.project_edge[0], self.project_edge[2]
+        he = Fn.SchNetFilterFunction.apply(edge_dists, rbf.centers, rbf.gamma, e0.weight, e0.bias, e2.weight, e2.bias, g,
+                                           link)
+        a = Fn.CFConvAggFunction.apply(hv, he, g, link)
+        return Fn.LinearSSPFunction.apply(a, self.project_out[0].weight, self.project_out[0].bias)
+
+
+class Interaction(nn.Module):
+    """dgllife's SchNet Interaction (restated): conv = CFConv(node_feats, K, hidden_feats, node_feats),
+    then project_out = Linear(node_feats, node_feats); no residual."""
+
+    def __init__(self, node_feats, edge_in_feats, hidden_feats):
+        super().__init__()
+        self.conv = CFConv(node_feats, edge_in_feats, hidden_feats, node_feats)
+        self.project_out = nn.Linear(node_feats, node_feats)
+
+    def reset_parameters(self):
+        self.conv.reset_parameters()
+        self.project_out.reset_parameters()
+
+    def forward(self, g, node_feats, edge_dists, rbf):
+        from .fusion import LinearFunction
+        return LinearFunction.apply(self.conv(g, node_feats, edge_dists, rbf), self.project_out.weight, self.project_out.bias)
+
+
+class SchNetGNN(nn.Module):
+    """dgllife.model.gnn.schnet.SchNetGNN (0.3.0; restated, parity with dgllife is unpinned): embed =
+    Embedding(num_node_types, node_feats) (Fn.EmbedSumFunction with one table), rbf = RBFExpansion(0,
+    cutoff, gap), gnn_layers = one Interaction per entry of hidden_feats (default [64, 64, 64]).
+    forward(g, node_types, edge_dists): node_types int32 [N], edge_dists float [E] or [E, 1] in edge-id
+    order; returns (N, node_feats).  Refused at construction: a hidden width that is no multiple of 16
+    in [16, 128], node_feats no multiple of 4 or above 1024, more than 512 centres, gap or cutoff <= 0,
+    more than 128 node types."""
+
+    def __init__(self, node_feats=64, hidden_feats=None, num_node_types=100, cutoff=30., gap=0.1):
+        super().__init__()
+        if hidden_feats is None:
+            hidden_feats = [64, 64, 64]
+        K = Fn.schnet_num_centers(cutoff, gap)
+        if not isinstance(num_node_types, int) or not 1 <= num_node_types <= Fn.EMBED_MAX_ROWS:
+            raise ValueError(f"SchNetGNN: num_node_types must be in [1, {Fn.EMBED_MAX_ROWS}] on the HIP path "
+                             f"(got {num_node_types})")
+        Fn.schnet_check("SchNetGNN", F=node_feats)
+        for H in hidden_feats:
+            Fn.schnet_check("SchNetGNN", H=H)
+        self.embed = nn.Embedding(num_node_types, node_feats)
+        self.rbf = RBFExpansion(high=cutoff, gap=gap)
+        self.gnn_layers = nn.ModuleList(Interaction(node_feats, K, H) for H in hidden_feats)
+
+    def reset_parameters(self):
+        self.embed.reset_parameters()
+        for layer in self.gnn_layers:
+            layer.reset_parameters()
+
+    def forward(self, g, node_types, edge_dists):
+        x = Fn.EmbedSumFunction.apply([node_types], self.embed.weight)
+        for layer in self.gnn_layers:
+            x = layer(g, x, edge_dists, self.rbf)
+        return x
+
+
+class MLPNodeReadout(nn.Module):
+    """dgllife's MLPNodeReadout (restated): out_project(activation(in_project(node_feats))) per atom,
+    then the per-molecule 'sum', 'mean' or 'max' (Fn.NodeReadoutFunction).  activation: None or a
+    ShiftedSoftplus (fused into in_project's node); forward(g, node_feats) -> (B, graph_feats)."""
+
+    def __init__(self, node_feats, hidden_feats, graph_feats, activation=None, mode="sum"):
+        super().__init__()
+        if mode not in Fn.POOL_MODES:
+            raise ValueError(f"Expect mode to be 'max' or 'mean' or 'sum', got {mode}")
+        if activation is not None and not isinstance(activation, ShiftedSoftplus):
+            raise ValueError("MLPNodeReadout: activation must be None or a ShiftedSoftplus on the HIP path")
+        self.mode, self.activation = mode, activation
+        self.in_project = nn.Linear(node_feats, hidden_feats)
+        self.out_project = nn.Linear(hidden_feats, graph_feats)
+
+    def forward(self, g, node_feats):
+        from .fusion import LinearFunction
+        fn = LinearFunction if self.activation is None else Fn.LinearSSPFunction
+        h = fn.apply(node_feats, self.in_project.weight, self.in_project.bias)
+        return Fn.NodeReadoutFunction.apply(h, self.out_project.weight, self.out_project.bias, g, self.mode)
+
+
+class SchNetPredictor(nn.Module):
+    """dgllife.model.model_zoo.schnet_predictor.SchNetPredictor (0.3.0; restated, parity with dgllife
+    is unpinned): gnn = SchNetGNN(...) -> readout = MLPNodeReadout(node_feats, predictor_hidden_feats,
+    n_tasks, ShiftedSoftplus()), summed per molecule.  classifier_hidden_feats is the deprecated alias
+    of predictor_hidden_feats, as in dgllife.  forward(g, node_types, edge_dists) returns (B, n_tasks)."""
+
+    def __init__(self, node_feats=64, hidden_feats=None, classifier_hidden_feats=64, n_tasks=1, num_node_types=100,
+                 cutoff=30., gap=0.1, predictor_hidden_feats=64):
+        super().__init__()
+        if predictor_hidden_feats == 64 and classifier_hidden_feats != 64:
+            print("classifier_hidden_feats is deprecated and will be removed in the future, use "
+                  "predictor_hidden_feats instead")
+            predictor_hidden_feats = classifier_hidden_feats
+        self.gnn = SchNetGNN(node_feats, hidden_feats, num_node_types, cutoff, gap)
+        self.readout = MLPNodeReadout(node_feats, predictor_hidden_feats, n_tasks, activation=ShiftedSoftplus())
+
+    def forward(self, g, node_types, edge_dists):
+        return self.readout(g, self.gnn(g, node_types, edge_dists))
