@@ -490,6 +490,74 @@ int mvml_gat_agg_bwd_res(int64_t num_nodes, const int32_t* node_groups, int64_t 
                          const float* g_out, int H, int F, float slope, int mode, float* gY,
                          int64_t ldgy, int64_t elr_col, float* gR, int64_t ldgr, uint32_t* gy_amax,
                          uint32_t* gy_row_amax, void* workspace, size_t workspace_bytes, void* stream);
+/* ---------------------------------------------------------------------------------------
+ * Class map of the atom-feature rows, and the aggregation over a row-mapped projection.
+ * The first GAT layer's input rows are featurizer vectors (one-hot blocks and a few small
+ * integers): a 1.75 M-atom batch holds a few hundred distinct ones.  mvml_feat_classes numbers
+ * them; the layer then projects one row per class, and the *_map entries below read atom a's
+ * projection row at Y + yrow[a] * ldy (yrow = cls), a table that stays in L2, instead of an
+ * [N, ldy] matrix in HBM.
+ *
+ * mvml_feat_classes: X [N, ldx] (ldx a multiple of 4, <= MVML_FEAT_CLASS_MAX_LD, 16-byte aligned).
+ * Two rows are one class iff all ldx floats are bit-identical (whole rows are compared: 0.0 and
+ * -0.0 differ, pad columns count).  Classes are numbered by first occurrence (the smallest atom
+ * index of the class), so the result does not depend on scheduling.  Writes
+ *   cls[N] (int32), Xc[c] = the row of class c for c < min(C, MVML_MAX_FEAT_CLASSES)  (Xc holds
+ *   MVML_MAX_FEAT_CLASSES rows of ldx floats), *count = C on the device.
+ * More than MVML_MAX_FEAT_CLASSES classes: *count = MVML_MAX_FEAT_CLASSES + 1 and cls is all
+ * zeros (the caller then keeps no map).  Integer atomics only; no host synchronisation.
+ * workspace: mvml_feat_classes_workspace_size() bytes. */
+#define MVML_MAX_FEAT_CLASSES 1024
+#define MVML_FEAT_CLASS_MAX_LD 80
+size_t mvml_feat_classes_workspace_size(void);
+int mvml_feat_classes(int64_t num_rows, const float* X, int64_t ldx, int32_t* cls, float* Xc,
+                      int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
+/* Row gather: dst[r, :cols] = src[idx[r], :cols] for r < rows.
+ * Rows of cols floats at strides lds, ldd >= cols; idx[r] must be a row of src.
+ * Moves 16-byte pieces where cols, both strides and both pointers allow it, single floats else.
+ * Used for the elr rows of a row-mapped projection (its last 2H columns through cls) and for
+ * materialising the whole projection. */
+int mvml_gather_rows(int64_t rows, int cols, const float* src, int64_t lds, const int32_t* idx,
+                     float* dst, int64_t ldd, void* stream);
+/* mvml_gat_agg_fwd / _fwd_res / _bwd / _bwd_res over a row-mapped projection: the same arguments
+ * plus yrow [N] (int32; ldy * MVML_MAX_FEAT_CLASSES floats must stay below 2 GiB): atom a's
+ * projection row — the source rows gathered per in-edge and
+ * out-edge and the atom's own residual columns — is Y + yrow[a] * ldy.  elr, out, attn, gY stay
+ * per atom.  The MAP instances of the same kernel templates: with Y[a] == table[yrow[a]] the
+ * results are bitwise those of the plain entries.  Honoured by every kernel path of the
+ * projection-row layout with a bias (destination wave, molecule and big windows, gather kernel,
+ * per-atom pair, both source-atom backwards).  A residual apart from Y's rows, none, or no bias
+ * (the separate-residual instances) is refused: MVML_ERR_INVALID before any launch, nothing
+ * written — the caller materialises Y (mvml_gather_rows) and calls the plain entry.
+ * The caller guarantees 0 <= yrow[a] < the rows Y really holds (at most MVML_MAX_FEAT_CLASSES).
+ * Nothing checks it: the window kernels address Y through a buffer resource that spans
+ * MVML_MAX_FEAT_CLASSES rows whatever Y's allocation, so a larger yrow[a] reads past the table. */
+int mvml_gat_agg_fwd_map(int64_t num_nodes, const int32_t* node_groups, int64_t num_groups,
+                         const int32_t* in_rowptr, const int32_t* in_src, const float* Y, int64_t ldy,
+                         int H, int F, const float* elr, const float* bias, float slope, int mode,
+                         float* out, float* attn, uint32_t* out_amax, uint32_t* out_row_amax,
+                         void* stream, const int32_t* yrow);
+int mvml_gat_agg_fwd_res_map(int64_t num_nodes, const int32_t* node_groups, int64_t num_groups,
+                             const int32_t* in_rowptr, const int32_t* in_src, const float* Y,
+                             int64_t ldy, int H, int F, const float* elr, const float* R, int64_t ldr,
+                             const float* bias, float slope, int mode, float* out, float* attn,
+                             uint32_t* out_amax, uint32_t* out_row_amax, void* stream,
+                             const int32_t* yrow);
+int mvml_gat_agg_bwd_map(int64_t num_nodes, const int32_t* node_groups, int64_t num_groups,
+                         const int32_t* in_rowptr, const int32_t* in_src, const int32_t* out_rowptr,
+                         const int32_t* out_dst, const int32_t* out_inslot, const float* Y,
+                         int64_t ldy, const float* elr, const float* attn, const float* out,
+                         const float* g_out, int H, int F, float slope, int mode, float* gY,
+                         int64_t ldgy, uint32_t* gy_amax, uint32_t* gy_row_amax, void* workspace,
+                         size_t workspace_bytes, void* stream, const int32_t* yrow);
+int mvml_gat_agg_bwd_res_map(int64_t num_nodes, const int32_t* node_groups, int64_t num_groups,
+                             const int32_t* in_rowptr, const int32_t* in_src, const int32_t* out_rowptr,
+                             const int32_t* out_dst, const int32_t* out_inslot, const float* Y,
+                             int64_t ldy, const float* elr, const float* attn, const float* out,
+                             const float* g_out, int H, int F, float slope, int mode, float* gY,
+                             int64_t ldgy, int64_t elr_col, float* gR, int64_t ldgr, uint32_t* gy_amax,
+                             uint32_t* gy_row_amax, void* workspace, size_t workspace_bytes, void* stream,
+                             const int32_t* yrow);
 /* (Projected residual with a bias only: the identity / absent residual and bias=False layers of
  * mvml_gat_agg_fwd_res run their backward through mvml_gat.functional.GATLayerFunction or the
  * separate entry points; extending this entry to them is not done.)

@@ -71,7 +71,7 @@ __device__ __forceinline__ float grp_sum_hi(float v) {
 // empty resource when it is not formed: the stores are dropped) and stays out of the |max|
 // bookkeeping, which then covers gY's columns only.
 template <int H, int MODE, int NPA, int CW, int NT = 16 * CW, int WIN = kWinL, int ECAP = kECap,
-          bool BIG = false, bool SEP = false>
+          bool BIG = false, bool SEP = false, bool MAP = false>
 __device__ __forceinline__ float bwd_lds_chunks(
     float4* zs, float4* gs, const float* s_att, const int* s_odst, const int* s_oslot,
     const int* s_orp, const int* s_rp, const uint16_t* s_src, float* s_ga,
@@ -81,7 +81,8 @@ __device__ __forceinline__ float bwd_lds_chunks(
     const uint32_t* s_segI = nullptr, int nsegI = 0, const uint32_t* s_segO = nullptr,
     int nsegO = 0, const int* s_rs = nullptr, float4* s_part = nullptr,
     const uint32_t* s_oxe = nullptr, const uint16_t* s_oxb = nullptr, float* s_rmx = nullptr,
-    __amdgpu_buffer_rsrc_t rR = __amdgpu_buffer_rsrc_t(), int ldri = 0) {
+    __amdgpu_buffer_rsrc_t rR = __amdgpu_buffer_rsrc_t(), int ldri = 0,
+    const int32_t* __restrict__ ymap = nullptr) {
   static_assert(kEC == 5, "in-edge writer lanes assume 5 cached in-edges");
   constexpr int LPD = CW / 4, DPP = NT / LPD;
   auto odst = [&](int o) -> int { if constexpr (BIG) return g_odst[e0 + o] - a0; else return s_odst[o]; };
@@ -90,13 +91,23 @@ __device__ __forceinline__ float bwd_lds_chunks(
   const int HF = H * F, nfc = F / CW, nch = H * nfc;
   const int ocols = MODE == 1 ? F : HF;
   // row byte offsets (recomputed where used: registers are the constraint at NPA = 2)
-  auto yrow = [&](int p) { return 4u * (uint32_t)((ds + DPP * p) * ldyi); };
+  // (MAP: rY spans the whole row table and the rows come through ymap, kept in registers)
+  uint32_t yb[MAP ? NPA : 1];
+  if constexpr (MAP) {
+#pragma unroll
+    for (int p = 0; p < NPA; ++p)
+      yb[p] = ds + DPP * p < nr ? 4u * (uint32_t)(ymap[a0 + ds + DPP * p] * ldyi) : 4u * (uint32_t)(kMaxFeatClasses * ldyi);
+  }
+  auto yrow = [&](int p) {
+    if constexpr (MAP) return yb[p];
+    else return 4u * (uint32_t)((ds + DPP * p) * ldyi);
+  };
   auto grow = [&](int p) { return 4u * (uint32_t)((ds + DPP * p) * ldgi); };
   auto gorow = [&](int p) { return 4u * (uint32_t)((ds + DPP * p) * ocols); };
   auto orow = [&](int p) { return 4u * (uint32_t)((ds + DPP * p) * HF); };
   // "no access" offsets just past each resource (see fwd_lds_chunks): every load and store is
   // unconditional, so the compiler's vmcnt counts are exact
-  const uint32_t noY = 4u * (uint32_t)(nr * ldyi), noGo = 4u * (uint32_t)(nr * ocols);
+  const uint32_t noY = 4u * (uint32_t)((MAP ? kMaxFeatClasses : nr) * ldyi), noGo = 4u * (uint32_t)(nr * ocols);
   const uint32_t noO = 4u * (uint32_t)(nr * HF), noG = 4u * (uint32_t)(nr * ldgi);
   auto rrow = [&](int p) { return 4u * (uint32_t)((ds + DPP * p) * ldri); };  // SEP: dR rows
   const uint32_t noR = 4u * (uint32_t)(nr * ldri);
@@ -342,7 +353,7 @@ __device__ __forceinline__ float bwd_lds_chunks(
 // (LDS holds the rows, the attention, the edge gradients and the in-CSR), one workgroup per CU
 // walking the list.
 template <int H, int MODE, int CW, int NT = 16 * CW, int WIN = kWinL, int ECAP = kECap, bool BIG = false,
-          bool SEP = false>
+          bool SEP = false, bool MAP = false>
 __global__ void __launch_bounds__(NT, kBwdWaves)
 gat_agg_bwd_lds_kernel(const int32_t* __restrict__ plan, int64_t G, const int32_t* __restrict__ rowptr,
                        const int32_t* __restrict__ in_src, const int32_t* __restrict__ out_rowptr,
@@ -352,7 +363,7 @@ gat_agg_bwd_lds_kernel(const int32_t* __restrict__ plan, int64_t G, const int32_
                        const float* __restrict__ g_out, float slope, float* __restrict__ gY,
                        int64_t ldgy, int C, uint32_t* __restrict__ gy_amax,
                        uint32_t* __restrict__ gy_rows, float* __restrict__ gR = nullptr,
-                       int64_t ldgr = 0) {
+                       int64_t ldgr = 0, const int32_t* __restrict__ ymap = nullptr) {
   constexpr int LPD = CW / 4;
   constexpr int DPP = NT / LPD;
   constexpr int NPM = WIN / DPP;  // passes over a full window
@@ -413,7 +424,8 @@ gat_agg_bwd_lds_kernel(const int32_t* __restrict__ plan, int64_t G, const int32_
     if constexpr (BIG) return s_elr_b[r * 2 * H + c]; else return s_elr[r * 2 * H + c];
   };
   const int ldyi = (int)ldy, ldgi = (int)ldgy;
-  const __amdgpu_buffer_rsrc_t rY = make_rsrc(Y + (int64_t)a0 * ldy, (uint32_t)(nr * ldyi) * 4u);
+  const __amdgpu_buffer_rsrc_t rY = MAP ? make_rsrc(Y, (uint32_t)(kMaxFeatClasses * ldyi) * 4u)
+                                        : make_rsrc(Y + (int64_t)a0 * ldy, (uint32_t)(nr * ldyi) * 4u);
   const __amdgpu_buffer_rsrc_t rG = make_rsrc(gY + (int64_t)a0 * ldgy, (uint32_t)(nr * ldgi) * 4u);
   const __amdgpu_buffer_rsrc_t rGo = make_rsrc(g_out + (int64_t)a0 * ocols, (uint32_t)(nr * ocols) * 4u);
   const __amdgpu_buffer_rsrc_t rO = make_rsrc(out + (int64_t)a0 * HF, MODE == 0 ? (uint32_t)(nr * HF) * 4u : 0u);
@@ -449,10 +461,10 @@ gat_agg_bwd_lds_kernel(const int32_t* __restrict__ plan, int64_t G, const int32_
   // (a macro, not a lambda: through a generic lambda every instance of this kernel compiled to
   // other machine code — DESIGN.md, "Aggregation source layout")
 #define MVML_BWD_CHUNKS(NPA)                                                                       \
-  gmx = fmaxf(gmx, bwd_lds_chunks<H, MODE, NPA, CW, NT, WIN, ECAP, BIG, SEP>(zs, gs, s_att, s_odst, s_oslot, s_orp, s_rp,  \
+  gmx = fmaxf(gmx, bwd_lds_chunks<H, MODE, NPA, CW, NT, WIN, ECAP, BIG, SEP, MAP>(zs, gs, s_att, s_odst, s_oslot, s_orp, s_rp,  \
                                                        s_src, s_ga, rY, ldyi, rGo, rO, rG, ldgi, nr, F, \
                                                        out_dst, out_inslot, e0, a0, s_segI, nsegI, \
-                                                       s_segO, nsegO, s_rs, s_part, s_oxe, s_oxb, s_rmx, rR, ldri))
+                                                       s_segO, nsegO, s_rs, s_part, s_oxe, s_oxb, s_rmx, rR, ldri, ymap))
   if (nr <= DPP) MVML_BWD_CHUNKS(1);
   else if (NPM == 2 || nr <= 2 * DPP) MVML_BWD_CHUNKS(2);
   else if (nr <= 3 * DPP) MVML_BWD_CHUNKS((NPM > 2 ? 3 : 2));
@@ -504,7 +516,7 @@ gat_agg_bwd_lds_kernel(const int32_t* __restrict__ plan, int64_t G, const int32_
 }
 
 // Pass A: one wave per destination v.
-template <int H, int VPL>
+template <int H, int VPL, bool MAP = false>
 __global__ void __launch_bounds__(kWavesPerBlock * 64)
 gat_agg_bwd_dst_kernel(int64_t N, const int32_t* __restrict__ groups, int64_t G,
                        const int32_t* __restrict__ rowptr, const int32_t* __restrict__ in_src,
@@ -514,7 +526,7 @@ gat_agg_bwd_dst_kernel(int64_t N, const int32_t* __restrict__ groups, int64_t G,
                        float* __restrict__ gpre, float* __restrict__ gY, int64_t ldgy,
                        float* __restrict__ gelr, int64_t ldgl, int skip_big,
                        uint32_t* __restrict__ gy_amax, uint32_t* __restrict__ gy_rows,
-                       float* gR, int64_t ldgr, int ramax) {
+                       float* gR, int64_t ldgr, int ramax, const int32_t* __restrict__ ymap = nullptr) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   float gmx = 0.f;  // |max| of this thread's gY stores (block-uniform early returns only)
   // G > 0: one block per backward fallback group of the plan; G == 0: one wave per atom over
@@ -579,7 +591,7 @@ gat_agg_bwd_dst_kernel(int64_t N, const int32_t* __restrict__ groups, int64_t G,
   float ga_l[H], a_l[H];
   for (int base = 0; base < deg; base += 64) {
     const int cnt = min(64, deg - base);
-    const int u_l = (base + lane < deg) ? in_src[beg + base + lane] : 0;
+    const int u_l = (base + lane < deg) ? yrow_of<MAP>(ymap, in_src[beg + base + lane]) : 0;  // projection row
 #pragma unroll
     for (int h = 0; h < H; ++h) ga_l[h] = 0.f;
     for (int j = 0; j < cnt; j += 2) {  // two source rows in flight
@@ -783,14 +795,15 @@ gat_agg_bwd_src_kernel(int64_t N, const int32_t* __restrict__ groups, int64_t G,
 // the atomwise dZ; g_a is written per edge (one writer: the edge's source) for the softmax pass.
 // (ld4nt / st4nt: the projection rows read once and the dZ rows written once pass through
 // without displacing the g_out rows the XCD's waves share in L2)
-template <int H, int NJ>
+template <int H, int NJ, bool MAP = false>
 __global__ void __launch_bounds__(256)
 gat_mean_bwd_src_kernel(int64_t N, const int32_t* __restrict__ out_rowptr,
                         const int32_t* __restrict__ out_dst, const int32_t* __restrict__ out_inslot,
                         const float* __restrict__ Y, int64_t ldy, const float* __restrict__ attn,
                         const float* __restrict__ g_out, int F, float* __restrict__ ga,
                         float* __restrict__ gY, int64_t ldgy, uint32_t* __restrict__ gy_amax,
-                        uint32_t* __restrict__ gy_rows, float* gR, int64_t ldgr, int ramax) {
+                        uint32_t* __restrict__ gy_rows, float* gR, int64_t ldgr, int ramax,
+                        const int32_t* __restrict__ ymap = nullptr) {
   const int lane = threadIdx.x & 63;
   const int64_t u = xcd_block(blockIdx.x, gridDim.x) * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   float gmx = 0.f;
@@ -800,7 +813,7 @@ gat_mean_bwd_src_kernel(int64_t N, const int32_t* __restrict__ out_rowptr,
     const float hh = (float)H;
     bool okj[NJ];
     float4 z[H][NJ], dz[H][NJ];
-    const float* zu = Y + u * ldy;
+    const float* zu = Y + (int64_t)yrow_of<MAP>(ymap, u) * ldy;
     float* gyu = gY + u * ldgy;
     float rmx = 0.f;
 #pragma unroll
@@ -950,7 +963,7 @@ gat_mean_bwd_gel_kernel(int64_t N, const int32_t* __restrict__ out_rowptr,
 // in registers with the same arithmetic, then dZ[u] += a_e g_rst[w] (out-CSR order) and
 // g_a[e] = <Z[u], g_rst[w]> per head.  (Round 4 had a two-pass form — every g_rst row written
 // first, then gathered — with the same bits; measured slower, deleted in round 5.)
-template <int H, int NJ, int MODE, int U = 2>
+template <int H, int NJ, int MODE, int U = 2, bool MAP = false>
 __global__ void __launch_bounds__(256)
 gat_flat_bwd_src1_kernel(int64_t N, const int32_t* __restrict__ out_rowptr,
                          const int32_t* __restrict__ out_dst, const int32_t* __restrict__ out_inslot,
@@ -958,12 +971,13 @@ gat_flat_bwd_src1_kernel(int64_t N, const int32_t* __restrict__ out_rowptr,
                          const float* __restrict__ out, const float* __restrict__ g_out, int F,
                          float* __restrict__ ga, float* __restrict__ gY, int64_t ldgy,
                          uint32_t* __restrict__ gy_amax, uint32_t* __restrict__ gy_rows,
-                         float* gR, int64_t ldgr, int ramax) {
+                         float* gR, int64_t ldgr, int ramax, const int32_t* __restrict__ ymap = nullptr) {
   const int lane = threadIdx.x & 63;
   const int64_t u = xcd_block(blockIdx.x, gridDim.x) * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   float gmx = 0.f;
   if (u < N) {  // (no early return: block_amax_commit below has a barrier)
     const int HF = H * F;
+    const float* zu = Y + (int64_t)yrow_of<MAP>(ymap, u) * ldy;
     bool okc[NJ];
     int hc[NJ];
     float4 z[NJ], dz[NJ];
@@ -985,7 +999,7 @@ gat_flat_bwd_src1_kernel(int64_t N, const int32_t* __restrict__ out_rowptr,
       const int col = 4 * (lane + 64 * c);
       okc[c] = col < HF;
       hc[c] = okc[c] ? col / F : 0;
-      z[c] = okc[c] ? ld4nt(Y + u * ldy + col) : f4(0.f);
+      z[c] = okc[c] ? ld4nt(zu + col) : f4(0.f);
       dz[c] = f4(0.f);
       if (okc[c] && gR) {  // dR[u] = g_rst[u] (gat_agg_bwd_dst_kernel: gR / ramax)
         const float4 g = grst(u, c);
@@ -1067,6 +1081,7 @@ struct BwdArgs {
   int64_t ldgr;
   int ramax;
   hipStream_t st;
+  const int32_t* ymap;  // the MAP instances' row map (mvml_gat_agg_bwd_map; NULL: atom rows)
   // with per-row maxima requested, max |gY| comes from them at the end (no per-block atomics)
   uint32_t* blk_amax() const { return gy_rows ? nullptr : gy_amax; }
 };
@@ -1088,14 +1103,14 @@ int finish_src_bwd(const BwdArgs& a) {
 }
 
 // Flatten layer by source atom, one pass, one out-neighbour row per trip.
-template <int H>
+template <int H, bool MAP>
 int launch_flat_src1(const BwdArgs& a) {
   const int rc = switch_const<1, 2, 3, 4, 5, 6, 7, 8>((int)ceil_div(H * a.F / 4, 64), [&](auto nj) {
     return switch_const<0, 2>(a.mode, [&](auto m) {
-      gat_flat_bwd_src1_kernel<H, decltype(nj)::value, decltype(m)::value, 1>
+      gat_flat_bwd_src1_kernel<H, decltype(nj)::value, decltype(m)::value, 1, MAP>
           <<<(unsigned)ceil_div(a.N, 4), 256, 0, a.st>>>(a.N, a.orp, a.odst, a.oslot, a.Y, a.ldy, a.attn, a.out,
                                                          a.g_out, a.F, a.gpre, a.gY, a.ldgy, a.blk_amax(),
-                                                         a.gy_rows, a.gR, a.ldgr, a.ramax);
+                                                         a.gy_rows, a.gR, a.ldgr, a.ramax, a.ymap);
       return check_launch("gat_flat_bwd_src1_kernel");
     });
   });
@@ -1108,16 +1123,16 @@ int launch_flat_src1(const BwdArgs& a) {
 
 // Head-mean layer by source atom.  wide (mvml_gat_agg_bwd_res with dR apart from gY): F > 1024,
 // which only H = 1 reaches, takes an 8-slot instance, so that this path holds every shape there.
-template <int H>
+template <int H, bool MAP>
 int launch_mean_src(const BwdArgs& a, bool wide) {
   const int nj = (int)ceil_div(a.F / 4, 64);
   const int rc = switch_const<1, 2, 3, 4, 8>(nj <= 4 ? nj : wide ? 8 : 0, [&](auto s) {
     constexpr int NJ = decltype(s)::value;
     if constexpr (NJ == 8 && H != 1) return kNoCase;
     else {
-      gat_mean_bwd_src_kernel<H, NJ><<<(unsigned)ceil_div(a.N, 4), 256, 0, a.st>>>(
+      gat_mean_bwd_src_kernel<H, NJ, MAP><<<(unsigned)ceil_div(a.N, 4), 256, 0, a.st>>>(
           a.N, a.orp, a.odst, a.oslot, a.Y, a.ldy, a.attn, a.g_out, a.F, a.gpre, a.gY, a.ldgy, a.blk_amax(),
-          a.gy_rows, a.gR, a.ldgr, a.ramax);
+          a.gy_rows, a.gR, a.ldgr, a.ramax, a.ymap);
       return check_launch("gat_mean_bwd_src_kernel");
     }
   });
@@ -1133,16 +1148,16 @@ template <typename Kernel>
 void launch_lds_bwd(Kernel kernel, unsigned blocks, unsigned threads, const BwdArgs& a, float* gR, int64_t ldgr) {
   kernel<<<blocks, threads, 0, a.st>>>(a.groups, a.G, a.rp, a.src, a.orp, a.odst, a.oslot, a.Y, a.ldy, a.F, a.elr,
                                        a.attn, a.out, a.g_out, a.slope, a.gY, a.ldgy, a.C, a.gy_amax, a.gy_rows, gR,
-                                       ldgr);
+                                       ldgr, a.ymap);
 }
 
 // The per-atom pair: the groups on the backward fallback list (a.G > 0) or every atom.
-template <int H, int VPL>
+template <int H, int VPL, bool MAP>
 int launch_atom_pair(const BwdArgs& a, int big) {
   const unsigned blocks = a.G > 0 ? (unsigned)a.G : (unsigned)ceil_div(a.N, kWavesPerBlock);
-  gat_agg_bwd_dst_kernel<H, VPL><<<blocks, kWavesPerBlock * 64, 0, a.st>>>(
+  gat_agg_bwd_dst_kernel<H, VPL, MAP><<<blocks, kWavesPerBlock * 64, 0, a.st>>>(
       a.N, a.groups, a.G, a.rp, a.src, a.Y, a.ldy, a.elr, a.attn, a.out, a.g_out, a.F, a.slope, a.mode, a.gpre,
-      a.gY, a.ldgy, a.gY + a.C, a.ldgy, big, a.gy_amax, a.gy_rows, a.gR, a.ldgr, a.ramax);
+      a.gY, a.ldgy, a.gY + a.C, a.ldgy, big, a.gy_amax, a.gy_rows, a.gR, a.ldgr, a.ramax, a.ymap);
   int rc = check_launch("gat_agg_bwd_dst_kernel");
   if (rc) return rc;
   gat_agg_bwd_src_kernel<H, VPL><<<blocks, kWavesPerBlock * 64, 0, a.st>>>(
@@ -1151,17 +1166,19 @@ int launch_atom_pair(const BwdArgs& a, int big) {
   return check_launch("gat_agg_bwd_src_kernel");
 }
 
-template <int H>
+template <int H, bool MAP>
 int launch_bwd(bool sep, BwdArgs a) {
+  if constexpr (MAP)
+    if (sep) return kNoCase;  // (refused by the entry: no row-mapped SEP instances)
   const int F = a.F, mode = a.mode;
   // dR apart from gY's rows or not formed (mvml_gat_agg_bwd_res, sep): native in the source-atom
   // kernels, the LDS molecule window and the per-atom pair.  Redirected here, before anything is
   // launched: a head-mean layer always runs by source atom (mean_src = 0 as 1, at every F), and
   // the big windows are off (their groups take the per-atom pair).
-  if (mode == 1 && ((option(MVML_OPT_MEAN_SRC) && F <= 1024) || sep)) return launch_mean_src<H>(a, sep);
+  if (mode == 1 && ((option(MVML_OPT_MEAN_SRC) && F <= 1024) || sep)) return launch_mean_src<H, MAP>(a, sep);
   // flatten layer by source atom, one pass (round 5; the round-4 two-pass form — g_rst rows
   // written first, then gathered — computed the same bits and was measured slower: deleted)
-  if (mode != 1 && option(MVML_OPT_FLAT_SRC)) return launch_flat_src1<H>(a);
+  if (mode != 1 && option(MVML_OPT_FLAT_SRC)) return launch_flat_src1<H, MAP>(a);
   if (option(MVML_OPT_BWD_ATOMWISE)) a.G = 0;  // tests: the per-atom pair over every atom
   if (F % 32 == 0 && a.G > 0) {  // molecule groups: one pass over Z / g_out / dZ per group
     // 32-column chunks (two 512-thread workgroups per CU); 64-column chunks (256-B row segments,
@@ -1169,7 +1186,7 @@ int launch_bwd(bool sep, BwdArgs a) {
     // round 4 (profiles/r04_fwd_chunk_width.txt, second part)
     switch_const<0, 1, 2>(mode, [&](auto m) {
       constexpr int M = decltype(m)::value;
-      if (!sep) launch_lds_bwd(gat_agg_bwd_lds_kernel<H, M, 32>, (unsigned)a.G, 512, a, nullptr, 0);
+      if (!sep) launch_lds_bwd(gat_agg_bwd_lds_kernel<H, M, 32, 512, kWinL, kECap, false, false, MAP>, (unsigned)a.G, 512, a, nullptr, 0);
       else if constexpr (M != 1)  // (flatten modes: a head-mean layer left above)
         launch_lds_bwd(gat_agg_bwd_lds_kernel<H, M, 32, 512, kWinL, kECap, false, true>, (unsigned)a.G, 512, a, a.gR,
                        a.ldgr);
@@ -1184,7 +1201,7 @@ int launch_bwd(bool sep, BwdArgs a) {
   if constexpr (H <= 4) {
     if (big) {
       switch_const<0, 1, 2>(mode, [&](auto m) {
-        launch_lds_bwd(gat_agg_bwd_lds_kernel<H, decltype(m)::value, 16, kBigThreads, kPlanBigAtoms, kPlanBigEdgeCap, true>,
+        launch_lds_bwd(gat_agg_bwd_lds_kernel<H, decltype(m)::value, 16, kBigThreads, kPlanBigAtoms, kPlanBigEdgeCap, true, false, MAP>,
                        (unsigned)std::min<int64_t>(a.G, kBigBlocks), kBigThreads, a, nullptr, 0);
         return MVML_OK;
       });
@@ -1193,7 +1210,7 @@ int launch_bwd(bool sep, BwdArgs a) {
     }
   }
   return switch_const<1, 2, 3, 4, 5, 6, 7, 8>((int)ceil_div(H * F, 256), [&](auto v) {
-    return launch_atom_pair<H, decltype(v)::value>(a, big);
+    return launch_atom_pair<H, decltype(v)::value, MAP>(a, big);
   });
 }
 
@@ -1225,16 +1242,14 @@ extern "C" int mvml_gat_agg_bwd(int64_t num_nodes, const int32_t* node_groups, i
                               gY + H * F, ldgy, gy_amax, gy_row_amax, workspace, workspace_bytes, stream);
 }
 
-extern "C" int mvml_gat_agg_bwd_res(int64_t num_nodes, const int32_t* node_groups, int64_t num_groups,
-                                    const int32_t* in_rowptr, const int32_t* in_src,
-                                    const int32_t* out_rowptr, const int32_t* out_dst,
-                                    const int32_t* out_inslot, const float* Y, int64_t ldy,
-                                    const float* elr, const float* attn, const float* out,
-                                    const float* g_out, int H, int F, float slope, int mode, float* gY,
-                                    int64_t ldgy, int64_t elr_col, float* gR, int64_t ldgr,
-                                    uint32_t* gy_amax, uint32_t* gy_row_amax, void* workspace,
-                                    size_t workspace_bytes, void* stream) {
-  clear_error();
+// mvml_gat_agg_bwd_res and, with a row map, mvml_gat_agg_bwd_res_map
+static int agg_bwd(int64_t num_nodes, const int32_t* node_groups, int64_t num_groups, const int32_t* in_rowptr,
+                   const int32_t* in_src, const int32_t* out_rowptr, const int32_t* out_dst,
+                   const int32_t* out_inslot, const float* Y, int64_t ldy, const float* elr, const float* attn,
+                   const float* out, const float* g_out, int H, int F, float slope, int mode, float* gY,
+                   int64_t ldgy, int64_t elr_col, float* gR, int64_t ldgr, uint32_t* gy_amax,
+                   uint32_t* gy_row_amax, void* workspace, size_t workspace_bytes, void* stream,
+                   const int32_t* ymap) {
   int rc = check_shapes(H, F, mode, ldy, Y, "gat_agg_bwd", (int64_t)H * F);
   if (rc) return rc;
   const int RW = mode == 1 ? F : H * F;
@@ -1252,6 +1267,9 @@ extern "C" int mvml_gat_agg_bwd_res(int64_t num_nodes, const int32_t* node_group
   MVML_REQUIRE(mode != 0 || out != nullptr, "gat_agg_bwd: mode 0 needs the forward output");
   MVML_REQUIRE(num_groups == mvml_node_group_count(num_nodes) && (num_groups == 0 || node_groups),
                "gat_agg_bwd: node_groups must come from mvml_build_node_groups");
+  MVML_REQUIRE(!ymap || !sep, "gat_agg_bwd: the row map needs the projection-row layout "
+                              "(no row-mapped separate-residual instances)");
+  MVML_REQUIRE(!ymap || ldy * kMaxFeatClasses < (int64_t(1) << 29), "gat_agg_bwd: row table past 2 GiB");
   if (num_nodes == 0) return MVML_OK;
   if (!workspace || workspace_bytes == 0) {
     set_error("gat_agg_bwd: workspace of mvml_gat_agg_bwd_workspace_size(E, H) bytes required");
@@ -1259,9 +1277,61 @@ extern "C" int mvml_gat_agg_bwd_res(int64_t num_nodes, const int32_t* node_group
   }
   const BwdArgs a{num_nodes, node_groups, num_groups, in_rowptr, in_src, out_rowptr, out_dst, out_inslot, Y, ldy,
                   elr, attn, out, g_out, F, slope, mode, static_cast<float*>(workspace), gY, ldgy, C, gy_amax,
-                  gy_row_amax, gR, ldgr, sep ? 0 : 1, as_stream(stream)};
-  rc = switch_const<1, 2, 4, 8>(H, [&](auto h) { return launch_bwd<decltype(h)::value>(sep, a); });
+                  gy_row_amax, gR, ldgr, sep ? 0 : 1, as_stream(stream), ymap};
+  rc = switch_const<1, 2, 4, 8>(H, [&](auto h) {
+    return ymap ? launch_bwd<decltype(h)::value, true>(sep, a) : launch_bwd<decltype(h)::value, false>(sep, a);
+  });
   if (rc != kNoCase) return rc;
   set_error("gat_agg_bwd: unsupported shape");
   return MVML_ERR_INVALID;
+}
+
+extern "C" int mvml_gat_agg_bwd_res(int64_t num_nodes, const int32_t* node_groups, int64_t num_groups,
+                                    const int32_t* in_rowptr, const int32_t* in_src,
+                                    const int32_t* out_rowptr, const int32_t* out_dst,
+                                    const int32_t* out_inslot, const float* Y, int64_t ldy,
+                                    const float* elr, const float* attn, const float* out,
+                                    const float* g_out, int H, int F, float slope, int mode, float* gY,
+                                    int64_t ldgy, int64_t elr_col, float* gR, int64_t ldgr,
+                                    uint32_t* gy_amax, uint32_t* gy_row_amax, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+  clear_error();
+  return agg_bwd(num_nodes, node_groups, num_groups, in_rowptr, in_src, out_rowptr, out_dst, out_inslot, Y, ldy,
+                 elr, attn, out, g_out, H, F, slope, mode, gY, ldgy, elr_col, gR, ldgr, gy_amax, gy_row_amax,
+                 workspace, workspace_bytes, stream, nullptr);
+}
+
+extern "C" int mvml_gat_agg_bwd_res_map(int64_t num_nodes, const int32_t* node_groups, int64_t num_groups,
+                                        const int32_t* in_rowptr, const int32_t* in_src,
+                                        const int32_t* out_rowptr, const int32_t* out_dst,
+                                        const int32_t* out_inslot, const float* Y, int64_t ldy,
+                                        const float* elr, const float* attn, const float* out,
+                                        const float* g_out, int H, int F, float slope, int mode, float* gY,
+                                        int64_t ldgy, int64_t elr_col, float* gR, int64_t ldgr,
+                                        uint32_t* gy_amax, uint32_t* gy_row_amax, void* workspace,
+                                        size_t workspace_bytes, void* stream, const int32_t* yrow) {
+  clear_error();
+  MVML_REQUIRE(yrow != nullptr, "gat_agg_bwd: the row-mapped entry needs yrow");
+  return agg_bwd(num_nodes, node_groups, num_groups, in_rowptr, in_src, out_rowptr, out_dst, out_inslot, Y, ldy,
+                 elr, attn, out, g_out, H, F, slope, mode, gY, ldgy, elr_col, gR, ldgr, gy_amax, gy_row_amax,
+                 workspace, workspace_bytes, stream, yrow);
+}
+
+extern "C" int mvml_gat_agg_bwd_map(int64_t num_nodes, const int32_t* node_groups, int64_t num_groups,
+                                    const int32_t* in_rowptr, const int32_t* in_src,
+                                    const int32_t* out_rowptr, const int32_t* out_dst,
+                                    const int32_t* out_inslot, const float* Y, int64_t ldy,
+                                    const float* elr, const float* attn, const float* out,
+                                    const float* g_out, int H, int F, float slope, int mode, float* gY,
+                                    int64_t ldgy, uint32_t* gy_amax, uint32_t* gy_row_amax, void* workspace,
+                                    size_t workspace_bytes, void* stream, const int32_t* yrow) {
+  clear_error();
+  int rc = check_shapes(H, F, mode, ldy, Y, "gat_agg_bwd");  // Y rows hold [Z | R]
+  if (rc) return rc;
+  const int C = mvml_gat_proj_cols(H, F, mode == 1);
+  MVML_REQUIRE(ldgy >= C + 2 * H && ldgy % 4 == 0 && ldgy < (1 << 20),
+               "gat_agg_bwd: ldgy must be >= proj_cols + 2H = %d and a multiple of 4", C + 2 * H);
+  return mvml_gat_agg_bwd_res_map(num_nodes, node_groups, num_groups, in_rowptr, in_src, out_rowptr, out_dst,
+                                  out_inslot, Y, ldy, elr, attn, out, g_out, H, F, slope, mode, gY, ldgy, C,
+                                  gY + H * F, ldgy, gy_amax, gy_row_amax, workspace, workspace_bytes, stream, yrow);
 }

@@ -46,6 +46,17 @@ __device__ __forceinline__ void st4nt(float* p, float4 v) {
   __builtin_nontemporal_store(w, reinterpret_cast<mvml_f4v*>(p));
 }
 
+// Row-mapped projection (mvml_gat_agg_fwd_map / mvml_gat_agg_bwd_map, MAP instances): atom a's
+// projection row is Y + yrow[a] * ldy, rows of a table of at most kMaxFeatClasses rows (layer 1:
+// one row per distinct atom-feature row, feat_classes.hip) that stays in an XCD's L2.  !MAP: the
+// atom's own row, compiled as before (yrow unused).
+constexpr int kMaxFeatClasses = MVML_MAX_FEAT_CLASSES;
+template <bool MAP>
+__device__ __forceinline__ int64_t yrow_of(const int32_t* __restrict__ yrow, int64_t a) {
+  if constexpr (MAP) return yrow[a];
+  else return a;  // (untouched: the !MAP instances keep their address arithmetic)
+}
+
 // wave-uniform per-head values -> p[0..H): lane h stores a[h]
 template <int H>
 __device__ __forceinline__ void store_heads(float* p, const float (&a)[H], int lane) {

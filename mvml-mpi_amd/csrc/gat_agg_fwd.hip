@@ -92,7 +92,8 @@ constexpr int kFwdRing = 2;           // LDS kernel: chunks in flight in the reg
 // resource's range check; chunks past the end use an out-of-range offset), so the loop is
 // straight-line and the compiler's vmcnt waits are exact; stores of rows past the group are
 // skipped (an out-of-range store is not free).
-template <int H, int CW, int MODE, int NT, int NPA, int WIN = kWinL, int ECAP = kECap, bool BIG = false>
+template <int H, int CW, int MODE, int NT, int NPA, int WIN = kWinL, int ECAP = kECap, bool BIG = false,
+          bool MAP = false>
 __device__ __forceinline__ float fwd_lds_chunks(float4 (*zbuf)[WIN * (CW / 4)], const float* s_att,
                                                const int32_t* __restrict__ rowptr,
                                                const int32_t* __restrict__ in_src,
@@ -102,7 +103,8 @@ __device__ __forceinline__ float fwd_lds_chunks(float4 (*zbuf)[WIN * (CW / 4)], 
                                                const uint16_t* s_srcs = nullptr,
                                                const uint32_t* s_seg = nullptr,
                                                const int* s_rs = nullptr, float4* s_part = nullptr,
-                                               int nseg = 0, uint32_t* __restrict__ out_rows = nullptr) {
+                                               int nseg = 0, uint32_t* __restrict__ out_rows = nullptr,
+                                               const int32_t* __restrict__ yrow = nullptr) {
   constexpr int LPD = CW / 4;                        // lanes per destination atom
   constexpr int DPP = NT / LPD;                      // destinations per pass
   constexpr int RING = NPA >= 3 ? 1 : kFwdRing;      // 3-4 pass groups: registers
@@ -120,7 +122,8 @@ __device__ __forceinline__ float fwd_lds_chunks(float4 (*zbuf)[WIN * (CW / 4)], 
   // "no access" offsets: just past the resource's range (reads 0, drops stores) yet next to
   // the group's own rows, so the address still translates through a warm TLB entry (a wild
   // out-of-range offset costs a page walk per access)
-  const uint32_t noY = (uint32_t)nr * rowb;
+  // (MAP: rY spans the whole row table; its rows come through yrow)
+  const uint32_t noY = (uint32_t)(MAP ? kMaxFeatClasses : nr) * rowb;
   float omx = 0.f;  // |max| of this thread's output stores (live rows)
   float rmx[NPA];   // ... per destination (out_rows: each row's |max|, the next GEMM's row scale)
   bool live[NPA];
@@ -141,6 +144,7 @@ __device__ __forceinline__ float fwd_lds_chunks(float4 (*zbuf)[WIN * (CW / 4)], 
       so[p][i] = ((i < deg) ? in_src[e0 + eb + i] - a0 : (live[p] ? d : 0)) * LPD + q;
     }
     rb[p] = (uint32_t)d * rowb;            // d >= nr: past the resource, reads 0
+    if constexpr (MAP) rb[p] = live[p] ? (uint32_t)yrow[a0 + d] * rowb : noY;
     ob[p] = 4u * (uint32_t)(d * ocols);
   }
   // BIG: this thread's rows' hub segments (first | count << 12); the edges of a row with none
@@ -304,13 +308,14 @@ __device__ __forceinline__ float fwd_lds_chunks(float4 (*zbuf)[WIN * (CW / 4)], 
 // BIG (kind bit 2): the big-window variant for the groups on the forward fallback list (config
 // 5's 150-400-atom molecules with hubs): 16-column chunks so that 512 rows fit LDS, in-degree
 // unbounded (the hub loop above), one workgroup per CU walking the list.
-template <int H, int CW, int MODE, int NT, int WIN = kWinL, int ECAP = kECap, bool BIG = false>
+template <int H, int CW, int MODE, int NT, int WIN = kWinL, int ECAP = kECap, bool BIG = false, bool MAP = false>
 __global__ void __launch_bounds__(NT, kLdsWaves)
 gat_agg_fwd_lds_kernel(const int32_t* __restrict__ plan, int64_t G, const int32_t* __restrict__ rowptr,
                        const int32_t* __restrict__ in_src, const float* __restrict__ Y, int64_t ldy,
                        int F, const float* __restrict__ bias, const float* __restrict__ elr,
                        float slope, float* __restrict__ attn, float* __restrict__ out,
-                       uint32_t* __restrict__ out_amax, uint32_t* __restrict__ out_rows) {
+                       uint32_t* __restrict__ out_amax, uint32_t* __restrict__ out_rows,
+                       const int32_t* __restrict__ yrow = nullptr) {
   constexpr int LPD = CW / 4;
   constexpr int DPP = NT / LPD;
   constexpr int NPM = WIN / DPP;  // passes over a full window
@@ -354,27 +359,29 @@ gat_agg_fwd_lds_kernel(const int32_t* __restrict__ plan, int64_t G, const int32_
     __syncthreads();
   }
   const uint32_t rowb = (uint32_t)ldy * 4u;
-  const __amdgpu_buffer_rsrc_t rY = make_rsrc(Y + (int64_t)a0 * ldy, (uint32_t)nr * rowb);
+  const __amdgpu_buffer_rsrc_t rY = MAP ? make_rsrc(Y, (uint32_t)kMaxFeatClasses * rowb)
+                                        : make_rsrc(Y + (int64_t)a0 * ldy, (uint32_t)nr * rowb);
   const __amdgpu_buffer_rsrc_t rO = make_rsrc(out + (int64_t)a0 * ocols, (uint32_t)(nr * ocols) * 4u);
   if (nr <= DPP)
-    omx = fmaxf(omx, fwd_lds_chunks<H, CW, MODE, NT, 1, WIN, ECAP, BIG>(zbuf, s_att, rowptr, in_src, rY, rowb, rO, a0, nr, e0, F, bias, s_srcs, s_seg, s_rs, s_part, nseg, out_rows));
+    omx = fmaxf(omx, fwd_lds_chunks<H, CW, MODE, NT, 1, WIN, ECAP, BIG, MAP>(zbuf, s_att, rowptr, in_src, rY, rowb, rO, a0, nr, e0, F, bias, s_srcs, s_seg, s_rs, s_part, nseg, out_rows, yrow));
   else if (NPM == 2 || nr <= 2 * DPP)
-    omx = fmaxf(omx, fwd_lds_chunks<H, CW, MODE, NT, 2, WIN, ECAP, BIG>(zbuf, s_att, rowptr, in_src, rY, rowb, rO, a0, nr, e0, F, bias, s_srcs, s_seg, s_rs, s_part, nseg, out_rows));
+    omx = fmaxf(omx, fwd_lds_chunks<H, CW, MODE, NT, 2, WIN, ECAP, BIG, MAP>(zbuf, s_att, rowptr, in_src, rY, rowb, rO, a0, nr, e0, F, bias, s_srcs, s_seg, s_rs, s_part, nseg, out_rows, yrow));
   else if (nr <= 3 * DPP)
-    omx = fmaxf(omx, fwd_lds_chunks<H, CW, MODE, NT, (NPM > 2 ? 3 : 2), WIN, ECAP, BIG>(zbuf, s_att, rowptr, in_src, rY, rowb, rO, a0, nr, e0, F, bias, s_srcs, s_seg, s_rs, s_part, nseg, out_rows));
+    omx = fmaxf(omx, fwd_lds_chunks<H, CW, MODE, NT, (NPM > 2 ? 3 : 2), WIN, ECAP, BIG, MAP>(zbuf, s_att, rowptr, in_src, rY, rowb, rO, a0, nr, e0, F, bias, s_srcs, s_seg, s_rs, s_part, nseg, out_rows, yrow));
   else
-    omx = fmaxf(omx, fwd_lds_chunks<H, CW, MODE, NT, NPM, WIN, ECAP, BIG>(zbuf, s_att, rowptr, in_src, rY, rowb, rO, a0, nr, e0, F, bias, s_srcs, s_seg, s_rs, s_part, nseg, out_rows));
+    omx = fmaxf(omx, fwd_lds_chunks<H, CW, MODE, NT, NPM, WIN, ECAP, BIG, MAP>(zbuf, s_att, rowptr, in_src, rY, rowb, rO, a0, nr, e0, F, bias, s_srcs, s_seg, s_rs, s_part, nseg, out_rows, yrow));
   }
   if (out_amax) block_amax_commit<NT>(omx, out_amax);
 }
 
-template <int H, int CW, int MODE>
+template <int H, int CW, int MODE, bool MAP = false>
 __global__ void __launch_bounds__(kAggThreads, 4)  // 2 workgroups (16 waves) per CU
 gat_agg_fwd_gather_kernel(const int32_t* __restrict__ plan, int64_t G, const int32_t* __restrict__ rowptr,
                    const int32_t* __restrict__ in_src, const float* __restrict__ Y, int64_t ldy,
                    int F, const float* __restrict__ bias, const float* __restrict__ elr, float slope,
                    float* __restrict__ attn, float* __restrict__ out, int skip_big,
-                   uint32_t* __restrict__ out_amax, uint32_t* __restrict__ out_rows) {
+                   uint32_t* __restrict__ out_amax, uint32_t* __restrict__ out_rows,
+                   const int32_t* __restrict__ yrow = nullptr) {
   constexpr int LPD = CW / 4;                        // lanes per destination atom
   constexpr int DPP = kAggThreads / LPD;             // destinations per pass
   constexpr int NP = (kWin + DPP - 1) / DPP;         // passes over a full window
@@ -395,7 +402,10 @@ gat_agg_fwd_gather_kernel(const int32_t* __restrict__ plan, int64_t G, const int
   // kNodeGroupAtoms + one molecule's atoms, rows of <= 2^20 floats are checked by the host)
   const float* Yg = Y + (int64_t)a0 * ldy;
   const uint32_t rowb = (uint32_t)ldy * 4u;
-  const __amdgpu_buffer_rsrc_t rY = make_rsrc(Yg, (uint32_t)(a1 - a0) * rowb);
+  const __amdgpu_buffer_rsrc_t rY = MAP ? make_rsrc(Y, (uint32_t)kMaxFeatClasses * rowb)
+                                        : make_rsrc(Yg, (uint32_t)(a1 - a0) * rowb);
+  // byte offset of atom n's projection row in rY (MAP: its row of the table)
+  auto yoff = [&](int n) -> uint32_t { return (uint32_t)(MAP ? yrow_of<MAP>(yrow, n) : n - a0) * rowb; };
   constexpr uint32_t kNone = 0xFFFFFFF0u;  // out of range: the load returns 0, moves no data
   // Hub destinations (in-degree > kHubDeg) leave the chunk sweep: after it, the whole block
   // aggregates one hub at a time over ALL its columns at once, so a hub costs deg / 8 memory
@@ -433,7 +443,7 @@ gat_agg_fwd_gather_kernel(const int32_t* __restrict__ plan, int64_t G, const int
       if (hub[p]) deg[p] = 0;  // aggregated by the hub pass below
 #pragma unroll
       for (int i = 0; i < kEC; ++i)
-        so[p][i] = (i < deg[p]) ? (uint32_t)(in_src[e0 + eb[p] + i] - a0) * rowb : kNone;
+        so[p][i] = (i < deg[p]) ? yoff(in_src[e0 + eb[p] + i]) : kNone;
       dmax = max(dmax, deg[p]);
     }
 #pragma unroll
@@ -454,7 +464,7 @@ gat_agg_fwd_gather_kernel(const int32_t* __restrict__ plan, int64_t G, const int
 #pragma unroll
       for (int p = 0; p < NP; ++p) {
         const int d = ds + DPP * p;
-        const uint32_t rb = (d < nr) ? (uint32_t)(w0 + d - a0) * rowb : kNone;
+        const uint32_t rb = (d < nr) ? yoff(w0 + d) : kNone;
         if (MODE != 1) res[p] = buf_ld4(rY, rb == kNone ? kNone : rb + 4u * (uint32_t)(HF + col));
         else if (h == 0) rm[p] = buf_ld4(rY, rb == kNone ? kNone : rb + 4u * (uint32_t)(HF + fc * CW + 4 * q));
       }
@@ -487,7 +497,7 @@ gat_agg_fwd_gather_kernel(const int32_t* __restrict__ plan, int64_t G, const int
             for (int j = 0; j < 8; ++j) {
               const bool ok = i + j < deg[p];
               const int e = eb[p] + (ok ? i + j : i);
-              ob[j] = ok ? (uint32_t)(in_src[e0 + e] - a0) * rowb + colb : kNone;
+              ob[j] = ok ? yoff(in_src[e0 + e]) + colb : kNone;
               av[j] = ok ? att(e, h) : 0.f;
             }
             float4 zv[8];
@@ -534,7 +544,7 @@ gat_agg_fwd_gather_kernel(const int32_t* __restrict__ plan, int64_t G, const int
     for (int d = 0; d < nr; ++d) {  // block-uniform walk over the window's hubs
       const int hb = rowptr[w0 + d] - e0, hdeg = rowptr[w0 + d + 1] - e0 - hb;
       if (hdeg <= kHubDeg) continue;
-      const uint32_t vb = (uint32_t)(w0 + d - a0) * rowb;
+      const uint32_t vb = yoff(w0 + d);
       float hmx = 0.f;  // this thread's part of the hub row's |max|
       for (int c4 = tid; c4 < HF / 4; c4 += kAggThreads) {
         const int col = 4 * c4, h = col / F;
@@ -547,7 +557,7 @@ gat_agg_fwd_gather_kernel(const int32_t* __restrict__ plan, int64_t G, const int
           for (int j = 0; j < 8; ++j) {
             const bool ok = i + j < hdeg;
             const int e = hb + (ok ? i + j : i);
-            ob[j] = ok ? (uint32_t)(in_src[e0 + e] - a0) * rowb + colb : kNone;
+            ob[j] = ok ? yoff(in_src[e0 + e]) + colb : kNone;
             av[j] = ok ? attw[e * H + h] : 0.f;
           }
           float4 zv[8];
@@ -622,14 +632,14 @@ gat_agg_fwd_gather_kernel(const int32_t* __restrict__ plan, int64_t G, const int
 // SEP (mvml_gat_agg_fwd_res): the residual rows come from R (row stride ldr; NULL: no residual)
 // instead of Y's columns past H F, and bias may be NULL.  !SEP is the in-row layout with a
 // bias, compiled exactly as before (R / ldr unused).
-template <int H, int MODE, int NJ, int U, bool SM, bool LR = false, bool SEP = false>
+template <int H, int MODE, int NJ, int U, bool SM, bool LR = false, bool SEP = false, bool MAP = false>
 __global__ void __launch_bounds__(256, LR ? (MODE == 1 ? 5 : 8) : 1)
 gat_agg_fwd_dst_kernel(int64_t N, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ in_src,
                        const float* __restrict__ Y, int64_t ldy, int F, const float* __restrict__ bias,
                        const float* __restrict__ elr, float slope, float* __restrict__ attn,
                        float* __restrict__ out, uint32_t* __restrict__ out_amax,
                        uint32_t* __restrict__ out_rows, const float* __restrict__ R = nullptr,
-                       int64_t ldr = 0) {
+                       int64_t ldr = 0, const int32_t* __restrict__ yrow = nullptr) {
   constexpr bool PAIR = MODE == 1 && H >= 2;
   constexpr int NH = PAIR ? H / 2 : 1;  // heads per lane (mean mode); 1 register set (flatten)
   const int lane = threadIdx.x & 63;
@@ -642,7 +652,7 @@ gat_agg_fwd_dst_kernel(int64_t N, const int32_t* __restrict__ rowptr, const int3
     const int HF = H * F;
     const int hp = PAIR ? lane >> 5 : 0;       // mean: this lane's half (heads hp H/2 ..)
     const int ql = PAIR ? (lane & 31) : lane;  // mean: f-float4 base of this lane
-    const float* yv = Y + v * ldy;
+    const float* yv = Y + (int64_t)yrow_of<MAP>(yrow, v) * ldy;
     // this atom's residual row (SEP: NULL without a residual) and the bias (SEP: may be NULL)
     const float* rv = SEP ? (R ? R + v * ldr : nullptr) : yv + HF;
     auto ldres = [&](int c) -> float4 {
@@ -759,12 +769,14 @@ gat_agg_fwd_dst_kernel(int64_t N, const int32_t* __restrict__ rowptr, const int3
           for (int h = 0; h < H; ++h) a_l[h] = lane < cnt ? ap[h] : 0.f;
         }
       }
+      int yr_l = src_l;  // the projection rows of the chunk's sources (MAP: through yrow)
+      if constexpr (MAP) yr_l = yrow[src_l];
       for (int j0 = 0; j0 < cnt; j0 += U) {
         float4 z[U][NH][NJ];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
           const int e = min(j0 + u, cnt - 1);  // past the chunk: a duplicate row, not summed
-          const float* zr = Y + (int64_t)rl(src_l, e) * ldy;
+          const float* zr = Y + (int64_t)rl(yr_l, e) * ldy;
 #pragma unroll
           for (int h = 0; h < NH; ++h)
 #pragma unroll
@@ -925,6 +937,7 @@ struct FwdArgs {
   const float* R;
   int64_t ldr;
   hipStream_t st;
+  const int32_t* yrow;  // the MAP instances' row map (mvml_gat_agg_fwd_map; NULL: atom rows)
 };
 
 // The destination-wave instance of a shape, <H, M, NJ, U, SM, LR, SEP>, is a function of its
@@ -943,21 +956,21 @@ constexpr bool dst_late_residual(int H, int M, int NJ, bool SEP, bool SM) {
   return !SEP && H == 4 && NJ == 3 && (M == 1 || SM);
 }
 
-template <int H, int M, int NJ, bool SEP>
+template <int H, int M, int NJ, bool SEP, bool MAP>
 int launch_dst_fwd(bool sm, const FwdArgs& a) {
   constexpr int U = dst_rows_in_flight(M, NJ);
-  const auto kernel = sm ? gat_agg_fwd_dst_kernel<H, M, NJ, U, true, dst_late_residual(H, M, NJ, SEP, true), SEP>
-                         : gat_agg_fwd_dst_kernel<H, M, NJ, U, false, dst_late_residual(H, M, NJ, SEP, false), SEP>;
+  const auto kernel = sm ? gat_agg_fwd_dst_kernel<H, M, NJ, U, true, dst_late_residual(H, M, NJ, SEP, true), SEP, MAP>
+                         : gat_agg_fwd_dst_kernel<H, M, NJ, U, false, dst_late_residual(H, M, NJ, SEP, false), SEP, MAP>;
   // with per-row maxima requested, max |out| comes from them afterwards (no per-block atomics)
   kernel<<<(unsigned)ceil_div(a.N, 4), 256, 0, a.st>>>(a.N, a.rp, a.src, a.Y, a.ldy, a.F, a.bias, a.elr, a.slope,
                                                        a.attn, a.out, a.out_rows ? nullptr : a.out_amax,
-                                                       a.out_rows, a.R, a.ldr);
+                                                       a.out_rows, a.R, a.ldr, a.yrow);
   return check_launch("gat_agg_fwd_dst_kernel");
 }
 
 // One wave per destination atom, every atom.  Mean mode: half-waves over the heads, lanes over
 // F / 4; flatten modes: lanes over H F / 4.  Shapes past four slots take the 8-slot instance.
-template <int H, bool SEP>
+template <int H, bool SEP, bool MAP = false>
 int launch_dst_fwd_shape(bool sm, const FwdArgs& a) {
   const int nj = a.mode == 1 ? (int)ceil_div(a.F / 4, H >= 2 ? 32 : 64) : (int)ceil_div(H * a.F / 4, 64);
   const int rc = switch_const<0, 1, 2>(a.mode, [&](auto m) {
@@ -966,7 +979,7 @@ int launch_dst_fwd_shape(bool sm, const FwdArgs& a) {
       // head-mean rows past 4 slots (F > 512 at H = 2, 1024 at H = 1): a separate residual and
       // H <= 2 only (in the projection-row layout launch_fwd's dst_fits keeps them away)
       if constexpr (M == 1 && NJ == 8 && !(SEP && H <= 2)) return kNoCase;
-      else return launch_dst_fwd<H, M, NJ, SEP>(sm, a);
+      else return launch_dst_fwd<H, M, NJ, SEP, MAP>(sm, a);
     });
   });
   if (rc) return rc;
@@ -975,22 +988,23 @@ int launch_dst_fwd_shape(bool sm, const FwdArgs& a) {
 
 // The node-group kernels at chunk width CW: the LDS window, the gather kernel for the groups on
 // the fallback list and, with big, the big window for those among them that fit it.
-template <int H, int CW, int M>
+template <int H, int CW, int M, bool MAP>
 void launch_group_fwd(bool big, const FwdArgs& a) {
-  gat_agg_fwd_lds_kernel<H, CW, M, CW * 16><<<(unsigned)a.G, CW * 16, 0, a.st>>>(
-      a.groups, a.G, a.rp, a.src, a.Y, a.ldy, a.F, a.bias, a.elr, a.slope, a.attn, a.out, a.out_amax, a.out_rows);
-  gat_agg_fwd_gather_kernel<H, CW, M><<<(unsigned)a.G, kAggThreads, 0, a.st>>>(
+  gat_agg_fwd_lds_kernel<H, CW, M, CW * 16, kWinL, kECap, false, MAP><<<(unsigned)a.G, CW * 16, 0, a.st>>>(
+      a.groups, a.G, a.rp, a.src, a.Y, a.ldy, a.F, a.bias, a.elr, a.slope, a.attn, a.out, a.out_amax, a.out_rows,
+      a.yrow);
+  gat_agg_fwd_gather_kernel<H, CW, M, MAP><<<(unsigned)a.G, kAggThreads, 0, a.st>>>(
       a.groups, a.G, a.rp, a.src, a.Y, a.ldy, a.F, a.bias, a.elr, a.slope, a.attn, a.out, big, a.out_amax,
-      a.out_rows);
+      a.out_rows, a.yrow);
   if constexpr (H <= 4)
     if (big)
-      gat_agg_fwd_lds_kernel<H, 16, M, kBigThreads, kPlanBigAtoms, kPlanBigEdgeCap, true>
+      gat_agg_fwd_lds_kernel<H, 16, M, kBigThreads, kPlanBigAtoms, kPlanBigEdgeCap, true, MAP>
           <<<(unsigned)std::min<int64_t>(a.G, kBigBlocks), kBigThreads, 0, a.st>>>(
               a.groups, a.G, a.rp, a.src, a.Y, a.ldy, a.F, a.bias, a.elr, a.slope, a.attn, a.out, a.out_amax,
-              a.out_rows);
+              a.out_rows, a.yrow);
 }
 
-template <int H>
+template <int H, bool MAP>
 int launch_fwd(bool sep, const FwdArgs& a) {
   const int F = a.F;
   // The edge softmax as a launch of its own before the destination waves (dst_fwd = 2).
@@ -1007,6 +1021,7 @@ int launch_fwd(bool sep, const FwdArgs& a) {
   // rows past 4 slots, H <= 2 only, take an 8-slot instance); every option value is redirected
   // to them here, before anything is launched (dst_fwd 0 runs as 1: the softmax in the wave).
   if (sep) {
+    if constexpr (MAP) return kNoCase;  // (refused by the entry: no row-mapped SEP instances)
     const bool sm = option(MVML_OPT_DST_FWD) != 2;
     if (!sm)
       if (int rc = softmax_first(false)) return rc;
@@ -1021,7 +1036,7 @@ int launch_fwd(bool sep, const FwdArgs& a) {
     const bool sm = option(MVML_OPT_DST_FWD) == 1;  // 2: the softmax as its own launch first
     if (!sm)
       if (int rc = softmax_first(H == 4)) return rc;
-    return launch_dst_fwd_shape<H, false>(sm, a);
+    return launch_dst_fwd_shape<H, false, MAP>(sm, a);
   }
   if (a.G == 0) return MVML_OK;
   const bool big = use_big_window(H, F);
@@ -1032,7 +1047,7 @@ int launch_fwd(bool sep, const FwdArgs& a) {
   const int cw = F % 32 == 0 ? 32 : F % 16 == 0 ? 16 : F % 8 == 0 ? 8 : 4;
   switch_const<4, 8, 16, 32>(cw, [&](auto c) {
     return switch_const<0, 1, 2>(a.mode, [&](auto m) {
-      launch_group_fwd<H, decltype(c)::value, decltype(m)::value>(big, a);
+      launch_group_fwd<H, decltype(c)::value, decltype(m)::value, MAP>(big, a);
       return MVML_OK;
     });
   });
@@ -1047,9 +1062,70 @@ int launch_rows_amax(int64_t n, const uint32_t* rows, uint32_t* out, hipStream_t
   return check_launch("rows_amax_kernel");
 }
 
+namespace {
+
+// mvml_gat_agg_fwd_res and, with a row map, mvml_gat_agg_fwd_res_map
+int agg_fwd(int64_t num_nodes, const int32_t* node_groups, int64_t num_groups, const int32_t* in_rowptr,
+            const int32_t* in_src, const float* Y, int64_t ldy, int H, int F, const float* elr, const float* R,
+            int64_t ldr, const float* bias, float slope, int mode, float* out, float* attn, uint32_t* out_amax,
+            uint32_t* out_row_amax, void* stream, const int32_t* yrow) {
+  int rc = check_shapes(H, F, mode, ldy, Y, "gat_agg_fwd", (int64_t)H * F);
+  if (rc) return rc;
+  const int RW = mode == 1 ? F : H * F;
+  MVML_REQUIRE(aligned16(out) && aligned16(bias),
+               "gat_agg_fwd: out / bias must be 16-byte aligned");
+  MVML_REQUIRE(R == nullptr || (aligned16(R) && ldr % 4 == 0 && ldr >= RW && ldr < (1 << 20)),
+               "gat_agg_fwd: R must be 16-byte aligned with a row stride ldr >= %d that is a multiple of 4", RW);
+  // the projection-row layout with a bias runs the instances compiled for it; a residual apart
+  // from Y, no residual or no bias the SEP ones (launch_fwd)
+  const bool sep = !(R == Y + H * F && ldr == ldy && bias != nullptr);
+  MVML_REQUIRE(attn != nullptr && elr != nullptr, "gat_agg_fwd: elr input and attn output are required");
+  MVML_REQUIRE(num_groups == mvml_node_group_count(num_nodes) && (num_groups == 0 || node_groups),
+               "gat_agg_fwd: node_groups must come from mvml_build_node_groups (%lld groups expected)",
+               (long long)mvml_node_group_count(num_nodes));
+  MVML_REQUIRE(!yrow || !sep, "gat_agg_fwd: the row map needs the projection-row layout with a bias "
+                              "(no row-mapped separate-residual instances)");
+  MVML_REQUIRE(!yrow || ldy * kMaxFeatClasses < (int64_t(1) << 29), "gat_agg_fwd: row table past 2 GiB");
+  if (num_nodes == 0) return MVML_OK;
+  const FwdArgs a{num_nodes, node_groups, num_groups, in_rowptr, in_src, Y, ldy, F, bias, elr, slope, mode, out,
+                  attn, out_amax, out_row_amax, sep ? R : nullptr, sep ? ldr : 0, as_stream(stream), yrow};
+  rc = switch_const<1, 2, 4, 8>(H, [&](auto h) {
+    return yrow ? launch_fwd<decltype(h)::value, true>(sep, a) : launch_fwd<decltype(h)::value, false>(sep, a);
+  });
+  if (rc != kNoCase) return rc;
+  set_error("gat_agg_fwd: unsupported shape");
+  return MVML_ERR_INVALID;
+}
+
+}  // namespace
 }  // namespace mvml
 
 using namespace mvml;
+
+extern "C" int mvml_gat_agg_fwd_map(int64_t num_nodes, const int32_t* node_groups, int64_t num_groups,
+                                    const int32_t* in_rowptr, const int32_t* in_src, const float* Y,
+                                    int64_t ldy, int H, int F, const float* elr, const float* bias,
+                                    float slope, int mode, float* out, float* attn, uint32_t* out_amax,
+                                    uint32_t* out_row_amax, void* stream, const int32_t* yrow) {
+  clear_error();
+  int rc = check_shapes(H, F, mode, ldy, Y, "gat_agg_fwd");  // Y rows hold [Z | R]
+  if (rc) return rc;
+  return mvml_gat_agg_fwd_res_map(num_nodes, node_groups, num_groups, in_rowptr, in_src, Y, ldy, H, F, elr,
+                                  Y + H * F, ldy, bias, slope, mode, out, attn, out_amax, out_row_amax, stream,
+                                  yrow);
+}
+
+extern "C" int mvml_gat_agg_fwd_res_map(int64_t num_nodes, const int32_t* node_groups, int64_t num_groups,
+                                        const int32_t* in_rowptr, const int32_t* in_src, const float* Y,
+                                        int64_t ldy, int H, int F, const float* elr, const float* R,
+                                        int64_t ldr, const float* bias, float slope, int mode, float* out,
+                                        float* attn, uint32_t* out_amax, uint32_t* out_row_amax,
+                                        void* stream, const int32_t* yrow) {
+  clear_error();
+  MVML_REQUIRE(yrow != nullptr, "gat_agg_fwd: the row-mapped entry needs yrow");
+  return agg_fwd(num_nodes, node_groups, num_groups, in_rowptr, in_src, Y, ldy, H, F, elr, R, ldr, bias, slope,
+                 mode, out, attn, out_amax, out_row_amax, stream, yrow);
+}
 
 extern "C" int mvml_gat_agg_fwd(int64_t num_nodes, const int32_t* node_groups, int64_t num_groups,
                                 const int32_t* in_rowptr, const int32_t* in_src, const float* Y,
@@ -1070,25 +1146,6 @@ extern "C" int mvml_gat_agg_fwd_res(int64_t num_nodes, const int32_t* node_group
                                     float* attn, uint32_t* out_amax, uint32_t* out_row_amax,
                                     void* stream) {
   clear_error();
-  int rc = check_shapes(H, F, mode, ldy, Y, "gat_agg_fwd", (int64_t)H * F);
-  if (rc) return rc;
-  const int RW = mode == 1 ? F : H * F;
-  MVML_REQUIRE(aligned16(out) && aligned16(bias),
-               "gat_agg_fwd: out / bias must be 16-byte aligned");
-  MVML_REQUIRE(R == nullptr || (aligned16(R) && ldr % 4 == 0 && ldr >= RW && ldr < (1 << 20)),
-               "gat_agg_fwd: R must be 16-byte aligned with a row stride ldr >= %d that is a multiple of 4", RW);
-  // the projection-row layout with a bias runs the instances compiled for it; a residual apart
-  // from Y, no residual or no bias the SEP ones (launch_fwd)
-  const bool sep = !(R == Y + H * F && ldr == ldy && bias != nullptr);
-  MVML_REQUIRE(attn != nullptr && elr != nullptr, "gat_agg_fwd: elr input and attn output are required");
-  MVML_REQUIRE(num_groups == mvml_node_group_count(num_nodes) && (num_groups == 0 || node_groups),
-               "gat_agg_fwd: node_groups must come from mvml_build_node_groups (%lld groups expected)",
-               (long long)mvml_node_group_count(num_nodes));
-  if (num_nodes == 0) return MVML_OK;
-  const FwdArgs a{num_nodes, node_groups, num_groups, in_rowptr, in_src, Y, ldy, F, bias, elr, slope, mode, out,
-                  attn, out_amax, out_row_amax, sep ? R : nullptr, sep ? ldr : 0, as_stream(stream)};
-  rc = switch_const<1, 2, 4, 8>(H, [&](auto h) { return launch_fwd<decltype(h)::value>(sep, a); });
-  if (rc != kNoCase) return rc;
-  set_error("gat_agg_fwd: unsupported shape");
-  return MVML_ERR_INVALID;
+  return agg_fwd(num_nodes, node_groups, num_groups, in_rowptr, in_src, Y, ldy, H, F, elr, R, ldr, bias, slope,
+                 mode, out, attn, out_amax, out_row_amax, stream, nullptr);
 }

@@ -131,16 +131,20 @@ timer = KernelTimer()
 call_tag = [None]  # set by callers to attach per-call metadata (e.g. bytes moved) to a timing
 
 
-def call(name, *args):
-    """Invoke an int-returning entry point; raise MvmlError with mvml_last_error() on failure."""
+def call(name, *args, timed_as=None):
+    """Invoke an int-returning entry point; raise MvmlError with mvml_last_error() on failure.
+    timed_as: the entry point whose timings this call is filed under (a variant of it, such as
+    the row-mapped aggregation entries: the timer's consumers keep one figure per operation)."""
     fn = getattr(lib(), name)
     tag, call_tag[0] = call_tag[0], None
-    if name in timer.names:
+    tname = timed_as or name
+    if tname in timer.names:
         s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         s.record()
         rc = fn(*args)
         e.record()
-        timer.record(name, s, e, tag)
+        if rc == 0:  # (a refused call launched nothing: the caller's fallback is what is timed)
+            timer.record(tname, s, e, tag)
     else:
         rc = fn(*args)
     if rc != 0:

@@ -14,7 +14,7 @@ which is what model.py:93 does with ``batch=None``.
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, functional
 from .functional import fold_padded
 
 
@@ -80,6 +80,66 @@ def pad_columns(v, device, mult=4):
     out.copy_(v, non_blocking=True)
     fold_padded(out, buf)
     return out
+
+
+class FeatMap:
+    """Class map of a resident feature buffer (mvml_feat_classes): cls[a] = the class of row a
+    (numbered by first occurrence), Xc[c] = the row of class c, count = the number of classes on
+    the device, C = the same number read back once, when the map was first built."""
+
+    __slots__ = ("buf", "cls", "Xc", "count", "C")
+
+    def __init__(self, buf):
+        n, ld = buf.shape
+        self.buf = buf
+        self.cls = torch.empty(max(n, 1), dtype=torch.int32, device=buf.device)
+        self.Xc = torch.zeros((L_MAX_CLASSES, ld), dtype=torch.float32, device=buf.device)
+        self.count = torch.zeros(1, dtype=torch.int32, device=buf.device)
+        self.C = 0
+
+    def build(self):
+        """(Re)number the rows on the current stream; no host synchronisation."""
+        buf = self.buf
+        wp, wn = _lib.ws_ptr_size(_lib.lib().mvml_feat_classes_workspace_size(), buf.device)
+        # Filed under mvml_build_node_groups' timings: the timer's consumers sum the collation
+        # from build_csr + build_node_groups, and the class build is part of the collation.  With a
+        # map, kernel_ms_per_step["mvml_build_node_groups"] is therefore node groups + class build
+        # (config 3: 0.04 + 0.78 ms), not that entry alone.
+        _lib.call("mvml_feat_classes", buf.shape[0], _lib.ptr(buf), buf.shape[1], _lib.ptr(self.cls),
+                  _lib.ptr(self.Xc), _lib.ptr(self.count), wp, wn, _lib.stream_ptr(buf.device),
+                  timed_as="mvml_build_node_groups")
+
+
+L_MAX_CLASSES = 1024     # MVML_MAX_FEAT_CLASSES
+L_CLASS_MAX_LD = 80      # MVML_FEAT_CLASS_MAX_LD
+FEAT_MAP_MIN_ROWS = 8    # a map is kept when N >= this many rows per class
+
+
+def feature_buffer(v):
+    """The buffer a GAT layer reads device feature tensor v from: its zero-padded buffer where it
+    has one (pad_columns), else v itself; None for anything but a 2-D float32 device tensor."""
+    if not (v.dim() == 2 and v.dtype == torch.float32 and v.is_cuda):
+        return None
+    buf = functional.zero_padded(v, (v.shape[1] + 3) // 4 * 4)
+    return v if buf is None else buf
+
+
+def feat_map(buf):
+    """The class map of the feature buffer buf, built here with one read-back of the class count,
+    or None: MVML_FEAT_CLASSES=0, not a contiguous [N, <= 80] buffer of 16-B rows, more classes
+    than the capacity or fewer than FEAT_MAP_MIN_ROWS rows per class."""
+    if not functional.FEAT_CLASSES or not hasattr(_lib.lib(), "mvml_feat_classes"):
+        return None
+    n, ld = buf.shape
+    if not (buf.is_contiguous() and ld % 4 == 0 and 4 <= ld <= L_CLASS_MAX_LD and buf.data_ptr() % 16 == 0):
+        return None
+    fm = FeatMap(buf)
+    fm.build()
+    fm.C = int(fm.count.item())  # the one read-back per feature buffer
+    if not (1 <= fm.C <= L_MAX_CLASSES and n >= FEAT_MAP_MIN_ROWS * fm.C):
+        return None
+    functional.fold_classes(buf, fm)
+    return fm
 
 
 def _edge_data(v, device):
@@ -194,6 +254,32 @@ class BatchedMolGraph:
         self.edata = {k: _edge_data(v, device) for k, v in self.edata.items()}
         return self
 
+    def feat_map_for(self, buf):
+        """The class map of buf if it is the buffer of one of this batch's per-atom feature
+        tensors (feature_buffer), else None.  Built, and whether it applies decided, the first
+        time a layer asks for it (a GAT layer handed the buffer: functional.feat_map_of), so
+        batches that only feed other convolutions never pay for it; recollate() rebuilds the
+        maps that exist."""
+        d = self.__dict__.get("_dev")
+        if d is None:
+            return None
+        known = d.setdefault("feat_map_cache", [])  # (buffer, its map or None)
+        for b, fm in known:
+            if b is buf:
+                return fm
+        if buf.shape[0] != self.num_nodes() or not any(feature_buffer(v) is buf for v in self.ndata.values()):
+            return None
+        with torch.cuda.device(buf.device):
+            fm = feat_map(buf)
+        known.append((buf, fm))
+        return fm
+
+    @property
+    def feat_maps(self):
+        """The class maps this batch carries."""
+        d = self.__dict__.get("_dev") or {}
+        return [fm for _, fm in d.get("feat_map_cache", ()) if fm is not None]
+
     def _build_device(self, device):
         B, N, E = self.batch_size, self.num_nodes(), self.num_edges()
         if N >= 2 ** 31 or E >= 2 ** 31:
@@ -263,6 +349,9 @@ class BatchedMolGraph:
                   P(d["out_rowptr"]), P(d["out_dst"]), P(d["out_inslot"]), P(flags), wp, wn, st)
         _lib.call("mvml_build_node_groups", B, N, P(d["node_offsets"]), P(d["in_rowptr"]),
                   P(d["node_groups"]), st)
+        if functional.FEAT_CLASSES:
+            for fm in self.feat_maps:  # the class maps are part of the collation
+                fm.build()
 
     def group_offsets_rows(self):
         """GraphNorm group offsets in molecules (rows of the (B, 2D) readout)."""

@@ -103,18 +103,22 @@ def _row_pitch(cols):
     return (cols + 63) // 64 * 64
 
 
-def agg_fwd_bytes(N, E, H, F, out_cols, res_cols):
+def agg_fwd_bytes(N, E, H, F, out_cols, res_cols, table_rows=None):
     """Algorithmic HBM bytes of one mvml_gat_agg_fwd: read Z and R once,
     rowptr, src ids, el/er; write the layer output and the saved attention.  R is the
-    head-mean residual (F columns) in mean mode."""
-    return 4 * (N * H * F + N * res_cols + 2 * N * H + (N + 1) + E + N * out_cols + E * H)
+    head-mean residual (F columns) in mean mode.  table_rows (mvml_gat_agg_fwd_map): Z and R are
+    the rows of a table read once, plus one row index per atom."""
+    zr = (H * F + res_cols) * (N if table_rows is None else table_rows) + (0 if table_rows is None else N)
+    return 4 * (zr + 2 * N * H + (N + 1) + E + N * out_cols + E * H)
 
 
-def agg_bwd_bytes(N, E, H, F, gout_cols, mode):
+def agg_bwd_bytes(N, E, H, F, gout_cols, mode, table_rows=None):
     """Algorithmic bytes of mvml_gat_agg_bwd: read Z, el/er, g_out (+ out for ELU'), the saved
-    attention, both CSRs; write gY = [dZ_agg | dR | d el | d er]."""
+    attention, both CSRs; write gY = [dZ_agg | dR | d el | d er].  table_rows
+    (mvml_gat_agg_bwd_map): Z is the rows of a table read once, plus one row index per atom."""
     rw = F if mode == MODE_MEAN else H * F
-    reads = N * H * F + 2 * N * H + N * gout_cols + (N * H * F if mode == 0 else 0) + E * H
+    z = N * H * F if table_rows is None else table_rows * H * F + N
+    reads = z + 2 * N * H + N * gout_cols + (N * H * F if mode == 0 else 0) + E * H
     idx = 2 * (N + 1) + 3 * E
     writes = N * (H * F + rw + 2 * H)
     return 4 * (reads + idx + writes)
@@ -179,6 +183,43 @@ def zero_padded(X, Fp):
 def fold_padded(out, buf):
     """Record that out is the [:, :F] view of the zero-padded buffer buf."""
     _remember(out, "_mvml_padded", buf)
+
+
+# Layer 1 over the distinct atom-feature rows: a device batch numbers the rows of its resident
+# feature buffer (batching.FeatMap, csrc/feat_classes.hip: a few hundred classes among 1.75 M
+# atoms); the GAT layer that is handed that buffer projects one row per class and the aggregation
+# reads the table through the class ids (mvml_gat_agg_fwd_map / mvml_gat_agg_bwd_map) — bitwise
+# the materialised path.  MVML_FEAT_CLASSES=0: no map is built or used.
+FEAT_CLASSES = os.environ.get("MVML_FEAT_CLASSES", "1") != "0"
+
+
+def fold_classes(buf, fm):
+    """Record that fm numbers the rows of the feature buffer buf."""
+    _remember(buf, "_mvml_classes", fm)
+
+
+def feat_map_of(g, Xp):
+    """The class map of Xp's rows if Xp is batch g's own feature buffer (the batch builds the map
+    the first time it is asked: BatchedMolGraph.feat_map_for), unchanged since the map was
+    recorded (same rule as known_amax), else None."""
+    ask = getattr(g, "feat_map_for", None) if FEAT_CLASSES else None
+    fm = ask(Xp) if ask is not None else None
+    rec = _recall(Xp, "_mvml_classes") if fm is not None else None
+    return fm if rec is not None and rec[0] is fm else None
+
+
+def map_layout_ok(sep, bias):
+    """Whether the row-mapped aggregation entries take this layer: the projection-row layout with
+    a bias (they refuse the separate-residual instances: identity / no residual, no bias)."""
+    return not sep and bias is not None
+
+
+def gather_rows(table, ld, cols, idx, rows, offset=0, ldd=None):
+    """out[r, :cols] = table[idx[r], offset : offset + cols] (mvml_gather_rows); out [rows, ldd]."""
+    out = torch.empty((rows, ldd or cols), dtype=torch.float32, device=table.device)
+    call("mvml_gather_rows", rows, cols, ctypes.c_void_p(table.data_ptr() + 4 * offset), ld, ptr(idx),
+         ptr(out), ldd or cols, _stream(table.device))
+    return out
 
 
 def fold_rows(out, rows):
@@ -505,6 +546,9 @@ class GATLayerFunction(torch.autograd.Function):
         ax = None  # (tensor, slot) of max |X|
         xr = None  # per-row max |X| bits (ROW_SCALES)
         wil = None  # Wcat's interleaved split image (BSPLIT_IL)
+        # the batch's own feature buffer with a class map: one projection row per class
+        fm = feat_map_of(g, Xp) if ((algo or GEMM_ALGO) == "f16x2" and ROW_SCALES
+                                    and map_layout_ok(sep, bias)) else None
         if (algo or GEMM_ALGO) == "f16x2":
             amx = zeros(4, dtype=torch.int32, device=dev)  # [X, Wcat, gY (bwd), out]
             if ROW_SCALES:
@@ -514,9 +558,14 @@ class GATLayerFunction(torch.autograd.Function):
                 # zeros): computed once and recorded on the feature tensor itself.  (Xp's pad
                 # columns are zeros: the whole padded row, float4 loads, has the same |max| as
                 # its Fin features)
-                xr = _row_scales(X, Xp, N, Fp, amx)
-                if not X.requires_grad:
-                    fold_rows(X, xr)
+                if fm is not None:
+                    # the class rows' scales; their max is max |X| (the same set of rows)
+                    xr = absmax_rows(fm.Xc, fm.C, Fp, Fp)
+                    absmax(xr, fm.C, 1, 1, amx, 0)
+                else:
+                    xr = _row_scales(X, Xp, N, Fp, amx)
+                    if not X.requires_grad:
+                        fold_rows(X, xr)
                 ax = (amx, 0)
             else:
                 ax = known_amax(Xp) if Xp is X else None  # layer 2: folded by layer 1's aggregation
@@ -542,8 +591,13 @@ class GATLayerFunction(torch.autograd.Function):
             # tile leaves through the LDS epilogue instead of the logit-partial one's column
             # stores (9.5 -> ~5 ms per config-3 layer-2 launch)
             ldy = _row_pitch(C + 2 * H)
-            Y = torch.empty((N, ldy), dtype=torch.float32, device=dev)
-            if xr is not None:
+            Y = torch.empty((N if fm is None else fm.C, ldy), dtype=torch.float32, device=dev)
+            if fm is not None:
+                # Y[c] = the projection of class c's row: a row of the product depends on that row,
+                # the weights and its scale only, so Y[cls[a]] is bitwise atom a's projection
+                gemm(fm.Xc, Wcat, fm.C, C + 2 * H, Fp, 0, 0, Fp, Fp, Y, ldy, amax=(None, slot(amx, 1)),
+                     arows=xr, bil4=wil, role="gat_proj")
+            elif xr is not None:
                 gemm(Xp, Wcat, N, C + 2 * H, Fp, 0, 0, Fp, Fp, Y, ldy, amax=(None, slot(amx, 1)),
                      arows=xr, bil4=wil, role="gat_proj")
             elif amx is not None:
@@ -552,8 +606,11 @@ class GATLayerFunction(torch.autograd.Function):
                 gemm(Xp, Wcat, N, C + 2 * H, Fp, 0, 0, Fp, Fp, Y, ldy, algo="bf16")
             # (a native slice copy: torch's strided copy splits into 32-bit-indexable pieces,
             # 8 launches for a 1.75 M-atom batch)
-            elr = torch.empty((N, 2 * H), dtype=torch.float32, device=dev)
-            call("mvml_copy_cols", N, 2 * H, ptr(Y[:, C:]), ldy, ptr(elr), 2 * H, st)
+            if fm is not None:
+                elr = gather_rows(Y, ldy, 2 * H, fm.cls, N, offset=C)
+            else:
+                elr = torch.empty((N, 2 * H), dtype=torch.float32, device=dev)
+                call("mvml_copy_cols", N, 2 * H, ptr(Y[:, C:]), ldy, ptr(elr), 2 * H, st)
         else:
             ldy = _row_pitch(C)
             Y = torch.empty((N, ldy), dtype=torch.float32, device=dev)
@@ -573,19 +630,33 @@ class GATLayerFunction(torch.autograd.Function):
         # (identity), or none
         rw = out_cols
         R, ldr = _identity_residual(Xp, H, F, mean_res, st) if res_kind == RES_IDENTITY else (None, 0)
-        _lib.call_tag[0] = {"layer": f"H{H}xF{F}",
-                            "bytes": agg_fwd_bytes(N, E, H, F, out_cols, 0 if res_kind == RES_NONE else rw)}
         with _fwd_path(g, mode):
-            if not sep and bias is not None:
-                call("mvml_gat_agg_fwd", N, ptr(g.node_groups), g.num_node_groups, ptr(g.in_rowptr),
-                     ptr(g.in_src), ptr(Y), ldy, H, F, ptr(elr), ptr(_c(bias)), float(slope), int(mode),
-                     ptr(out), ptr(attn), slot(amx, 3), ptr(orows), st)
-            else:
-                rp = ctypes.c_void_p(Y.data_ptr() + 4 * HF) if not sep else ptr(R)
-                call("mvml_gat_agg_fwd_res", N, ptr(g.node_groups), g.num_node_groups, ptr(g.in_rowptr),
-                     ptr(g.in_src), ptr(Y), ldy, H, F, ptr(elr), rp, ldr if sep else ldy,
-                     ptr(_c(bias)) if bias is not None else None, float(slope), int(mode),
-                     ptr(out), ptr(attn), slot(amx, 3), ptr(orows), st)
+            while True:
+                # yrow: the aggregation reads atom a's projection row at Y[yrow[a]] (the *_map
+                # entries, filed under the plain entry's timings); a path that has no row-mapped
+                # instances refuses before it launches anything, and Y is materialised instead
+                yrow = None if fm is None else fm.cls
+                sfx, extra = ("", ()) if yrow is None else ("_map", (ptr(yrow),))
+                _lib.call_tag[0] = {"layer": f"H{H}xF{F}",
+                                    "bytes": agg_fwd_bytes(N, E, H, F, out_cols, 0 if res_kind == RES_NONE else rw,
+                                                           None if fm is None else fm.C)}
+                try:
+                    if not sep and bias is not None:
+                        call("mvml_gat_agg_fwd" + sfx, N, ptr(g.node_groups), g.num_node_groups, ptr(g.in_rowptr),
+                             ptr(g.in_src), ptr(Y), ldy, H, F, ptr(elr), ptr(_c(bias)), float(slope), int(mode),
+                             ptr(out), ptr(attn), slot(amx, 3), ptr(orows), st, *extra, timed_as="mvml_gat_agg_fwd")
+                    else:
+                        rp = ctypes.c_void_p(Y.data_ptr() + 4 * HF) if not sep else ptr(R)
+                        call("mvml_gat_agg_fwd_res" + sfx, N, ptr(g.node_groups), g.num_node_groups,
+                             ptr(g.in_rowptr), ptr(g.in_src), ptr(Y), ldy, H, F, ptr(elr), rp, ldr if sep else ldy,
+                             ptr(_c(bias)) if bias is not None else None, float(slope), int(mode),
+                             ptr(out), ptr(attn), slot(amx, 3), ptr(orows), st, *extra,
+                             timed_as="mvml_gat_agg_fwd_res")
+                    break
+                except _lib.MvmlError as e:
+                    if fm is None or "the row map needs" not in str(e):  # the entry's own refusal only
+                        raise
+                    Y, fm = gather_rows(Y, ldy, ldy, fm.cls, N), None
         if amx is not None:  # max |out| for the consumer's split-fp16 GEMMs (next layer, Set2Set)
             fold_amax(out, amx, 3)
         if orows is not None:
@@ -599,6 +670,7 @@ class GATLayerFunction(torch.autograd.Function):
             _remember(out, "_mvml_elu", ctx.link)
         if DEBUG_CAPTURE is not None:
             DEBUG_CAPTURE.setdefault("elr_fwd", []).append(elr.detach().clone())
+            DEBUG_CAPTURE.setdefault("mapped_fwd", []).append((fm is not None, Y.shape[0]))
         ctx.save_for_backward(Xp, Wcat, Y, attn, elr, out, attn_l, attn_r, attn_lr)
         ctx.Fin = Fin
         ctx.g, ctx.H, ctx.F, ctx.slope, ctx.mode, ctx.ldy = g, H, F, slope, mode, ldy
@@ -607,12 +679,14 @@ class GATLayerFunction(torch.autograd.Function):
         ctx.amx = amx
         ctx.ax = ax
         ctx.wil = wil
+        ctx.yrow = None if fm is None else fm.cls  # Y is the class table: rows through yrow
         return out
 
     @staticmethod
     def backward(ctx, g_out):
         Xp, Wcat, Y, attn, elr, out, attn_l, attn_r, attn_lr = ctx.saved_tensors
         g, H, F, mode, ldy = ctx.g, ctx.H, ctx.F, ctx.mode, ctx.ldy
+        yrow = ctx.yrow
         link = ctx.link
         if link is not None and link.claimed:
             # the next layer's data-gradient GEMM applied ELU' already: g_out IS g_rst, and the
@@ -648,8 +722,6 @@ class GATLayerFunction(torch.autograd.Function):
         if ctx.amx is not None and ROW_SCALES and (ctx.needs_input_grad[0] or flat_src):
             # (the source-atom kernels then form max |gY| from the row maxima: no per-block atomics)
             gyr = torch.empty(max(N, 1), dtype=torch.int32, device=dev)
-        _lib.call_tag[0] = {"layer": f"H{H}xF{F}",
-                            "bytes": agg_bwd_bytes(N, g.num_edges(), H, F, g_out.shape[1], mode)}
         # Identity / absent residual: dR leaves through gR (mvml_gat_agg_bwd_res).  A flatten
         # layer's gR = g_rst is the identity residual's share of dL/dX — written straight into gX,
         # which the data-gradient product below then accumulates onto (beta = 1) — and its column
@@ -664,17 +736,31 @@ class GATLayerFunction(torch.autograd.Function):
             elif has_bias:
                 gR, ldgr = torch.empty((N, HF), dtype=torch.float32, device=dev), HF
         with (_lib.option("flat_src", 2) if flat_src else contextlib.nullcontext()):
-            if sep:
-                call("mvml_gat_agg_bwd_res", N, ptr(g.node_groups), g.num_node_groups, ptr(g.in_rowptr),
-                     ptr(g.in_src), ptr(g.out_rowptr), ptr(g.out_dst), ptr(g.out_inslot), ptr(Y), ldy,
-                     ptr(elr), ptr(attn), ptr(out), ptr(g_out), H, F, float(ctx.slope), int(mode), ptr(gY),
-                     ldg, C, ptr(gR), ldgr, slot(ctx.amx, 2), ptr(gyr), wp, wn, st)
-            else:
-                call("mvml_gat_agg_bwd", N, ptr(g.node_groups), g.num_node_groups, ptr(g.in_rowptr),
-                     ptr(g.in_src), ptr(g.out_rowptr), ptr(g.out_dst), ptr(g.out_inslot), ptr(Y), ldy,
-                     ptr(elr), ptr(attn), ptr(out), ptr(g_out), H, F, float(ctx.slope), int(mode), ptr(gY),
-                     ldg, slot(ctx.amx, 2), ptr(gyr), wp, wn, st)
+            while True:  # (yrow: as in the forward)
+                sfx, extra = ("", ()) if yrow is None else ("_map", (ptr(yrow),))
+                _lib.call_tag[0] = {"layer": f"H{H}xF{F}",
+                                    "bytes": agg_bwd_bytes(N, g.num_edges(), H, F, g_out.shape[1], mode,
+                                                           None if yrow is None else Y.shape[0])}
+                try:
+                    if sep:
+                        call("mvml_gat_agg_bwd_res" + sfx, N, ptr(g.node_groups), g.num_node_groups,
+                             ptr(g.in_rowptr), ptr(g.in_src), ptr(g.out_rowptr), ptr(g.out_dst), ptr(g.out_inslot),
+                             ptr(Y), ldy, ptr(elr), ptr(attn), ptr(out), ptr(g_out), H, F, float(ctx.slope),
+                             int(mode), ptr(gY), ldg, C, ptr(gR), ldgr, slot(ctx.amx, 2), ptr(gyr), wp, wn, st,
+                             *extra, timed_as="mvml_gat_agg_bwd_res")
+                    else:
+                        call("mvml_gat_agg_bwd" + sfx, N, ptr(g.node_groups), g.num_node_groups, ptr(g.in_rowptr),
+                             ptr(g.in_src), ptr(g.out_rowptr), ptr(g.out_dst), ptr(g.out_inslot), ptr(Y), ldy,
+                             ptr(elr), ptr(attn), ptr(out), ptr(g_out), H, F, float(ctx.slope), int(mode), ptr(gY),
+                             ldg, slot(ctx.amx, 2), ptr(gyr), wp, wn, st, *extra, timed_as="mvml_gat_agg_bwd")
+                    break
+                except _lib.MvmlError as e:
+                    if yrow is None or "the row map needs" not in str(e):
+                        raise
+                    Y, yrow = gather_rows(Y, ldy, ldy, yrow, N), None
         amx = ctx.amx  # slot 2 = max |gY|, folded in by mvml_gat_agg_bwd's stores
+        if DEBUG_CAPTURE is not None:
+            DEBUG_CAPTURE.setdefault("mapped_bwd", []).append(yrow is not None)
         if DEBUG_CAPTURE is not None and amx is not None:
             DEBUG_CAPTURE.setdefault("gy_amax", []).append((gY[:, :CE].clone(), amx[2:3].clone()))
             if gyr is not None:

@@ -51,7 +51,10 @@ def _pattern(name, pat):
     if base not in name:
         return False
     if "lds_kernel" in base:
-        return ("true>" in name) == big
+        # BIG is the seventh template argument of both window kernels (<H, .., WIN, ECAP, BIG, ...>;
+        # SEP / MAP follow it)
+        args = name[name.index("<") + 1:name.rindex(">")].split(",") if "<" in name else []
+        return (len(args) > 6 and args[6].strip() == "true") == big
     return True
 
 
