@@ -1391,6 +1391,13 @@ int mvml_attn_pool_bwd(int64_t B, int64_t N, int D, const int64_t* node_offsets,
  *   (every row written; the b2 part's share is not included).
  * mvml_nnconv_bwd_weight: dW2[(i, o), k] (+)= sum_s z[s][k] h_u[i] g_out[v][o]; fp32 MFMA over
  *   edge ranges, the partials summed in fixed order.
+ * mvml_nnconv_bwd_weight_f16x2 (csrc/nnconv_wgrad.hip): the same sum, same limits, refusals,
+ *   num_edges == 0 behaviour and `accumulate`, on split-fp16 MFMA (three products) under three
+ *   global power-of-two scales (max |h|, max |g_out| over the rows the edges use, max |z|).  It reads
+ *   z through z_image, the split and transposed copy that mvml_nnconv_split_z makes of the SAME
+ *   num_edges, H and z: mvml_nnconv_z_image_bytes(num_edges, H) bytes (0: bad shape; 256 + 4 H bytes
+ *   per edge, in whole 32-edge chunks), made once per z and shared by every step that uses it.
+ *   z_image may be NULL only without edges.
  * ------------------------------------------------------------------------------------- */
 size_t mvml_nnconv_image_bytes(int D, int H);
 int mvml_nnconv_split_w2(int D, int H, const float* W2, void* image, void* stream);
@@ -1412,6 +1419,15 @@ int mvml_nnconv_bwd_weight(int64_t num_edges, const int32_t* in_src, const int32
                            const float* h, int64_t ldh, int D, const float* z, int64_t ldz, int H,
                            const float* g_out, int64_t ldg, int accumulate, float* dW2,
                            void* workspace, size_t workspace_bytes, void* stream);
+size_t mvml_nnconv_z_image_bytes(int64_t num_edges, int H);
+int mvml_nnconv_split_z(int64_t num_edges, int H, const float* z, int64_t ldz, void* image,
+                        void* stream);
+size_t mvml_nnconv_bwd_weight_f16x2_workspace_size(int64_t num_edges, int D, int H);
+int mvml_nnconv_bwd_weight_f16x2(int64_t num_edges, const int32_t* in_src, const int32_t* slot_dst,
+                                 const float* h, int64_t ldh, int D, const float* z, int64_t ldz,
+                                 int H, const float* g_out, int64_t ldg, int accumulate, float* dW2,
+                                 void* workspace, size_t workspace_bytes, void* stream,
+                                 const void* z_image);
 
 /* ---------------------------------------------------------------------------------------
  * D-MPNN, the directed bond-message network (Chemprop v1 MPNEncoder, bond messages, directed,

@@ -2706,6 +2706,24 @@ def nnconv_check(who, D, H):
             raise ValueError(f"{who}: {what} must be a multiple of 16 in [16, {hi}] on the HIP path (got {v})")
 
 
+NNCONV_WEIGHT_GRADS = ("fp32", "split_fp16")  # mvml_nnconv_bwd_weight, mvml_nnconv_bwd_weight_f16x2
+
+
+def nnconv_weight_grad(value):
+    if value not in NNCONV_WEIGHT_GRADS:
+        raise ValueError(f"NNConv: weight_grad must be one of {NNCONV_WEIGHT_GRADS} (got {value!r})")
+    return value
+
+
+def nnconv_z_image(z, E):
+    """max |z| and z split and transposed into MFMA fragment order (mvml_nnconv_split_z): 4 H bytes per
+    edge, the operand of mvml_nnconv_bwd_weight_f16x2."""
+    H = z.shape[1]
+    img = torch.empty(_lib.lib().mvml_nnconv_z_image_bytes(E, H), dtype=torch.uint8, device=z.device)
+    call("mvml_nnconv_split_z", E, H, ptr(z), z.stride(0), ptr(img), _stream(z.device))
+    return img
+
+
 def nnconv_flops(E, D, H):
     """2 H D^2 per edge: the flops of one of the three NNConv products (the MFMA work of the
     split-fp16 kernels is three times that, before their K padding)."""
@@ -2737,10 +2755,13 @@ def nnconv_image(W2, D, H):
 class NNConvShared:
     """What the message-passing steps of one MPNNGNN forward share: W2's image (split once) and, in
     the backward, ONE dz, dW2, db2 and dbias that every step's kernels add onto (their accumulate
-    flag), handed to autograd by the step whose backward runs last."""
+    flag), handed to autograd by the step whose backward runs last.  weight_grad "split_fp16" runs
+    dW2 on mvml_nnconv_bwd_weight_f16x2: z's image (mvml_nnconv_split_z) is made by the first backward,
+    reused by every step's and dropped with the last."""
 
-    def __init__(self, image, steps):
+    def __init__(self, image, steps, weight_grad="fp32"):
         self.image, self.steps, self.done = image, steps, 0
+        self.weight_grad, self.z_image = nnconv_weight_grad(weight_grad), None
 
     def alloc(self, E, D, H, dev):
         f32 = dict(dtype=torch.float32, device=dev)
@@ -2787,10 +2808,18 @@ def nnconv_backward(g, h, z, b2, image, S, out, g_out, act, acc, accumulate):
     _lib.call_tag[0] = {"layer": f"D{D}xH{H}", "flops": 2 * nnconv_flops(E, D, H)}
     call("mvml_nnconv_bwd_data", N, E, ptr(g.in_src), ptr(sd), ptr(g.out_rowptr), ptr(g.out_inslot), ptr(h), h.stride(0),
          D, ptr(z), z.stride(0), H, ptr(image), ptr(g_pre), D, int(accumulate), ptr(acc.dz), H, ptr(dH), D, wp, wn, st)
-    wp, wn = _lib.ws_ptr_size(L.mvml_nnconv_bwd_weight_workspace_size(E, D, H), dev)
-    _lib.call_tag[0] = {"layer": f"D{D}xH{H}", "flops": nnconv_flops(E, D, H)}
-    call("mvml_nnconv_bwd_weight", E, ptr(g.in_src), ptr(sd), ptr(h), h.stride(0), D, ptr(z), z.stride(0), H, ptr(g_pre), D,
-         int(accumulate), ptr(acc.dW2), wp, wn, st)
+    if acc.weight_grad == "split_fp16":
+        if acc.z_image is None:
+            acc.z_image = nnconv_z_image(z, E)
+        wp, wn = _lib.ws_ptr_size(L.mvml_nnconv_bwd_weight_f16x2_workspace_size(E, D, H), dev)
+        _lib.call_tag[0] = {"layer": f"D{D}xH{H}", "flops": nnconv_flops(E, D, H)}
+        call("mvml_nnconv_bwd_weight_f16x2", E, ptr(g.in_src), ptr(sd), ptr(h), h.stride(0), D, ptr(z), z.stride(0), H,
+             ptr(g_pre), D, int(accumulate), ptr(acc.dW2), wp, wn, st, ptr(acc.z_image))
+    else:
+        wp, wn = _lib.ws_ptr_size(L.mvml_nnconv_bwd_weight_workspace_size(E, D, H), dev)
+        _lib.call_tag[0] = {"layer": f"D{D}xH{H}", "flops": nnconv_flops(E, D, H)}
+        call("mvml_nnconv_bwd_weight", E, ptr(g.in_src), ptr(sd), ptr(h), h.stride(0), D, ptr(z), z.stride(0), H, ptr(g_pre),
+             D, int(accumulate), ptr(acc.dW2), wp, wn, st)
     # the b2 part, out += S view(b2): dB2 = S^T g, dS = g B2^T, dh += the sum of dS over the out-edges
     beta = 1.0 if accumulate else 0.0
     gemm(S, g_pre, D, D, N, 1, 1, D, D, acc.db2, D, beta=beta)
@@ -2840,6 +2869,7 @@ class NNConvFunction(torch.autograd.Function):
         acc.done += 1
         if acc.done < acc.steps:  # a later backward hands the sums over
             return dH, None, None, None, None, None, None, None
+        acc.z_image = None
         return dH, acc.dz[:E], acc.dW2, acc.db2, acc.dbias if has_bias else None, None, None, None
 
 

@@ -1227,10 +1227,15 @@ class NNConv(nn.Module):
     [in_feats, out_feats] matrices are never in memory.  forward(graph, feat, efeat) -> (N,
     out_feats); efeat is a float [E, edge_in_feats] tensor in edge-id order.  Refused at
     construction: in_feats != out_feats (and bipartite inputs with them), widths that are not
-    multiples of 16 or above 128 (H: 256), another aggregator, residual=True."""
+    multiples of 16 or above 128 (H: 256), another aggregator, residual=True.  weight_grad (after
+    dgl's arguments): the kernel of edge_func[2].weight's gradient, "fp32" (fp32 MFMA, the default) or
+    "split_fp16" (split-fp16 MFMA on a pre-split image of the edge rows, 4 H bytes per edge during
+    the backward); anything else is a ValueError."""
 
-    def __init__(self, in_feats, out_feats, edge_func, aggregator_type="sum", residual=False, bias=True):
+    def __init__(self, in_feats, out_feats, edge_func, aggregator_type="sum", residual=False, bias=True,
+                 weight_grad="fp32"):
         super().__init__()
+        self.weight_grad = Fn.nnconv_weight_grad(weight_grad)
         if isinstance(in_feats, (tuple, list)) or in_feats != out_feats:
             raise ValueError(f"NNConv: in_feats must equal out_feats on the HIP path, bipartite inputs are not "
                              f"implemented (got {in_feats}, {out_feats})")
@@ -1267,9 +1272,12 @@ class NNConv(nn.Module):
     def shared(self, steps):
         """The NNConvShared of `steps` applications of this layer in one forward."""
         w2 = self.edge_func[2].weight
-        return Fn.NNConvShared(Fn.nnconv_image(w2.detach().contiguous(), self._out_feats, w2.shape[1]), steps)
+        return Fn.NNConvShared(Fn.nnconv_image(w2.detach().contiguous(), self._out_feats, w2.shape[1]), steps,
+                               self.weight_grad)
 
     def fused(self, graph, feat, z, act=False, shared=None):
+        if shared is None and self.weight_grad != "fp32":  # a lone step carries its own z image
+            shared = self.shared(1)
         return Fn.NNConvFunction.apply(feat, z, self.edge_func[2].weight, self.edge_func[2].bias, self.bias, graph,
                                        act, shared)
 
@@ -1283,10 +1291,11 @@ class MPNNGNN(nn.Module):
     h = GRU(relu(gnn_layer(g, h, e)), h) with ONE NNConv and ONE single-layer GRU shared by all
     steps.  forward(g, node_feats, edge_feats) -> (N, node_out_feats); edge_feats is a float [E,
     edge_in_feats] tensor in edge-id order.  Refused at construction: node_out_feats no multiple of
-    16 in [16, 128], edge_hidden_feats none in [16, 256], more than 32 bond features."""
+    16 in [16, 128], edge_hidden_feats none in [16, 256], more than 32 bond features.  weight_grad
+    (after dgllife's arguments): NNConv's."""
 
     def __init__(self, node_in_feats, edge_in_feats, node_out_feats=64, edge_hidden_feats=128,
-                 num_step_message_passing=6):
+                 num_step_message_passing=6, weight_grad="fp32"):
         super().__init__()
         Fn.nnconv_check("MPNNGNN", node_out_feats, edge_hidden_feats)
         D = node_out_feats
@@ -1294,7 +1303,8 @@ class MPNNGNN(nn.Module):
         self.num_step_message_passing = num_step_message_passing
         edge_network = nn.Sequential(nn.Linear(edge_in_feats, edge_hidden_feats), nn.ReLU(),
                                      nn.Linear(edge_hidden_feats, D * D))
-        self.gnn_layer = NNConv(in_feats=D, out_feats=D, edge_func=edge_network, aggregator_type="sum")
+        self.gnn_layer = NNConv(in_feats=D, out_feats=D, edge_func=edge_network, aggregator_type="sum",
+                                weight_grad=weight_grad)
         self.gru = nn.GRU(D, D)
 
     def reset_parameters(self):
@@ -1328,13 +1338,15 @@ class MPNNGNN(nn.Module):
 class MPNNPredictor(nn.Module):
     """dgllife.model.model_zoo.mpnn_predictor.MPNNPredictor (0.3.0; restated, parity with dgllife
     is unpinned): gnn = MPNNGNN -> readout = Set2Set -> predict = Sequential(Linear(2 D, D), ReLU,
-    Linear(D, n_tasks)).  forward(g, node_feats, edge_feats) returns (B, n_tasks)."""
+    Linear(D, n_tasks)).  forward(g, node_feats, edge_feats) returns (B, n_tasks).  weight_grad
+    (after dgllife's arguments): NNConv's."""
 
     def __init__(self, node_in_feats, edge_in_feats, node_out_feats=64, edge_hidden_feats=128, n_tasks=1,
-                 num_step_message_passing=6, num_step_set2set=6, num_layer_set2set=3):
+                 num_step_message_passing=6, num_step_set2set=6, num_layer_set2set=3, weight_grad="fp32"):
         super().__init__()
         self.gnn = MPNNGNN(node_in_feats=node_in_feats, node_out_feats=node_out_feats, edge_in_feats=edge_in_feats,
-                           edge_hidden_feats=edge_hidden_feats, num_step_message_passing=num_step_message_passing)
+                           edge_hidden_feats=edge_hidden_feats, num_step_message_passing=num_step_message_passing,
+                           weight_grad=weight_grad)
         self.readout = Set2Set(input_dim=node_out_feats, n_iters=num_step_set2set, n_layers=num_layer_set2set)
         self.predict = nn.Sequential(nn.Linear(2 * node_out_feats, node_out_feats), nn.ReLU(),
                                      nn.Linear(node_out_feats, n_tasks))

@@ -5,7 +5,9 @@ On the config-3 batch with De = 10 seeded bond features, at D / H = 32/64, 64/12
   * mvml_nnconv_fwd, mvml_nnconv_bwd_data, mvml_nnconv_bwd_weight: ms per launch and the useful
     flops (2 H D^2 per edge and product; the data gradient is two products) as a fraction of the
     fp16 MFMA peak / 3 (the project's convention for fp32-accurate products, bench.py);
-  * one MPNNPredictor(39, 10, D, H) training step with FlatAdam;
+  * mvml_nnconv_bwd_weight_f16x2 (csrc/nnconv_wgrad.hip) beside the fp32 mvml_nnconv_bwd_weight in the
+    same interleaved windows, and mvml_nnconv_split_z (its z image) on its own;
+  * one MPNNPredictor(39, 10, D, H) training step with FlatAdam, with each weight_grad;
   * at --small-mols molecules (4,096: the per-edge matrices fit, E D^2 4 bytes), the forward against
     the materialised composition: the project's GEMM for W_e = z W2^T, then torch's bmm and
     index_add_.  That composition is timed here only; no module runs it.
@@ -62,24 +64,48 @@ def kernel_calls(g, D, H):
 
     def bwd_weight():
         call("mvml_nnconv_bwd_weight", E, ptr(g.in_src), ptr(sd), ptr(h), D, D, ptr(z), H, H, ptr(go), D, 0, ptr(dW2), *ws, st)
-    return {"fwd": fwd, "bwd_data": bwd_data, "bwd_weight": bwd_weight}, (h, z, W2, out)
+
+    # the split-fp16 form: its z image, a result of its own (compared below) and a workspace of its own
+    zimg = torch.empty(L.mvml_nnconv_z_image_bytes(E, H), dtype=torch.uint8, device="cuda")
+    dW2h = torch.empty_like(W2)
+    wsh = torch.empty(L.mvml_nnconv_bwd_weight_f16x2_workspace_size(E, D, H), dtype=torch.uint8, device="cuda")
+
+    def split_z():
+        call("mvml_nnconv_split_z", E, H, ptr(z), H, ptr(zimg), st)
+
+    def bwd_weight_f16x2():
+        call("mvml_nnconv_bwd_weight_f16x2", E, ptr(g.in_src), ptr(sd), ptr(h), D, D, ptr(z), H, H, ptr(go), D, 0, ptr(dW2h),
+             ptr(wsh), wsh.numel(), st, ptr(zimg))
+    split_z()
+    return ({"fwd": fwd, "bwd_data": bwd_data, "bwd_weight": bwd_weight, "bwd_weight_f16x2": bwd_weight_f16x2,
+             "split_z": split_z}, (h, z, W2, out, dW2, dW2h, zimg))
 
 
 def bench_kernels(g, D, H):
     E = g.num_edges()
-    calls, _ = kernel_calls(g, D, H)
-    tm = timed(calls, launches=2, reps=5, warm=1)
+    calls, ops = kernel_calls(g, D, H)
+    tm = timed(calls, launches=2, reps=5, warm=1)  # (the two weight gradients share every window)
     f = Fn.nnconv_flops(E, D, H)
-    return {"fwd": flops_row(f"nnconv_fwd D={D} H={H}", tm["fwd"], f),
-            "bwd_data": flops_row(f"nnconv_bwd_data D={D} H={H}", tm["bwd_data"], 2 * f),
-            "bwd_weight": flops_row(f"nnconv_bwd_weight D={D} H={H} (fp32 MFMA)", tm["bwd_weight"], f)}
+    dW2, dW2h, zimg = ops[4:]
+    res = {"fwd": flops_row(f"nnconv_fwd D={D} H={H}", tm["fwd"], f),
+           "bwd_data": flops_row(f"nnconv_bwd_data D={D} H={H}", tm["bwd_data"], 2 * f),
+           "bwd_weight": flops_row(f"nnconv_bwd_weight D={D} H={H} (fp32 MFMA)", tm["bwd_weight"], f),
+           "bwd_weight_f16x2": flops_row(f"nnconv_bwd_weight_f16x2 D={D} H={H}", tm["bwd_weight_f16x2"], f),
+           "split_z": row(f"nnconv_split_z H={H}", tm["split_z"], 4 * E * H + zimg.numel()),
+           "z_image_gb": zimg.numel() / 1e9,
+           "f16x2_vs_fp32_rel_diff": float((dW2h - dW2).abs().max() / dW2.abs().max())}
+    a, b = res["bwd_weight"], res["bwd_weight_f16x2"]
+    print(f"    fp32 / split-fp16 = {a['ms'] / b['ms']:.2f} (windows {a['min_ms']:.2f} .. {a['max_ms']:.2f} against "
+          f"{b['min_ms']:.2f} .. {b['max_ms']:.2f} ms); z image {res['z_image_gb']:.2f} GB; the two results differ by "
+          f"{res['f16x2_vs_fp32_rel_diff']:.1e} of max |dW2|")
+    return res
 
 
 def bench_materialised(g, D, H):
     """The fused forward against W_e in memory, at a batch where E D^2 4 bytes fit."""
     N, E = g.num_nodes(), g.num_edges()
-    calls, (h, z, W2, out) = kernel_calls(g, D, H)
-    We = torch.empty((E, D * D), device="cuda")
+    calls, (h, z, W2, out, *_) = kernel_calls(g, D, H)
+    We =torch.empty((E, D * D), device="cuda")
     src, dst = g.in_src.long(), Fn.nnconv_slot_dst(g).long()
 
     def composed():
@@ -97,17 +123,22 @@ def bench_materialised(g, D, H):
 
 
 def bench_step(g, D, H, x, e):
-    torch.manual_seed(0)
-    model = MPNNPredictor(FN, DE, node_out_feats=D, edge_hidden_feats=H, n_tasks=11).cuda().train()
-    opt = FlatAdam(model.parameters(), lr=1e-3)
+    """One training step with each weight_grad, the two models' steps interleaved window by window."""
     y = (torch.rand(g.batch_size, 11, device="cuda") < 0.5).float()
 
-    def step():
-        opt.zero_grad()
-        bce_with_logits(model(g, x, e), y).backward()
-        opt.step()
-    tm = timed({"step": step}, launches=2, reps=3, warm=1)
-    return {"step": row(f"MPNNPredictor D={D} H={H} step (FlatAdam)", tm["step"]),
+    def stepper(weight_grad):
+        torch.manual_seed(0)
+        model = MPNNPredictor(FN, DE, node_out_feats=D, edge_hidden_feats=H, n_tasks=11, weight_grad=weight_grad).cuda().train()
+        opt = FlatAdam(model.parameters(), lr=1e-3)
+
+        def step():
+            opt.zero_grad()
+            bce_with_logits(model(g, x, e), y).backward()
+            opt.step()
+        return step
+    tm = timed({wg: stepper(wg) for wg in Fn.NNCONV_WEIGHT_GRADS}, launches=2, reps=3, warm=1)
+    return {"step": row(f"MPNNPredictor D={D} H={H} step (FlatAdam)", tm["fp32"]),
+            "step_split_fp16": row(f'MPNNPredictor D={D} H={H} step, weight_grad="split_fp16"', tm["split_fp16"]),
             "max_memory_gb": torch.cuda.max_memory_allocated() / 1e9}
 
 
