@@ -1535,6 +1535,34 @@ int mvml_cfconv_agg(int64_t num_nodes, int64_t num_edges, const int32_t* rowptr,
 int mvml_ssp_fwd(int64_t n, const float* x, float* y, void* stream);
 int mvml_ssp_bwd(int64_t n, const float* y, const float* g_y, float* g_x, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Weave's Gaussian-histogram readout (dgllife 0.3.0 WeaveGather; restated, parity with dgllife
+ * unpinned; csrc/weave_gather.hip, DESIGN.md "Weave").  All fp32.  For x = X[n][f] and the K
+ * memberships (means[k], stds[k]):
+ *   q_k = exp(-(x - mean_k)^2 / (2 std_k^2)) + 1e-7,  p_k = q_k / sum_j q_j
+ *   out[g][f K + k] = sum of p_k(X[n][f]) over n in [node_offsets[g], node_offsets[g+1]) ascending,
+ *                     from 0, each add rounded once (the [N][F K] histogram is never in memory)
+ *   gX[n][f] = sum_k G[g][f K + k] (dq_k - p_k sum_j dq_j) / sum_j q_j,  dq_k = -(x - mean_k) / std_k^2 (q_k - 1e-7)
+ * means and stds are HOST arrays of K floats, read before the call returns and passed to the kernel
+ * by value; they take no gradient.  node_offsets int64[B+1] on the device (mvml_build_csr).  A
+ * molecule without atoms gives zeros and takes no gradient; every other gX row is written once.
+ * F a multiple of 4 in [4, 1024]; 1 <= K <= 16; every mean finite, every std > 0 with 1 / std^2 a
+ * finite float; X, out, G, gX 16-byte aligned with row pitches that are multiples of 4 and at least F
+ * (out, G: F K); B < 2^28, N < 2^31.  Anything else: MVML_ERR_INVALID before any launch, nothing
+ * written.  B == 0 (backward: or N == 0): MVML_OK, nothing written.  No atomics: bitwise repeatable,
+ * and a molecule's bits do not depend on the batch around it.
+ * mvml_tanh_fwd: y[i] = tanh(x[i]); mvml_tanh_bwd: g_x[i] = g_y[i] (1 - y[i]^2), from the output.
+ *   x == y and g_y == g_x are allowed.
+ * ------------------------------------------------------------------------------------- */
+int mvml_weave_gather_fwd(int64_t B, int64_t N, int F, int K, const float* means, const float* stds,
+                          const int64_t* node_offsets, const float* X, int64_t ldx, float* out,
+                          int64_t ldo, void* stream);
+int mvml_weave_gather_bwd(int64_t B, int64_t N, int F, int K, const float* means, const float* stds,
+                          const int64_t* node_offsets, const float* X, int64_t ldx, const float* G,
+                          int64_t ldg, float* gX, int64_t ldgx, void* stream);
+int mvml_tanh_fwd(int64_t n, const float* x, float* y, void* stream);
+int mvml_tanh_bwd(int64_t n, const float* y, const float* g_y, float* g_x, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

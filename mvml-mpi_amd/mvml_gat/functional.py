@@ -3428,3 +3428,94 @@ class NodeReadoutFunction(torch.autograd.Function):
         g_rows = SegmentPoolFunction.backward(ctx.pool, Gp)[0]
         gx, gWp, gbp = linear_backward(h, Wp, g_rows, lm, need_gx=ctx.needs_input_grad[0])
         return gx, _dense(gWp[:T]), _dense(gbp[:T]), None, None
+
+
+# ---- Weave: the Gaussian-histogram readout on csrc/weave_gather.hip ("Weave") -----------
+WEAVE_MAX_MEMBERSHIPS = 16  # mvml_weave_gather_fwd
+WEAVE_MAX_GATHER_F = 1024
+# dgllife's default memberships (mean, std)
+WEAVE_MEMBERSHIPS = ((-1.645, 0.283), (-1.080, 0.170), (-0.739, 0.134), (-0.468, 0.118), (-0.228, 0.114), (0., 0.114),
+                     (0.228, 0.114), (0.468, 0.118), (0.739, 0.134), (1.080, 0.170), (1.645, 0.283))
+
+
+def weave_gather_check(who, F, memberships=None):
+    """What mvml_weave_gather_* take: F a multiple of 4 in [4, 1024]; 1 to 16 memberships, every mean
+    finite and every std > 0."""
+    if not isinstance(F, int) or F < 4 or F % 4 or F > WEAVE_MAX_GATHER_F:
+        raise ValueError(f"{who}: node_in_feats must be a multiple of 4 in [4, {WEAVE_MAX_GATHER_F}] on the HIP path (got {F})")
+    if memberships is None:
+        return
+    if not 1 <= len(memberships) <= WEAVE_MAX_MEMBERSHIPS:
+        raise ValueError(f"{who}: 1 to {WEAVE_MAX_MEMBERSHIPS} gaussian memberships on the HIP path (got {len(memberships)})")
+    for mean, std in memberships:
+        if not (np.isfinite(mean) and np.isfinite(std) and std > 0 and np.isfinite(np.float32(1) / np.float32(std) ** 2)):
+            raise ValueError(f"{who}: every membership needs a finite mean and a std > 0 (got ({mean}, {std}))")
+
+
+def weave_gather_bytes(B, N, F, K):
+    """Algorithmic bytes of one mvml_weave_gather_fwd: the [N, F] rows once, the [B, F K] rows once, the
+    offsets.  The backward reads both and writes [N, F] more."""
+    return 4 * (N * F + B * F * K) + 8 * (B + 1)
+
+
+def weave_gather_exps(N, F, K):
+    """exp evaluations of one mvml_weave_gather_fwd or _bwd (the backward recomputes them)."""
+    return N * F * K
+
+
+def _host_floats(vals):
+    return (ctypes.c_float * len(vals))(*vals)
+
+
+class WeaveGatherFunction(torch.autograd.Function):
+    """WeaveGather's histogram and node sum as one node: out[g, f K + k] = sum over g's atoms of
+    p_k(X[n, f]) (mvml_weave_gather_fwd / _bwd); [N, F K] is never formed.  means, stds: K host floats
+    each (they take no gradient).  Returns (B, F K)."""
+
+    @staticmethod
+    def forward(ctx, X, g, means, stds):
+        _check_cuda_f32(X, "node_feats")
+        X = _rows_f32(X)
+        (N, F), K, B, dev = X.shape, len(means), g.batch_size, X.device
+        weave_gather_check("WeaveGatherFunction", F, list(zip(means, stds)))
+        mu, sd = _host_floats(means), _host_floats(stds)
+        out = torch.empty((B, F * K), dtype=torch.float32, device=dev)
+        _lib.call_tag[0] = {"layer": f"F{F}xK{K}", "bytes": weave_gather_bytes(B, N, F, K)}
+        call("mvml_weave_gather_fwd", B, N, F, K, mu, sd, ptr(g.node_offsets), ptr(X), X.stride(0), ptr(out), F * K, _stream(dev))
+        ctx.save_for_backward(X)
+        ctx.state = (g, mu, sd, K)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        (X,) = ctx.saved_tensors
+        g, mu, sd, K = ctx.state
+        G = _rows_f32(g_out)
+        N, F = X.shape
+        B = g.batch_size
+        # (rows of atoms outside every molecule cannot exist: node_offsets covers [0, N))
+        gX = torch.empty((N, F), dtype=torch.float32, device=X.device)
+        _lib.call_tag[0] = {"layer": f"F{F}xK{K}", "bytes": weave_gather_bytes(B, N, F, K) + 4 * N * F}
+        call("mvml_weave_gather_bwd", B, N, F, K, mu, sd, ptr(g.node_offsets), ptr(X), X.stride(0), ptr(G), G.stride(0),
+             ptr(gX), F, _stream(X.device))
+        return gX, None, None, None
+
+
+class LinearTanhFunction(torch.autograd.Function):
+    """tanh(x W^T + b): the GEMM with its bias epilogue, mvml_tanh_fwd in place; the backward takes
+    1 - y^2 from the output (mvml_tanh_bwd) and runs the Linear's three products."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        _check_cuda_f32(x, "x")
+        x, weight, y, ctx.lm = linear_forward(x, weight, bias)
+        call("mvml_tanh_fwd", y.numel(), ptr(y), ptr(y), _stream(y.device))
+        ctx.save_for_backward(x, weight, y)
+        return y
+
+    @staticmethod
+    def backward(ctx, g_y):
+        x, weight, y = ctx.saved_tensors
+        g_pre = torch.empty_like(y)
+        call("mvml_tanh_bwd", y.numel(), ptr(y), ptr(_c(g_y)), ptr(g_pre), _stream(y.device))
+        return linear_backward(x, weight, g_pre, ctx.lm, need_gx=ctx.needs_input_grad[0])

@@ -1587,3 +1587,57 @@ class SchNetPredictor(nn.Module):
 
     def forward(self, g, node_types, edge_dists):
         return self.readout(g, self.gnn(g, node_types, edge_dists))
+
+
+class WeaveGather(nn.Module):
+    """dgllife.model.readout.weave_readout.WeaveGather (0.3.0; restated, parity with dgllife is
+    unpinned): with gaussian_expand every atom value x is spread over the K Gaussian memberships,
+    q_k = exp(-(x - mean_k)^2 / (2 std_k^2)) + 1e-7, p_k = q_k / sum_j q_j, laid out [N, F, K] -> [N, F K]
+    (column f K + k), summed per molecule, then to_out = Linear(K F, F) and the activation.  The
+    histogram and the sum are ONE kernel (Fn.WeaveGatherFunction, csrc/weave_gather.hip): [N, F K] is
+    never formed.  The memberships are the non-trainable parameter lists means.{k} / stds.{k}
+    (dgllife's 11 defaults when gaussian_memberships is None); their values reach the kernel as
+    arguments and are read back from the device once per value, not per step.  Without
+    gaussian_expand: the plain per-molecule sum (mvml_segment_pool_fwd) and nothing else.
+    forward(g, node_feats) -> (B, node_in_feats).  Refused at construction: node_in_feats no multiple
+    of 4 or above 1024, more than 16 memberships or none, a std <= 0, an activation other than
+    nn.Tanh() or None."""
+
+    _check_graph = GATConv._check_graph
+    _allow_zero_in_degree = True  # (the readout never looks at an edge)
+
+    def __init__(self, node_in_feats, gaussian_expand=True, gaussian_memberships=None, activation=nn.Tanh()):
+        super().__init__()
+        if activation is not None and not isinstance(activation, nn.Tanh):
+            raise ValueError("WeaveGather: activation must be nn.Tanh() or None on the HIP path")
+        self.gaussian_expand = gaussian_expand
+        if not gaussian_expand:
+            Fn.weave_gather_check("WeaveGather", node_in_feats)
+            return
+        if gaussian_memberships is None:
+            gaussian_memberships = Fn.WEAVE_MEMBERSHIPS
+        members = [(float(m), float(s)) for m, s in gaussian_memberships]
+        Fn.weave_gather_check("WeaveGather", node_in_feats, members)
+        self.means = nn.ParameterList(nn.Parameter(torch.tensor(m), requires_grad=False) for m, _ in members)
+        self.stds = nn.ParameterList(nn.Parameter(torch.tensor(s), requires_grad=False) for _, s in members)
+        self.to_out = nn.Linear(node_in_feats * len(members), node_in_feats)
+        self.activation = activation
+        self._members = None  # (key, means, stds): the host copy the kernel arguments are made from
+
+    def memberships(self):
+        """The K (means, stds) as host floats, re-read when a parameter's value or storage changed."""
+        ps = [*self.means, *self.stds]
+        key = tuple((p._version, p.data_ptr()) for p in ps)
+        if self._members is None or self._members[0] != key:
+            vals = [float(p) for p in ps]
+            self._members = (key, vals[:len(self.means)], vals[len(self.means):])
+        return self._members[1], self._members[2]
+
+    def forward(self, g, node_feats):
+        self._check_graph(g)
+        if not self.gaussian_expand:
+            return Fn.SegmentPoolFunction.apply(node_feats, g, "sum")
+        from .fusion import LinearFunction
+        hist = Fn.WeaveGatherFunction.apply(node_feats, g, *self.memberships())
+        fn = LinearFunction if self.activation is None else Fn.LinearTanhFunction
+        return fn.apply(hist, self.to_out.weight, self.to_out.bias)
