@@ -1563,6 +1563,65 @@ int mvml_weave_gather_bwd(int64_t B, int64_t N, int F, int K, const float* means
 int mvml_tanh_fwd(int64_t n, const float* x, float* y, void* stream);
 int mvml_tanh_bwd(int64_t n, const float* y, const float* g_y, float* g_x, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Weave's pair-update layer (dgllife 0.3.0 WeaveLayer; restated, parity with dgllife unpinned;
+ * csrc/weave_pair.hip, DESIGN.md "Weave: the pair update").  All fp32, every per-edge matrix in
+ * in-CSR SLOT order.  For s = (u -> v), u = in_src[s], v = slot_dst[s], with the widths De (edge_in),
+ * Hee (edge_edge), Hen (edge_node), Hne (node_edge), Heo (edge_out), each in [1, 128]:
+ *   third_s = relu(e_s W_ee^T + b_ee)                    pair_s = relu(L[u] + R[v]) + relu(R[u] + L[v])
+ *   e'_s = relu([pair_s | third_s] W_ue^T + b_ue)        S[v] = sum over v's in-slots of relu(e_s W_en^T + b_en)
+ * W_ee [Hee][De], W_en [Hen][De], W_ue [Heo][Hne + Hee] dense.  LR [N][ldlr] holds L in columns
+ * [0, Hne) and R in [r_off, r_off + Hne), r_off a multiple of 4 >= Hne, with zeros from Hne up to the next
+ * multiple of 4 in both parts.  Split-fp16 MFMA products on 128-slot tiles, every A row split with its
+ * own scale; K is padded to 32s and N to 16-column blocks inside the kernels.  A matrix of w columns
+ * has a 16-byte aligned base and a pitch that is a multiple of 4 and at least w; its columns from w up
+ * to the next multiple of 4 are written as zeros and may hold anything on input.  Anything else, a NULL
+ * pointer, a negative size or one of 2^31 - 128 and more: MVML_ERR_INVALID before any launch, nothing
+ * written.  num_edges == 0: MVML_OK (mvml_weave_e2n_fwd still writes its zero rows).  No float atomics:
+ * bitwise repeatable.
+ *
+ * mvml_weave_split_w: the three maxima and the split-fp16 images in MFMA fragment order of W_ee, W_en,
+ *   W_ue's pair and third column blocks, and those two transposed; mvml_weave_image_bytes(...) bytes (0:
+ *   a bad width); once per weight value.  W_ee and W_ue may both be NULL (a node-only layer).
+ * mvml_weave_edge_fwd: e' [E][ldo] from e [E][lde] and LR; third stays on the CU.  A, when not NULL,
+ *   receives the second product's operand: pair in columns [0, Hne), third in [ao, ao + Hee), ao = Hne
+ *   rounded up to 4, pitch lda >= ao + Hee rounded up to 4.
+ * mvml_weave_edge_bwd: from g_out = dL/de', e' and A: dpre = g_out * (e' > 0) [E][ldp];
+ *   dfs [E][ldf] = [dfirst | dsecond] (dsecond from column ao on, ldf >= 2 ao) with dfirst = dA[:, :Hne] *
+ *   (L[u] + R[v] > 0), dsecond = dA[:, :Hne] * (R[u] + L[v] > 0), dA = dpre W_ue; dthird [E][ldt] =
+ *   dA[:, Hne:] * (third > 0).
+ * mvml_weave_e2n_fwd: S [N][lds] (lds >= Hen, any alignment), every row written; the product, the ReLU
+ *   and the destination sum in one kernel, runs cut by a tile through fixed-order partials in the
+ *   workspace (mvml_weave_e2n_workspace_size(num_edges, Hen) bytes).
+ * mvml_weave_e2n_bwd: dpre [E][ldd] = dS[slot_dst[s]] * (e_s W_en^T + b_en > 0), the pre-activation
+ *   recomputed with the forward's bits.
+ * mvml_weave_permute_rows: dst[in_eid[s]] = src[s] (scatter != 0: slot order to edge-id order) or
+ *   dst[s] = src[in_eid[s]] (edge-id order to slot order), cols floats per row, any pitches >= cols.
+ * ------------------------------------------------------------------------------------- */
+size_t mvml_weave_image_bytes(int De, int Hee, int Hen, int Hne, int Heo);
+int mvml_weave_split_w(int De, int Hee, int Hen, int Hne, int Heo, const float* W_ee, const float* W_en,
+                       const float* W_ue, void* image, void* stream);
+int mvml_weave_edge_fwd(int64_t num_nodes, int64_t num_edges, const int32_t* in_src, const int32_t* slot_dst,
+                        const float* e, int64_t lde, int De, const float* LR, int64_t ldlr, int r_off, int Hne,
+                        int Hee, int Hen, int Heo, const void* image, const float* b_ee, const float* b_ue,
+                        float* out, int64_t ldo, float* A, int64_t lda, void* stream);
+int mvml_weave_edge_bwd(int64_t num_nodes, int64_t num_edges, const int32_t* in_src, const int32_t* slot_dst,
+                        const float* g_out, int64_t ldg, const float* out, int64_t ldo, const float* A,
+                        int64_t lda, const float* LR, int64_t ldlr, int r_off, int De, int Hne, int Hee,
+                        int Hen, int Heo, const void* image, float* dpre, int64_t ldp, float* dfs, int64_t ldf,
+                        float* dthird, int64_t ldt, void* stream);
+size_t mvml_weave_e2n_workspace_size(int64_t num_edges, int Hen);
+int mvml_weave_e2n_fwd(int64_t num_nodes, int64_t num_edges, const int32_t* in_rowptr, const int32_t* slot_dst,
+                       const float* e, int64_t lde, int De, int Hee, int Hen, int Hne, int Heo,
+                       const void* image, const float* b_en, float* S, int64_t lds, void* workspace,
+                       size_t workspace_bytes, void* stream);
+int mvml_weave_e2n_bwd(int64_t num_nodes, int64_t num_edges, const int32_t* slot_dst, const float* e,
+                       int64_t lde, int De, int Hee, int Hen, int Hne, int Heo, const void* image,
+                       const float* b_en, const float* dS, int64_t ldds, float* dpre, int64_t ldd,
+                       void* stream);
+int mvml_weave_permute_rows(int64_t num_edges, int cols, const int32_t* in_eid, const float* src, int64_t lds,
+                            float* dst, int64_t ldd, int scatter, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,7 +29,8 @@ FLAGS = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-Wno-
 NO_PACKED_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {"afp_agg.hip": NO_PACKED_F32, "gru.hip": NO_PACKED_F32, "attn_pool.hip": NO_PACKED_F32,
                "nnconv.hip": NO_PACKED_F32, "nnconv_wgrad.hip": NO_PACKED_F32,
-               "dmpnn.hip": NO_PACKED_F32, "schnet.hip": NO_PACKED_F32, "weave_gather.hip": NO_PACKED_F32}
+               "dmpnn.hip": NO_PACKED_F32, "schnet.hip": NO_PACKED_F32, "weave_gather.hip": NO_PACKED_F32,
+               "weave_pair.hip": NO_PACKED_F32}
 
 
 def sources():

@@ -26,12 +26,12 @@ from .nn import AttentiveFPGNN, AttentiveFPPredictor, AttentiveFPReadout
 from .nn import MPNNGNN, MPNNPredictor, NNConv
 from .nn import DMPNNGNN, DMPNNPredictor
 from .nn import CFConv, Interaction, MLPNodeReadout, RBFExpansion, SchNetGNN, SchNetPredictor, ShiftedSoftplus
-from .nn import WeaveGather
+from .nn import WeaveGather, WeaveGNN, WeaveLayer, WeavePredictor
 from .optim import FlatAdam
 from .mvp import MVP
 from .metrics import MultiLabelMeter, evaluate, evaluate_class_wise
 
 __all__ = ["MultiLabelMeter", "evaluate", "evaluate_class_wise","GNNModule", "MVFusion", "FPNModule", "RNNModule", "tokens_struct", "collate_smiles", "bce_with_logits", "GAT", "GATLayer", "GATConv", "GATv2", "GATv2Layer", "GATv2Conv", "Set2Set", "WeightAndSum", "WeightedSumAndMax", "GATPredictor", "GATv2Predictor", "MLPPredictor", "GraphConv", "GCNLayer", "GCN", "GCNPredictor", "SAGEConv", "GraphSAGE", "GraphSAGEPredictor", "GINLayer", "GIN", "GINPredictor", "AttentiveFPGNN", "AttentiveFPReadout", "AttentiveFPPredictor", "NNConv", "MPNNGNN", "MPNNPredictor", "DMPNNGNN", "DMPNNPredictor", "ShiftedSoftplus", "RBFExpansion", "CFConv", "Interaction", "SchNetGNN",
-           "MLPNodeReadout", "SchNetPredictor", "WeaveGather", "GraphNorm", "BatchedMolGraph",
+           "MLPNodeReadout", "SchNetPredictor", "WeaveGather", "WeaveLayer", "WeaveGNN", "WeavePredictor", "GraphNorm", "BatchedMolGraph",
            "MolGraph", "batch", "graph", "bigraph_from_bonds", "from_arrays", "lib", "MvmlError", "FlatAdam", "MVP"]
 __version__ = "0.1.0"

@@ -3519,3 +3519,241 @@ class LinearTanhFunction(torch.autograd.Function):
         g_pre = torch.empty_like(y)
         call("mvml_tanh_bwd", y.numel(), ptr(y), ptr(_c(g_y)), ptr(g_pre), _stream(y.device))
         return linear_backward(x, weight, g_pre, ctx.lm, need_gx=ctx.needs_input_grad[0])
+
+
+# ---- Weave: the pair-update layer on csrc/weave_pair.hip ("Weave: the pair update") -----
+WEAVE_MAX_WIDTH = 128  # every width of mvml_weave_edge_* / mvml_weave_e2n_*
+WEAVE_WIDTHS = ("node_node_hidden_feats", "edge_node_hidden_feats", "node_out_feats", "node_edge_hidden_feats",
+                "edge_edge_hidden_feats", "edge_out_feats")
+
+
+def weave_check(who, node_in_feats, edge_in_feats, widths, slot_input=False):
+    """What a WeaveLayer takes on the HIP path: every hidden and output width and a slot-order edge input in
+    [1, 128]; a user's edge_in_feats (edge-id order, through mvml_afp_edge_rows) in [1, 32]."""
+    for name, w in zip(WEAVE_WIDTHS, widths):
+        if not isinstance(w, int) or not 1 <= w <= WEAVE_MAX_WIDTH:
+            raise ValueError(f"{who}: {name} must be in [1, {WEAVE_MAX_WIDTH}] on the HIP path (got {w})")
+    hi = WEAVE_MAX_WIDTH if slot_input else AFP_MAX_EDGE_FEATS
+    if not isinstance(edge_in_feats, int) or not 1 <= edge_in_feats <= hi:
+        raise ValueError(f"{who}: edge_in_feats must be in [1, {hi}] on the HIP path (got {edge_in_feats})")
+    if not isinstance(node_in_feats, int) or node_in_feats < 1:
+        raise ValueError(f"{who}: node_in_feats must be positive (got {node_in_feats})")
+
+
+def weave_edge_flops(E, De, Hne, Hee, Heo):
+    """Useful flops of one mvml_weave_edge_fwd: the two products per edge (the MFMA work is three times
+    that, before the padding of K to 32s and of N to 16s); the backward's are 2 E Heo (Hne + Hee)."""
+    return 2 * E * (De * Hee + (Hne + Hee) * Heo)
+
+
+def weave_edge_fwd_bytes(N, E, De, Hne, Hee, Heo, grad=False):
+    """Algorithmic bytes of one mvml_weave_edge_fwd: e read, e' written (and the [pair | third] operand when
+    a gradient is wanted), both index lists, the LR rows once (re-gathers not counted), the three images."""
+    return 4 * (E * (De + Heo + (Hne + Hee if grad else 0) + 2) + 2 * N * Hne + De * Hee + (Hne + Hee) * Heo)
+
+
+def weave_edge_bwd_bytes(N, E, Hne, Hee, Heo):
+    """Algorithmic bytes of one mvml_weave_edge_bwd: g, e' and third read, dpre, dfirst, dsecond and dthird
+    written, both index lists, the LR rows once, the transposed images."""
+    return 4 * (E * (3 * Heo + 2 * Hee + 2 * Hne + 2) + 2 * N * Hne + (Hne + Hee) * Heo)
+
+
+def weave_e2n_flops(E, De, Hen):
+    return 2 * E * De * Hen
+
+
+def weave_e2n_bytes(N, E, De, Hen, backward=False):
+    """Algorithmic bytes of mvml_weave_e2n_fwd (e read, S written, the destinations) or _bwd (e and dS read,
+    dpre written)."""
+    return 4 * (E * (De + 1 + (Hen if backward else 0)) + N * (Hen + 1) + De * Hen)
+
+
+def weave_image(De, Hee, Hen, Hne, Heo, W_ee, W_en, W_ue):
+    """The maxima and split-fp16 images of a layer's three edge-side weights (mvml_weave_split_w); W_ee and
+    W_ue None: a node-only layer's."""
+    nbytes = _lib.lib().mvml_weave_image_bytes(De, Hee, Hen, Hne, Heo)
+    if nbytes == 0:
+        raise ValueError(f"WeaveLayer: every width must be in [1, {WEAVE_MAX_WIDTH}] (got {(De, Hee, Hen, Hne, Heo)})")
+    img = torch.empty(nbytes, dtype=torch.uint8, device=W_en.device)
+    call("mvml_weave_split_w", De, Hee, Hen, Hne, Heo, ptr(W_ee), ptr(W_en), ptr(W_ue), ptr(img), _stream(W_en.device))
+    return img
+
+
+def weave_permute_rows(g, rows, cols, to_edges):
+    """[E, cols] dense: slot-order rows in edge-id order (to_edges) or the reverse (mvml_weave_permute_rows)."""
+    E = g.num_edges()
+    out = torch.empty((E, cols), dtype=torch.float32, device=rows.device)
+    call("mvml_weave_permute_rows", E, cols, ptr(g.in_eid), ptr(rows), rows.stride(0) if E else cols, ptr(out), cols,
+         int(to_edges), _stream(rows.device))
+    return out
+
+
+class WeaveEdgeOrderFunction(torch.autograd.Function):
+    """Slot-order edge rows in edge-id order (what a WeaveLayer hands back to its caller); the backward is
+    the reverse permutation."""
+
+    @staticmethod
+    def forward(ctx, rows, g):
+        ctx.g = g
+        return weave_permute_rows(g, _rows_f32(rows), rows.shape[1], True)
+
+    @staticmethod
+    def backward(ctx, g_out):
+        return weave_permute_rows(ctx.g, _rows_f32(g_out), g_out.shape[1], False), None
+
+
+def _rows4(t):
+    """t as rows the pair-update kernels read in place (_rows_f32), else a copy at a pitch rounded up to a
+    multiple of 4 (mvml_copy_cols); the pad columns are never used."""
+    r = _rows_f32(t)
+    if r.shape[0] == 0 or (r.stride(0) % 4 == 0 and r.data_ptr() % 16 == 0):
+        return r
+    buf = torch.empty((r.shape[0], _round4(r.shape[1])), dtype=torch.float32, device=r.device)
+    copy2d(buf[:, :r.shape[1]], r)
+    return buf[:, :r.shape[1]]
+
+
+def _relu_bwd(y, g_y):
+    g_x = torch.empty_like(y)
+    call("mvml_relu_bwd", y.numel(), ptr(y), ptr(_c(g_y)), ptr(g_x), 1.0, _stream(y.device))
+    return g_x
+
+
+class WeaveLayerFunction(torch.autograd.Function):
+    """One WeaveLayer as ONE autograd node with its fourteen parameters as leaves; returns (x', e') with e'
+    [E, edge_out] in in-CSR slot order (None with node_only).  slot_in: edge_feats are already in slot
+    order (a previous layer's e'), else in edge-id order and brought over once by mvml_afp_edge_rows.
+    Node side on the GEMM: relu(node_to_node(x)); S = the destination sums of relu(edge_to_node(e))
+    (mvml_weave_e2n_fwd, no [E, H] array); update_node without its concat, as two products, the second onto
+    the first with the ReLU in its epilogue.  Edge side: LR = x [W_left ; W_right]^T in one product (each
+    half padded to a multiple of 4 rows), then mvml_weave_edge_fwd.  Backward: mvml_weave_edge_bwd, the
+    weight and bias gradients on the GEMM and mvml_colsum_f32, dLR as two mvml_dmpnn_atom_sum calls (over the
+    in-slots the halves land swapped), mvml_weave_e2n_bwd, then the node side's Linears.  With node_only
+    the four edge-side Linears get no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, e, g, node_only, slot_in, W_nn, b_nn, W_en, b_en, W_un, b_un, W_l, b_l, W_r, b_r, W_ee, b_ee,
+                W_ue, b_ue):
+        _check_cuda_f32(x, "node_feats")
+        _check_cuda_f32(e, "edge_feats")
+        N, E, dev = g.num_nodes(), g.num_edges(), x.device
+        if x.dim() != 2 or x.shape[0] != N or x.shape[1] != W_nn.shape[1]:
+            raise ValueError(f"WeaveLayer: node_feats must be [N = {N}, {W_nn.shape[1]}] (got {tuple(x.shape)})")
+        De = W_en.shape[1]
+        if e.dim() != 2 or tuple(e.shape) != (E, De):
+            raise ValueError(f"WeaveLayer: edge_feats must be [E = {E}, {De}] (got {tuple(e.shape)})")
+        Hnn, Hen, Hne, Hee, Heo = W_nn.shape[0], W_en.shape[0], W_l.shape[0], W_ee.shape[0], W_ue.shape[0]
+        erows = _rows4(e) if slot_in else afp_edge_rows(g, e)
+        lde = erows.stride(0) if E else _round4(De)
+        W_en, b_en, W_ee, b_ee, W_ue, b_ue = (_c(t) for t in (W_en, b_en, W_ee, b_ee, W_ue, b_ue))
+        image = weave_image(De, Hee, Hen, Hne, Heo, None if node_only else W_ee, W_en, None if node_only else W_ue)
+        dims = (De, Hee, Hen, Hne, Heo)
+        st = _stream(dev)
+        # node side
+        x, W_nn, hn, lm_nn = linear_forward(x, W_nn, b_nn, act=1)
+        S = torch.empty((N, Hen), dtype=torch.float32, device=dev)
+        wp, wn = _lib.ws_ptr_size(_lib.lib().mvml_weave_e2n_workspace_size(E, Hen), dev)
+        _lib.call_tag[0] = {"layer": f"De{De}xH{Hen}", "flops": weave_e2n_flops(E, De, Hen),
+                            "bytes": weave_e2n_bytes(N, E, De, Hen)}
+        call("mvml_weave_e2n_fwd", N, E, ptr(g.in_rowptr), ptr(nnconv_slot_dst(g)), ptr(erows), lde, De, Hee, Hen, Hne, Heo,
+             ptr(image), ptr(b_en), ptr(S), Hen, wp, wn, st)
+        W_un = _c(W_un)
+        WunN, WunS = _dense(W_un[:, :Hnn]), _dense(W_un[:, Hnn:])
+        hn, WunN, y, lmN = linear_forward(hn, WunN, b_un)
+        S, WunS, xn, lmS = linear_forward(S, WunS, None, act=1, onto=y)
+        ctx.dims, ctx.node_only, ctx.slot_in = dims, node_only, slot_in
+        # (the outputs and the large rows go through save_for_backward, not into the node's own state)
+        ctx.node = (g, W_nn, lm_nn, WunN, lmN, WunS, lmS, lde, image, W_en, b_en)
+        ctx.edge = None
+        if node_only:
+            ctx.save_for_backward(xn, x, hn, S, erows)
+            return xn, None
+        # edge side.  The stacked [W_left ; W_right], like update_node's two column blocks and the weight
+        # images above, is rebuilt on every call by design: a handful of small launches per layer, which
+        # keeps the parameters the only state between steps (it shows on small batches only).
+        Hq = _round4(Hne)
+        Wlr, blr = zeros((2 * Hq, x.shape[1]), device=dev), zeros(2 * Hq, device=dev)
+        for off, W, b in ((0, W_l, b_l), (Hq, W_r, b_r)):
+            copy2d(Wlr[off:off + Hne], _c(W))
+            copy2d(blr[off:off + Hne], _c(b))
+        x, Wlr, LR, lm_lr = linear_forward(x, Wlr, blr)
+        Ho4, lda = _round4(Heo), Hq + _round4(Hee)
+        en = torch.empty((E, Ho4), dtype=torch.float32, device=dev)
+        A = torch.empty((E, lda), dtype=torch.float32, device=dev) if any(ctx.needs_input_grad) else None
+        if E:
+            _lib.call_tag[0] = {"layer": f"De{De}xH{Heo}", "flops": weave_edge_flops(E, De, Hne, Hee, Heo),
+                                "bytes": weave_edge_fwd_bytes(N, E, De, Hne, Hee, Heo, A is not None)}
+            call("mvml_weave_edge_fwd", N, E, ptr(g.in_src), ptr(nnconv_slot_dst(g)), ptr(erows), lde, De, ptr(LR), 2 * Hq, Hq,
+                 Hne, Hee, Hen, Heo, ptr(image), ptr(b_ee), ptr(b_ue), ptr(en), Ho4, ptr(A), lda, st)
+        ctx.edge = (Wlr, lm_lr, W_ee, W_ue)
+        en = en[:, :Heo]
+        ctx.save_for_backward(xn, x, hn, S, erows, en, LR, A)
+        return xn, en
+
+    @staticmethod
+    def backward(ctx, g_xn, g_en):
+        g, W_nn, lm_nn, WunN, lmN, WunS, lmS, lde, image, W_en, b_en = ctx.node
+        xn, x, hn, S, erows = ctx.saved_tensors[:5]
+        De, Hee, Hen, Hne, Heo = ctx.dims
+        N, E, dev = g.num_nodes(), g.num_edges(), x.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        st = _stream(dev)
+        need_gx, need_ge = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        De4 = _round4(De)
+        de = torch.empty((E, De4), **f32) if need_ge else None
+        # node side down to dS and the node_to_node branch
+        g_pre = _relu_bwd(xn, g_xn)
+        dS, gWunS, _ = linear_backward(S, WunS, g_pre, lmS, need_gb=False)
+        dhn, gWunN, gb_un = linear_backward(hn, WunN, g_pre, lmN)
+        gx, gW_nn, gb_nn = linear_backward(x, W_nn, _relu_bwd(hn, dhn), lm_nn, need_gx=need_gx)
+        gW_un = _dmpnn_join(gWunN, gWunS)
+        new = (lambda shape: torch.empty(shape, **f32)) if E else (lambda shape: zeros(shape, device=dev))  # (no edge: zeros)
+        gW_en, gb_en = new((Hen, De)), new(Hen)
+        if E:
+            ldd = _round4(Hen)
+            dpre_en = torch.empty((E, ldd), **f32)
+            _lib.call_tag[0] = {"layer": f"De{De}xH{Hen}", "flops": weave_e2n_flops(E, De, Hen),
+                                "bytes": weave_e2n_bytes(N, E, De, Hen, True)}
+            call("mvml_weave_e2n_bwd", N, E, ptr(nnconv_slot_dst(g)), ptr(erows), lde, De, Hee, Hen, Hne, Heo, ptr(image),
+                 ptr(b_en), ptr(dS), Hen, ptr(dpre_en), ldd, st)
+            gemm(dpre_en, erows, Hen, De, E, 1, 1, ldd, lde, gW_en, De)  # dpre_en^T e
+            colsum(dpre_en, E, Hen, ldd, gb_en)
+            if need_ge:
+                gemm(dpre_en, W_en, E, De, Hen, 0, 1, ldd, De, de, De4)
+        edge_grads = (None,) * 8
+        if ctx.edge is not None:
+            Wlr, lm_lr, W_ee, W_ue = ctx.edge
+            en, LR, A = ctx.saved_tensors[5:]  # (en: the [:, :Heo] view of its [E, Ho4] rows)
+            Hq, Ho4, He4 = _round4(Hne), _round4(Heo), _round4(Hee)
+            lda = Hq + He4
+            gW_ue, gb_ue, gW_ee, gb_ee = new((Heo, Hne + Hee)), new(Heo), new((Hee, De)), new(Hee)
+            dfs = torch.empty((E, 2 * Hq), **f32)
+            if E:
+                G = _rows4(g_en)
+                dpre, dthird = torch.empty((E, Ho4), **f32), torch.empty((E, He4), **f32)
+                _lib.call_tag[0] = {"layer": f"De{De}xH{Heo}", "flops": 2 * E * Heo * (Hne + Hee),
+                                    "bytes": weave_edge_bwd_bytes(N, E, Hne, Hee, Heo)}
+                call("mvml_weave_edge_bwd", N, E, ptr(g.in_src), ptr(nnconv_slot_dst(g)), ptr(G), G.stride(0), ptr(en), Ho4,
+                     ptr(A), lda, ptr(LR), 2 * Hq, Hq, De, Hne, Hee, Hen, Heo, ptr(image), ptr(dpre), Ho4, ptr(dfs), 2 * Hq,
+                     ptr(dthird), He4, st)
+                gA = torch.empty((Heo, lda), **f32)
+                gemm(dpre, A, Heo, lda, E, 1, 1, Ho4, lda, gA, lda)  # dpre^T [pair | third]
+                copy2d(gW_ue[:, :Hne], gA[:, :Hne])
+                copy2d(gW_ue[:, Hne:], gA[:, Hq:Hq + Hee])
+                colsum(dpre, E, Heo, Ho4, gb_ue)
+                gemm(dthird, erows, Hee, De, E, 1, 1, He4, lde, gW_ee, De)
+                colsum(dthird, E, Hee, He4, gb_ee)
+                if need_ge:
+                    gemm(dthird, W_ee, E, De, Hee, 0, 1, He4, De, de, De4, beta=1.0)
+            # dLR: over the out-edges [dfirst | dsecond] as it lies, over the in-slots with the halves swapped
+            G2, G1 = dmpnn_atom_sum(g, dfs, transpose=True), dmpnn_atom_sum(g, dfs)
+            if N:
+                call("mvml_add_cols_f32", N, Hq, _off(G1, Hq), 2 * Hq, ptr(G2), 2 * Hq, st)
+                call("mvml_add_cols_f32", N, Hq, ptr(G1), 2 * Hq, _off(G2, Hq), 2 * Hq, st)
+            gx, gWlr, gblr = linear_backward(x, Wlr, G2, lm_lr, need_gx=need_gx, gx_acc=gx)
+            edge_grads = (_dense(gWlr[:Hne]), _dense(gblr[:Hne]), _dense(gWlr[Hq:Hq + Hne]), _dense(gblr[Hq:Hq + Hne]),
+                          gW_ee, gb_ee, gW_ue, gb_ue)
+        ge = None
+        if need_ge:
+            ge = _dense(de[:, :De]) if ctx.slot_in or E == 0 else weave_permute_rows(g, de, De, True)
+        return (gx, ge, None, None, None, gW_nn, gb_nn, gW_en, gb_en, gW_un, gb_un, *edge_grads)

@@ -1641,3 +1641,114 @@ class WeaveGather(nn.Module):
         hist = Fn.WeaveGatherFunction.apply(node_feats, g, *self.memberships())
         fn = LinearFunction if self.activation is None else Fn.LinearTanhFunction
         return fn.apply(hist, self.to_out.weight, self.to_out.bias)
+
+
+class WeaveLayer(nn.Module):
+    """dgllife.model.gnn.weave.WeaveLayer (0.3.0; restated, parity with dgllife is unpinned).  With L =
+    left_node_to_edge(x), R = right_node_to_edge(x) and an edge s = (u -> v):
+        x'_v = relu(update_node(cat[relu(node_to_node(x_v)), sum_{s into v} relu(edge_to_node(e_s))]))
+        e'_s = relu(update_edge(cat[relu(L[u] + R[v]) + relu(R[u] + L[v]), relu(edge_to_edge(e_s))]))
+    as one autograd node on the fused kernels of csrc/weave_pair.hip (Fn.WeaveLayerFunction): no [E, H]
+    intermediate is written in the forward.  forward(g, node_feats, edge_feats, node_only=False):
+    edge_feats a float [E, edge_in_feats] tensor in edge-id order; returns (x', e') with e' in edge-id
+    order, or x' alone with node_only.  Graphs are inputs: there is no WeaveEdgeFeaturizer here.  Refused
+    at construction: an activation other than ReLU, a width outside [1, 128], edge_in_feats outside
+    [1, 32]."""
+
+    _check_graph = GATConv._check_graph
+    _allow_zero_in_degree = True  # (an atom without in-edges sums nothing)
+
+    def __init__(self, node_in_feats, edge_in_feats, node_node_hidden_feats=50, edge_node_hidden_feats=50,
+                 node_out_feats=50, node_edge_hidden_feats=50, edge_edge_hidden_feats=50, edge_out_feats=50,
+                 activation=F.relu, _slot_input=False):
+        super().__init__()
+        if not _is_relu(activation):
+            raise ValueError("WeaveLayer: activation must be ReLU (F.relu, torch.relu, nn.ReLU()) on the HIP path")
+        Fn.weave_check("WeaveLayer", node_in_feats, edge_in_feats,
+                       (node_node_hidden_feats, edge_node_hidden_feats, node_out_feats, node_edge_hidden_feats,
+                        edge_edge_hidden_feats, edge_out_feats), slot_input=_slot_input)
+        self._slot_input = _slot_input  # (inside WeaveGNN: the edge state arrives and leaves in in-CSR slot order)
+        self.activation = activation
+        self.node_to_node = nn.Linear(node_in_feats, node_node_hidden_feats)
+        self.edge_to_node = nn.Linear(edge_in_feats, edge_node_hidden_feats)
+        self.update_node = nn.Linear(node_node_hidden_feats + edge_node_hidden_feats, node_out_feats)
+        self.left_node_to_edge = nn.Linear(node_in_feats, node_edge_hidden_feats)
+        self.right_node_to_edge = nn.Linear(node_in_feats, node_edge_hidden_feats)
+        self.edge_to_edge = nn.Linear(edge_in_feats, edge_edge_hidden_feats)
+        self.update_edge = nn.Linear(node_edge_hidden_feats + edge_edge_hidden_feats, edge_out_feats)
+
+    def linears(self):
+        return (self.node_to_node, self.edge_to_node, self.update_node, self.left_node_to_edge,
+                self.right_node_to_edge, self.edge_to_edge, self.update_edge)
+
+    def reset_parameters(self):
+        for lin in self.linears():
+            lin.reset_parameters()
+
+    def slots(self, g, node_feats, edge_feats, node_only=False):
+        """(x', e') with e' in slot order (None with node_only); edge_feats in slot order if the layer was
+        built for it."""
+        self._check_graph(g)
+        params = [p for lin in self.linears() for p in (lin.weight, lin.bias)]
+        return Fn.WeaveLayerFunction.apply(node_feats, edge_feats, g, bool(node_only), self._slot_input, *params)
+
+    def forward(self, g, node_feats, edge_feats, node_only=False):
+        if self._slot_input:
+            raise RuntimeError("WeaveLayer: a layer inside WeaveGNN takes its edge state in slot order; call WeaveGNN")
+        x, e = self.slots(g, node_feats, edge_feats, node_only)
+        return x if node_only else (x, Fn.WeaveEdgeOrderFunction.apply(e, g))
+
+
+class WeaveGNN(nn.Module):
+    """dgllife.model.gnn.weave.WeaveGNN (0.3.0; restated, parity with dgllife is unpinned): num_layers
+    WeaveLayers of width hidden_feats, every layer with all seven Linears; the last is called with
+    node_only.  The edge state stays in in-CSR slot order between the layers.  forward(g, node_feats,
+    edge_feats, node_only=True) returns x', or (x', e') with e' in edge-id order."""
+
+    def __init__(self, node_in_feats, edge_in_feats, num_layers=2, hidden_feats=50, activation=F.relu):
+        super().__init__()
+        if not isinstance(num_layers, int) or num_layers < 1:
+            raise ValueError(f"WeaveGNN: num_layers must be at least 1 (got {num_layers})")
+        h = hidden_feats
+        self.gnn_layers = nn.ModuleList(
+            WeaveLayer(node_in_feats if i == 0 else h, edge_in_feats if i == 0 else h, h, h, h, h, h, h, activation,
+                       _slot_input=i > 0) for i in range(num_layers))
+
+    def reset_parameters(self):
+        for layer in self.gnn_layers:
+            layer.reset_parameters()
+
+    def forward(self, g, node_feats, edge_feats, node_only=True):
+        for layer in self.gnn_layers[:-1]:
+            node_feats, edge_feats = layer.slots(g, node_feats, edge_feats)
+        x, e = self.gnn_layers[-1].slots(g, node_feats, edge_feats, node_only)
+        return x if node_only else (x, Fn.WeaveEdgeOrderFunction.apply(e, g))
+
+
+class WeavePredictor(nn.Module):
+    """dgllife.model.model_zoo.weave_predictor.WeavePredictor (0.3.0; restated, parity with dgllife is
+    unpinned): gnn = WeaveGNN -> node_to_graph = Sequential(Linear(gnn_hidden_feats, graph_feats), Tanh,
+    BatchNorm1d) (Fn.LinearTanhFunction, the BatchNorm1d kernels) -> readout = WeaveGather -> predict =
+    Linear(graph_feats, n_tasks).  forward(g, node_feats, edge_feats) returns (B, n_tasks).  Refused at
+    construction: what WeaveGNN and WeaveGather refuse (graph_feats a multiple of 4 in [4, 1024]) and a
+    readout_activation other than nn.Tanh()."""
+
+    def __init__(self, node_in_feats, edge_in_feats, num_gnn_layers=2, gnn_hidden_feats=50, gnn_activation=F.relu,
+                 graph_feats=128, gaussian_expand=True, gaussian_memberships=None, readout_activation=nn.Tanh(),
+                 n_tasks=1):
+        super().__init__()
+        if not isinstance(readout_activation, nn.Tanh):
+            raise ValueError("WeavePredictor: readout_activation must be nn.Tanh() on the HIP path")
+        self.gnn = WeaveGNN(node_in_feats, edge_in_feats, num_gnn_layers, gnn_hidden_feats, gnn_activation)
+        Fn.weave_gather_check("WeavePredictor (graph_feats)", graph_feats)
+        self.node_to_graph = nn.Sequential(nn.Linear(gnn_hidden_feats, graph_feats), readout_activation,
+                                           nn.BatchNorm1d(graph_feats))
+        self.readout = WeaveGather(graph_feats, gaussian_expand, gaussian_memberships, readout_activation)
+        self.predict = nn.Linear(graph_feats, n_tasks)
+
+    def forward(self, g, node_feats, edge_feats):
+        from .fusion import LinearFunction
+        h = self.gnn(g, node_feats, edge_feats, node_only=True)
+        h = Fn.LinearTanhFunction.apply(h, self.node_to_graph[0].weight, self.node_to_graph[0].bias)
+        h = Fn.batch_norm1d(h, self.node_to_graph[2])
+        return LinearFunction.apply(self.readout(g, h), self.predict.weight, self.predict.bias)

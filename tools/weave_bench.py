@@ -12,6 +12,15 @@ default memberships:
     composition (the [N, F K] histogram by torch, then mvml_segment_pool_fwd over it; in this tool only), and
     the norm-wise distance of the two results.
 
+The pair-update layers (csrc/weave_pair.hip), on the same batch with 12 bond features, every width H = 50
+(dgllife's default) and 128:
+  * mvml_weave_split_w, mvml_weave_edge_fwd (with and without the saved operand), mvml_weave_edge_bwd,
+    mvml_weave_e2n_fwd and mvml_weave_e2n_bwd against their algorithmic bytes and useful flops;
+  * one WeaveLayer forward + backward and one WeavePredictor step at the defaults;
+  * at --small-mols molecules: the fused edge forward against the composition that materialises first,
+    second, their sum, third and the concat (products on the project's GEMM, the rest by torch; in this
+    tool only), their ratio and distance.
+
 The atom values are drawn from tanh of a unit normal, the range WeavePredictor's node_to_graph hands the
 readout; the timings do not depend on the values beyond exp's range.
 
@@ -109,11 +118,118 @@ def bench_module(g, F):
             "max_memory_gb": torch.cuda.max_memory_allocated() / 1e9}
 
 
+def flop_row(name, t, by, flops):
+    r = row(name, t, by)
+    r.update(flops=flops, tflops=flops / t[0] / 1e9)
+    print(f"  {'':44s} {flops / 1e9:8.2f} GFLOP useful  {r['tflops']:6.2f} TFLOP/s", flush=True)
+    return r
+
+
+def pair_state(g, H, De=12):
+    """Operands of the five kernels of csrc/weave_pair.hip with every width H and De bond features."""
+    N, E = g.num_nodes(), g.num_edges()
+    gen = torch.Generator("cuda").manual_seed(H)
+    rnd = lambda *s: torch.randn(s, device="cuda", generator=gen)
+    Hq, De4 = Fn._round4(H), Fn._round4(De)
+    s = dict(N=N, E=E, H=H, De=De, Hq=Hq, De4=De4, W_ee=rnd(H, De) * De ** -0.5, W_en=rnd(H, De) * De ** -0.5,
+             W_ue=rnd(H, 2 * H) * (2 * H) ** -0.5, b=rnd(H) * 0.1, e=Fn.zeros((E, De4), device="cuda"), LR=Fn.zeros((N, 2 * Hq), device="cuda"),
+             en=torch.empty((E, Hq), device="cuda"), A=torch.empty((E, 2 * Hq), device="cuda"), G=rnd(E, Hq),
+             dpre=torch.empty((E, Hq), device="cuda"), dfs=torch.empty((E, 2 * Hq), device="cuda"),
+             dthird=torch.empty((E, Hq), device="cuda"), S=torch.empty((N, H), device="cuda"), dS=rnd(N, H),
+             dpre_en=torch.empty((E, Hq), device="cuda"), dst=Fn.nnconv_slot_dst(g))
+    s["e"][:, :De] = rnd(E, De)
+    s["LR"][:, :H], s["LR"][:, Hq:Hq + H] = rnd(N, H), rnd(N, H)
+    s["image"] = Fn.weave_image(De, H, H, H, H, s["W_ee"], s["W_en"], s["W_ue"])
+    s["ws"] = torch.empty(_lib.lib().mvml_weave_e2n_workspace_size(E, H), dtype=torch.uint8, device="cuda")
+    return s
+
+
+def pair_calls(g, s):
+    st = _lib.stream_ptr()
+    N, E, H, De, Hq, De4 = (s[k] for k in ("N", "E", "H", "De", "Hq", "De4"))
+    P = lambda k: ptr(s[k])
+
+    def edge_fwd(A):
+        return lambda: call("mvml_weave_edge_fwd", N, E, ptr(g.in_src), P("dst"), P("e"), De4, De, P("LR"), 2 * Hq, Hq, H, H, H, H,
+                            P("image"), P("b"), P("b"), P("en"), Hq, ptr(A), 2 * Hq, st)
+    return {
+        "split_w": lambda: call("mvml_weave_split_w", De, H, H, H, H, P("W_ee"), P("W_en"), P("W_ue"), P("image"), st),
+        "edge_fwd": edge_fwd(None), "edge_fwd_grad": edge_fwd(s["A"]),
+        "edge_bwd": lambda: call("mvml_weave_edge_bwd", N, E, ptr(g.in_src), P("dst"), P("G"), Hq, P("en"), Hq, P("A"), 2 * Hq, P("LR"),
+                                 2 * Hq, Hq, De, H, H, H, H, P("image"), P("dpre"), Hq, P("dfs"), 2 * Hq, P("dthird"), Hq, st),
+        "e2n_fwd": lambda: call("mvml_weave_e2n_fwd", N, E, ptr(g.in_rowptr), P("dst"), P("e"), De4, De, H, H, H, H, P("image"), P("b"),
+                                P("S"), H, P("ws"), s["ws"].numel(), st),
+        "e2n_bwd": lambda: call("mvml_weave_e2n_bwd", N, E, P("dst"), P("e"), De4, De, H, H, H, H, P("image"), P("b"), P("dS"), H,
+                                P("dpre_en"), Hq, st)}
+
+
+def bench_pair_kernels(g, H):
+    s = pair_state(g, H)
+    N, E, De = s["N"], s["E"], s["De"]
+    calls = pair_calls(g, s)
+    calls["edge_fwd_grad"]()  # (the backward reads e' and the saved operand)
+    tm = timed(calls, launches=4, reps=7, warm=2)
+    fl = Fn.weave_edge_flops(E, De, H, H, H)
+    return {"split_w": row(f"weave_split_w H={H}", tm["split_w"]),
+            "edge_fwd": flop_row(f"weave_edge_fwd H={H}", tm["edge_fwd"], Fn.weave_edge_fwd_bytes(N, E, De, H, H, H), fl),
+            "edge_fwd_grad": flop_row(f"weave_edge_fwd H={H} (+ saved operand)", tm["edge_fwd_grad"],
+                                      Fn.weave_edge_fwd_bytes(N, E, De, H, H, H, True), fl),
+            "edge_bwd": flop_row(f"weave_edge_bwd H={H}", tm["edge_bwd"], Fn.weave_edge_bwd_bytes(N, E, H, H, H), 4 * E * H * H),
+            "e2n_fwd": flop_row(f"weave_e2n_fwd H={H}", tm["e2n_fwd"], Fn.weave_e2n_bytes(N, E, De, H), Fn.weave_e2n_flops(E, De, H)),
+            "e2n_bwd": flop_row(f"weave_e2n_bwd H={H}", tm["e2n_bwd"], Fn.weave_e2n_bytes(N, E, De, H, True),
+                                Fn.weave_e2n_flops(E, De, H))}
+
+
+def bench_pair_fused_vs_materialised(g, H):
+    """The fused edge forward against the composition that writes first, second, their sum, third and the
+    concat: the products on the project's GEMM, the gathers and element-wise steps by torch (in this tool only)."""
+    s = pair_state(g, H)
+    Hq, De = s["Hq"], s["De"]
+    src, dst = g.in_src.long(), s["dst"].long()
+    L, R, e = s["LR"][:, :H].contiguous(), s["LR"][:, Hq:Hq + H].contiguous(), s["e"][:, :De].contiguous()
+    box = {}
+
+    def materialised():
+        first, second = torch.relu(L[src] + R[dst]), torch.relu(R[src] + L[dst])
+        third = Fn.linear_forward(e, s["W_ee"], s["b"], act=1)[2]
+        box["out"] = Fn.linear_forward(torch.cat([first + second, third], 1), s["W_ue"], s["b"], act=1)[2]
+    tm = timed({"fused": pair_calls(g, s)["edge_fwd"], "materialised": materialised}, launches=2, reps=7, warm=2)
+    dist = float((s["en"][:, :H] - box["out"]).abs().max() / box["out"].abs().max())
+    print(f"  fused against materialised, max|a - b| / max|b|: {dist:.2e}", flush=True)
+    return {"fused": row(f"edge forward fused H={H} E={s['E']}", tm["fused"]),
+            "materialised": row(f"edge forward materialised H={H}", tm["materialised"]), "distance": dist,
+            "ratio": tm["materialised"][0] / tm["fused"][0]}
+
+
+def bench_pair_modules(g, De=12, Dn=27):
+    from mvml_gat import WeaveLayer, WeavePredictor
+    torch.manual_seed(0)
+    N, E, B = g.num_nodes(), g.num_edges(), g.batch_size
+    x, e = torch.randn((N, Dn), device="cuda").requires_grad_(), torch.randn((E, De), device="cuda")
+    layer, model = WeaveLayer(Dn, De).cuda().train(), WeavePredictor(Dn, De).cuda().train()
+    gx, ge, gy = torch.randn((N, 50), device="cuda"), torch.randn((E, 50), device="cuda"), torch.randn((B, 1), device="cuda")
+
+    def layer_step():
+        layer.zero_grad(set_to_none=True)
+        x.grad = None
+        torch.autograd.backward(list(layer(g, x, e)), [gx, ge])
+
+    def model_step():
+        model.zero_grad(set_to_none=True)
+        x.grad = None
+        model(g, x, e).backward(gy)
+    tm = timed({"layer": layer_step, "predictor": model_step}, launches=2, reps=5, warm=1)
+    return {"layer": row("WeaveLayer H=50 forward + backward", tm["layer"]),
+            "predictor": row("WeavePredictor forward + backward", tm["predictor"]),
+            "max_memory_gb": torch.cuda.max_memory_allocated() / 1e9}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mols", type=int, default=65536)
     ap.add_argument("--small-mols", type=int, default=4096)
     ap.add_argument("--sizes", default="128,64")
+    ap.add_argument("--pair-sizes", default="50,128")
     ap.add_argument("--no-modules", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -128,6 +244,14 @@ def main():
             torch.cuda.empty_cache()
     small = synth.config3(a.small_mols).to_graph().to("cuda")
     res["fused_vs_materialised"] = bench_fused_vs_materialised(small, 128)
+    print("pair-update layers (csrc/weave_pair.hip), 12 bond features:")
+    for H in (int(v) for v in a.pair_sizes.split(",")):
+        res[f"pair_H{H}"] = bench_pair_kernels(g, H)
+        torch.cuda.empty_cache()
+    if not a.no_modules:
+        res["pair_modules"] = bench_pair_modules(g)
+        torch.cuda.empty_cache()
+    res["pair_fused_vs_materialised"] = bench_pair_fused_vs_materialised(small, 50)
     if a.out:
         with open(a.out, "w") as f:
             json.dump(res, f, indent=1)
